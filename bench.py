@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py - atoms*steps/s of AIMNet2 energy+forces(+stress) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pbc10k|md1024|batch256|taxol]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pbc10k|md1024|batch256|taxol] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W checked warm-up steps, times K steps once and prints the headline line: `value` (atoms*steps/s),
+`ms_per_step` (the timed region / K), `metric`, `unit`, `higher_is_better`, `dtype`, `data`, `config`.  Everything described
+below from `roofline` on is measured only with --full, whose `value` / `ms_per_step` are the median of five timed regions.
+--dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy (inputs and weights are seeded).
 
 A "step" is one full evaluation of the hot path (neighbour lists rebuilt, 3 message passing
 passes, energy head, Coulomb, analytic force/virial backward) on inputs already resident in HBM.
@@ -416,6 +421,25 @@ def hessian_config4(eng):
             "ok": bool(np.allclose(H, Href, rtol=1e-3, atol=1e-3) and np.allclose(hv4, g["hv4"], rtol=1e-3, atol=1e-3))}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, outputs: dict, gathered_energy=None) -> None:
+    """What the last timed step returned to its caller, as path/<name>.npy in the engine's own float32 / float64; the status words
+    (include/aimnet_hip.h) are checked by the timed loop and not written.  The inputs are seeded, so two builds given the same
+    arguments can be compared output for output.  The largest workload writes ~0.2 MB: no sampling is needed below the cap."""
+    arrays = {k: v.detach().cpu().numpy() for k, v in outputs.items() if k != "status"}
+    if gathered_energy is not None:
+        arrays["energy_all_ranks"] = gathered_energy.detach().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte cap")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), f"{k}: unexpected dtype {a.dtype}"
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -424,6 +448,14 @@ def main():
                     help="untimed steps in front of the timed region (default 60 = ~80 ms: the five regions of timed_region_repeat show the "
                          "first ~40 steps after an idle phase running 2 - 3 % slower than the following ones)")
     ap.add_argument("--workload", default="pbc10k")
+    ap.add_argument("--full", action="store_true",
+                    help="every record beside the headline: the HIP-event GEMM roofline sampled inside the timed region, the four "
+                         "repeats of the timed region (value = their median), the per-family pass, the other GEMM precisions, Ewald / "
+                         "PME, scaling_md1024, the CPU baseline, the parity gates and the config-4 Hessian; the --no-* options below "
+                         "trim it.  Without it the run times the --steps steps once and prints the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (energy, charges, forces[, stress]; N > 1: + the all-gathered "
+                         "energies) as DIR/<name>.npy, from rank 0")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-repeat", action="store_true", help="skip the four extra repeats of the timed region (timed_region_repeat)")
     ap.add_argument("--no-exact-f32", action="store_true", help="skip the extra pass with the exact-fp32 GEMM kernels (profiling runs)")
@@ -481,12 +513,14 @@ def main():
         n_atoms = int(t["coord"].shape[0])
         frames = int(wl["frames"])
         statuses = []
+        last = {}  # the result dict of the latest step (--dump-outputs)
 
         def local_step(sync=True):  # this rank's shard only: no collective
             r = eng.eval(t["coord"], t["numbers"], t["mol_idx"], t["charge"], cell=cell, forces=True, stress=wl["stress"],
                          coulomb=wl["coulomb"], sync=sync)
             if not sync:
                 statuses.append(r["status"])
+            last["outputs"] = r
             return r["energy"]
 
         def step(sync=True):
@@ -527,11 +561,46 @@ def main():
             total_atoms = n_atoms
         assert bool(torch.isfinite(e_all).all()), "non-finite energies"
         return dict(elapsed=elapsed, total_atoms=total_atoms, n_atoms=n_atoms, frames=frames, prof=prof, wl=wl, local_step=local_step,
-                    ranks_seen=ranks_seen)
+                    ranks_seen=ranks_seen, outputs=last["outputs"], e_all=e_all)
 
-    run = timed_run(args.workload, args.steps, args.warmup)
+    run = timed_run(args.workload, args.steps, args.warmup, profile=args.full)
     elapsed, total_atoms, n_atoms, frames, prof, wl, local_step = (run[k] for k in ("elapsed", "total_atoms", "n_atoms", "frames", "prof",
                                                                                    "wl", "local_step"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run["outputs"], run["e_all"] if distributed else None)
+
+    presplit = eng.get_option("gemm_presplit") != 0 and eng.get_option("gemm_bf3") != 0 and n_atoms > max(256, eng.get_option("split_max"))
+    h2 = presplit and eng.get_option("gemm_h2") != 0  # fp16x2-split operands (csrc/gemm_h2.hip): three products per fp32 product
+
+    def headline(ms_per_step):
+        return {
+            "metric": "atoms*steps/sec (energy+forces)",
+            "value": total_atoms / (ms_per_step * 1e-3),
+            "unit": "atoms*steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": ("f32 (fp16x2-split MFMA operands: fp32 == hi + lo / 4096 to 2^-24, three fp16 products per fp32 product, fp32 accumulate; "
+                      "rms error against fp64 below the fp32 MFMA chain and the bf16x3 split, profiles/r5_gemm_h2.md)") if h2 else
+                     "f32 (bf16x3-split MFMA operands, fp32 accumulate)",
+            "data": "synthetic (seeded weights of the real aimnet2 architecture; " + (
+                "crystal from 2019828.cif + 0.02 A jitter)" if args.workload == "pbc10k" else
+                "taxol.xyz frame 0)" if args.workload == "taxol" else "seeded random organic geometries)"),
+            "config": {"workload": wl["label"], "atoms_per_gpu": n_atoms, "frames_per_gpu": frames,
+                       "parallelism": f"batch-shard x{world} (independent frames, RCCL all-gather of energies)" if world > 1 else "single GPU"},
+        }
+
+    if not args.full:  # the headline alone: one timed region of --steps steps, nothing measured after it
+        if rank == 0:
+            print(json.dumps(headline(elapsed / args.steps * 1e3)))
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # the line's own noise bar: four more repeats of the identical timed region (untouched `value` = the FIRST region, as the driver
     # clocks it); min / median / max of the five regions' ms per step
@@ -644,14 +713,11 @@ def main():
         # a single timed loop would have reported - is kept as `first_region_ms`
         first_region_ms = elapsed / args.steps * 1e3
         ms_per_step = float(np.median(repeats))
-        value = total_atoms / (ms_per_step * 1e-3)
         gemm_ms = prof["gemm"] / max(1.0, prof["evals"])  # average over the sampled timed steps
         flops_step = eng.gemm_flops_per_atom(True) * n_atoms
         achieved = flops_step / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
         traffic, traffic_commit = pmc_traffic(args.workload)
         pmc = pmc_record(args.workload)
-        presplit = eng.get_option("gemm_presplit") != 0 and eng.get_option("gemm_bf3") != 0 and n_atoms > max(256, eng.get_option("split_max"))
-        h2 = presplit and eng.get_option("gemm_h2") != 0  # fp16x2-split operands (csrc/gemm_h2.hip): three products per fp32 product
         peak_split = PEAK_F16X2_TFLOPS if h2 else PEAK_BF16X3_TFLOPS
         n_lay = sum(len(d) - 1 for d in eng.spec.mlp_dims)
         fused = presplit and eng.get_option("head_fused") != 0
@@ -660,28 +726,11 @@ def main():
         e2e_flops = e2e_flops_per_atom(n_pairs / n_atoms) * n_atoms
         e2e_tflops = e2e_flops * world / (ms_per_step * 1e-3) / 1e12 / world  # per GPU (weak scaling: every rank runs the same work)
         out = {
-            "metric": "atoms*steps/sec (energy+forces)",
-            "value": value,
-            "unit": "atoms*steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
+            **headline(ms_per_step),
             "first_region_ms": first_region_ms,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": ("f32 (fp16x2-split MFMA operands: fp32 == hi + lo / 4096 to 2^-24, three fp16 products per fp32 product, fp32 accumulate; "
-                      "rms error against fp64 below the fp32 MFMA chain and the bf16x3 split, profiles/r5_gemm_h2.md)") if h2 else
-                     "f32 (bf16x3-split MFMA operands, fp32 accumulate)",
             "timed_region_repeat": {"ms_per_step": repeats, "min": float(np.min(repeats)), "median": float(np.median(repeats)),
                                     "max": float(np.max(repeats)), "regions": len(repeats), "steps_per_region": args.steps,
                                     "note": "`value` / `ms_per_step` = the median of these regions; region 0 = `first_region_ms`; the others repeat it after one re-warming evaluation"},
-            "data": "synthetic (seeded weights of the real aimnet2 architecture; " + (
-                "crystal from 2019828.cif + 0.02 A jitter)" if args.workload == "pbc10k" else
-                "taxol.xyz frame 0)" if args.workload == "taxol" else "seeded random organic geometries)"),
-            "config": {"workload": wl["label"], "atoms_per_gpu": n_atoms, "frames_per_gpu": frames,
-                       "parallelism": f"batch-shard x{world} (independent frames, RCCL all-gather of energies)" if world > 1 else "single GPU"},
             # algorithmic fp32 FLOPs of the MLP GEMMs / their time: against the roof of the kernel that runs them (six bf16 MFMA
             # products per fp32 product: 2.5 PFLOP/s / 6) and against the fp32-matrix peak the exact kernels are bound by
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak_split, "unit": "TFLOP/s",

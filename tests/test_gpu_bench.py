@@ -24,9 +24,45 @@ def _last_json(out: str) -> dict:
     return json.loads(lines[-1])
 
 
+HEADLINE = KEYS - {"roofline"}
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: one timed region of exactly --steps steps, the headline keys alone, and --dump-outputs writes what the last
+    timed step returned; the same arguments give the same outputs again."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "md1024",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        assert set(d) == HEADLINE and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
+        assert abs(d["value"] - d["config"]["atoms_per_gpu"] * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert d["dtype"].startswith("f32 (fp16x2-split")
+        assert sorted(os.listdir(out)) == ["charges.npy", "energy.npy", "forces.npy"]
+        a = {n: np.load(out / (n + ".npy")) for n in ("energy", "charges", "forces")}
+        assert a["energy"].shape == (128,) and a["charges"].shape == (6400,) and a["forces"].shape == (6400, 3)
+        assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+        dumps.append(a)
+    for n in dumps[0]:
+        np.testing.assert_allclose(dumps[1][n], dumps[0][n], rtol=1e-6, atol=1e-6, err_msg=n)
+    # N > 1 (two ranks on the one GPU over gloo): rank 0 prints the headline alone and dumps its outputs + the gathered energies
+    out = tmp_path / "two_ranks"
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", "29532", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, BENCH_BACKEND="gloo"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    d = _last_json(r.stdout)
+    assert set(d) == HEADLINE and d["n_gpus"] == 2 and d["config"]["atoms_per_gpu"] == 10080
+    assert np.load(out / "forces.npy").shape == (10080, 3) and np.load(out / "stress.npy").shape == (3, 3)
+    assert np.load(out / "energy_all_ranks.npy").shape == (2,)
+
+
 def test_single_gpu_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "md1024",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0
@@ -50,7 +86,7 @@ def test_single_gpu_json_contract():
 
 def test_default_workload_carries_the_parity_gate():
     """The default line (config 3) with the CPU baseline: `parity` compares engine and oracle on the two bounded samples."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-budget", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-budget", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -84,7 +120,7 @@ def test_default_workload_carries_the_parity_gate():
 def test_two_ranks_share_the_gpu_over_gloo():
     env = dict(os.environ, BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "--master-port", "29531", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)

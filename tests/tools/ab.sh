@@ -9,7 +9,7 @@ res = {"A": [], "B": []}
 for which in "ABBAABBA":
     env = dict(os.environ)
     if which == "B": env["AIMNET_HIP_LIB"] = v
-    out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--steps", "40", *extra], capture_output=True, text=True, env=env).stdout
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--steps", "40", *extra], capture_output=True, text=True, env=env).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     res[which].append(d["ms_per_step"])
 for k, name in (("A", "in-tree"), ("B", v)):

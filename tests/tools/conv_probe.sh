@@ -7,7 +7,7 @@ out=$R/gpurun_out/conv_probe.txt; : > $out
 for so in "" $(ls $R/gpurun_in/conv_*.so 2>/dev/null); do
   tag=$(basename "${so:-shipped}" .so)
   rm -rf /tmp/kt_$tag
-  AIMNET_HIP_LIB=$so timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > /tmp/kt_$tag.log 2>&1
+  AIMNET_HIP_LIB=$so timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > /tmp/kt_$tag.log 2>&1
   echo "== $tag" >> $out
   python $R/tests/tools/prof_summary.py $(ls /tmp/kt_$tag/*/*kernel_trace.csv | head -1) 27 | grep "conv_fwd_kernel\|conv_bwd_kernel\|total" >> $out
   AIMNET_HIP_LIB=$so python $R/tests/tools/checksum.py 2>/dev/null | tail -1 >> $out

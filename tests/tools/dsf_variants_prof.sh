@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 for v in intree "$@"; do
   if [ $v = intree ]; then unset AIMNET_HIP_LIB; else export AIMNET_HIP_LIB=$R/gpurun_in/$v.so; fi
   rm -rf /tmp/tr_$v
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$v -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > /tmp/tr_$v.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$v -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > /tmp/tr_$v.log 2>&1
   f=$(ls /tmp/tr_$v/*/*kernel_stats.csv | head -1)
   python - $v $f <<'PY'
 import csv, sys

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
 for so in "" $(ls $R/gpurun_in/*_noslp.so 2>/dev/null); do
   tag=$(basename "${so:-shipped}" .so)
   rm -rf /tmp/kt_$tag
-  AIMNET_HIP_LIB=$so timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > /tmp/kt_$tag.log 2>&1
+  AIMNET_HIP_LIB=$so timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > /tmp/kt_$tag.log 2>&1
   echo "== $tag"
   python $R/tests/tools/prof_summary.py $(ls /tmp/kt_$tag/*/*kernel_trace.csv | head -1) 27 | head -24 | cut -c1-118
 done

@@ -1,21 +1,23 @@
 #!/bin/bash
-# rocprofv3 passes over the default bench (run on the GPU box): kernel trace + two PMC passes, summaries into gpurun_out/$1
+# rocprofv3 passes over the default bench (run on the GPU box): kernel trace + two PMC passes, summaries into $PROF_OUT/$1
+# (default: prof_out/$1 in the repository)
 out=$1
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out/$out
+D=${PROF_OUT:-$R/prof_out}/$out
+mkdir -p $D
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$out/trace -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > $R/gpurun_out/$out/bench_traced.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > $D/bench_traced.log 2>&1
 for pass in "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVES" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_HIT_sum TCC_MISS_sum"; do
   tag=$(echo $pass | cut -d' ' -f1)
-  timeout 300 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/gpurun_out/$out/$tag -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > $R/gpurun_out/$out/$tag.log 2>&1
+  timeout 300 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $D/$tag -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-exact-f32 --no-hessian --no-repeat > $D/$tag.log 2>&1
 done
 cd $R
-python tests/tools/prof_summary.py $(ls gpurun_out/$out/trace/*/*kernel_trace.csv | head -1) 17 > gpurun_out/$out/kernel_summary.txt
-cp $(ls gpurun_out/$out/trace/*/*kernel_stats.csv | head -1) gpurun_out/$out/kernel_stats.csv
-python - <<PY > gpurun_out/$out/pmc_summary.txt
+python tests/tools/prof_summary.py $(ls $D/trace/*/*kernel_trace.csv | head -1) 17 > $D/kernel_summary.txt
+cp $(ls $D/trace/*/*kernel_stats.csv | head -1) $D/kernel_stats.csv
+python - <<PY > $D/pmc_summary.txt
 import csv, glob, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(lambda: [0.0, 0]))
-for f in sorted(glob.glob("gpurun_out/$out/*/*/*counter_collection.csv")):
+for f in sorted(glob.glob("$D/*/*/*counter_collection.csv")):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"].replace("aimnet::", "").replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0][:48]
         a = agg[k][r["Counter_Name"]]; a[0] += float(r["Counter_Value"]); a[1] += 1
@@ -24,11 +26,11 @@ print("per-dispatch averages; kernel | " + " | ".join(names))
 for k in sorted(agg, key=lambda k: -agg[k].get("GRBM_GUI_ACTIVE", [0, 1])[0]):
     print(f"{k:48s} | " + " | ".join(f"{agg[k][c][0] / max(1, agg[k][c][1]):.4g}" if c in agg[k] else "-" for c in names))
 PY
-python - <<PY > gpurun_out/$out/pmc.json
+python - <<PY > $D/pmc.json
 # GEMM-family aggregates for bench.py's roofline.traffic (profiles/r2_pmc.json), stamped with the commit (gpurun_in/HEAD)
 import csv, glob, collections, json, os
 tot = collections.defaultdict(float); n = collections.defaultdict(int)
-for f in sorted(glob.glob("gpurun_out/$out/*/*/*counter_collection.csv")):
+for f in sorted(glob.glob("$D/*/*/*counter_collection.csv")):
     for r in csv.DictReader(open(f)):
         if not any(k in r["Kernel_Name"] for k in ("gemm_nt", "gemm_bf3", "gemm_h2", "gemm_chain", "head_fused")): continue
         tot[r["Counter_Name"]] += float(r["Counter_Value"]); n[r["Counter_Name"]] += 1
@@ -40,5 +42,5 @@ print(json.dumps({"source": "tests/tools/pmc_bench.sh (rocprofv3 --pmc TCC_EA0_R
                   "traffic_bytes_per_launch": rd + wr,
                   "mfma_busy_frac_in_kernel": tot["SQ_VALU_MFMA_BUSY_CYCLES"] / max(1.0, 1024 * tot["GRBM_GUI_ACTIVE"] / 8)}, indent=1))
 PY
-rm -rf gpurun_out/$out/SQ_VALU_MFMA_BUSY_CYCLES gpurun_out/$out/TCC_EA0_RDREQ_sum gpurun_out/$out/trace
-head -30 gpurun_out/$out/kernel_summary.txt; head -24 gpurun_out/$out/pmc_summary.txt
+rm -rf $D/SQ_VALU_MFMA_BUSY_CYCLES $D/TCC_EA0_RDREQ_sum $D/trace
+head -30 $D/kernel_summary.txt; head -24 $D/pmc_summary.txt
