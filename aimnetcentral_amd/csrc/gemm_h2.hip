@@ -271,11 +271,18 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* _
         const int row = m0 + wm * 16 * SM + 16 * i + l16;
         unsigned short* crow = C3 + (size_t)row * ldc3;
         if (j + 1 < SN) {
+          // N % 32 == 0: the first tile of a pair is inside whenever its first column is.  The second one can be outside: with
+          // SN odd (tile 223) a wave's pairs start 16 columns past a 32-aligned column, and N % TN == TN - 32 puts that column
+          // pair across N - then only the first tile is stored (the branch is uniform: the column does not depend on the lane)
+          const int col0 = n0 + wn * 16 * SN + 16 * j;
           f32x4 v0, v1;
-          const bool ok = finish(i, j, v0);
-          finish(i, j + 1, v1);  // N % 32 == 0 and 32-aligned tile pairs: both tiles are inside or both outside
-          if (!ok) continue;
-          store_h2_tile_pair(crow, n0 + wn * 16 * SN + 16 * j, lc, v0, v1);
+          if (!finish(i, j, v0)) continue;
+          if (col0 + 16 < N) {
+            finish(i, j + 1, v1);
+            store_h2_tile_pair(crow, col0, lc, v0, v1);
+          } else {
+            store_h2_x4(crow, col0 + 4 * lc, v0);
+          }
         } else {
           f32x4 v;
           if (!finish(i, j, v)) continue;

@@ -1,11 +1,13 @@
 // gemm_h2_common.h - the fp16x2-split operand form ("h2") of the MLP GEMMs (gemm_h2.hip, gemm_head.hip) and the device helpers
 // its producers use (conv.hip row assembly, model.hip build_zbar, the GEMM epilogues).
 //
-// fp32 value x = hi + lo / 4096 with hi = fp16(x) and lo = fp16((x - hi) * 4096), both rounded to nearest even: |x - hi| <= 2^-12 |x|,
-// so the scaled residual is no larger than |x| itself (no overflow beyond hi's own; gradual underflow only below 1e-11 absolute)
-// and its own rounding leaves |x - hi - lo / 4096| <= 2^-24 |x| - the rounding of ONE fp32 operation.  A product of two such
-// operands needs three matrix instructions instead of the six of the bf16x3 split (gemm_bf3a.hip):
-//     a b = ah bh + (ah bl + al bh) / 4096 + al bl / 4096^2,   the last term <= 2^-24 |a b| (typically 2^-26) and dropped,
+// fp32 value x = hi + lo / 4096 with hi = fp16(x) and lo = fp16((x - hi) * 4096), both rounded to nearest even: |x - hi| <= 2^-11 |x|
+// (half an fp16 ulp), so the scaled residual is below 2 |x| and fits fp16 for |x| < 32768 (at 32784 = 32768 + 16, a tie, it is
+// 65536: inf - the range checks below stop at 32768); the residual has up to 13 significant bits, lo keeps 11, which leaves
+// |x - hi - lo / 4096| <= 2^-23 |x| (reached, e.g. at 1 + 2^-11 + 2^-23; below 2^-24 |x| for three values in four) where lo is a
+// normal number (|x| >= 2^-13; below it 2^-37 absolute).  A product of two such operands needs three matrix instructions instead
+// of the six of the bf16x3 split (gemm_bf3a.hip):
+//     a b = ah bh + (ah bl + al bh) / 4096 + al bl / 4096^2,   the last term <= 2^-22 |a b| (typically 2^-26) and dropped,
 // with the cross terms summed in an accumulator of their own and scaled once in the epilogue.  Measured on the layer shapes
 // (tests/tools/h2_bench.py, profiles/r5_gemm_h2.md): rms error against fp64 BELOW the fp32 MFMA chain and below the bf16x3 split.
 //
@@ -15,10 +17,11 @@
 //   activations : hi plain, lo of every ODD k-block negated           (the producers below, H2_ACT)
 // so that ah (-bh) lands in the odd set with a minus sign (epilogue: even - odd) and both cross terms ah bl, (-al)(-bh) keep
 // their sign in the single cross accumulator.
-// Range: |x| >= 65520 does not fit hi: it becomes inf, the products inf / NaN, and the energies / forces non-finite.  The kernels that
-// write those raise status[6] bit 5 (kernels.h STATUS_NONFINITE, include/aimnet_hip.h) - visible to every consumer of the C ABI, also
-// for an overflow in the adjoint sweep alone; the Python layer (engine.py) then repeats the evaluation with the bf16x3 operands
-// (set_option("gemm_h2", 0)) and stays on them if that is finite.  Weights are checked at create time (h2_fits).
+// Range: from |x| = 32768 on lo can overflow, from 65520 on hi does: inf, the products inf / NaN, the energies / forces non-finite.
+// The kernels that write those raise status[6] bit 5 (kernels.h STATUS_NONFINITE, include/aimnet_hip.h) - visible to every
+// consumer of the C ABI, also for an overflow in the adjoint sweep alone; the Python layer (engine.py) then repeats the evaluation
+// with the bf16x3 operands (set_option("gemm_h2", 0)) and stays on them if that is finite.  Weights are checked at create time
+// (h2_fits: |w| < H2_MAX).
 // (h2_flag_overflow below is the per-element form for the stand-alone split kernel of the tests.)
 #pragma once
 
@@ -34,7 +37,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr float H2_SCALE = 4096.0f;
 constexpr float H2_INV_SCALE = 1.0f / 4096.0f;
-constexpr float H2_MAX = 65504.0f;
+constexpr float H2_MAX = 32768.0f;  // |x| below it splits into two finite planes (above, lo can overflow: see the top)
 
 // two fp32 -> packed hi pair, packed (scaled) lo pair; lo_scale = +-4096 (the sign of the k-block for activations)
 __device__ __forceinline__ void split2_pair(float a, float b, float lo_scale, unsigned& hi, unsigned& lo) {

@@ -294,7 +294,7 @@ int aimnet_debug_gemm_bf3a(int cfg, int epi, int out3, const void* A3, int lda3,
                            const float* bias, float* C, void* C3, int ldc3, float* D, int ldc, int alt, void* hip_stream);
 
 /* aimnet_debug_split_h2 / aimnet_debug_gemm_h2 (csrc/gemm_h2.hip): the same product on fp16x2-split operands ("h2" layout: per row,
- * K/32 blocks of [hi: 32 fp16][lo: 32 fp16] = 128 bytes, fp32 value == hi + lo / 4096 to 2^-24; ld* count 16-bit elements,
+ * K/32 blocks of [hi: 32 fp16][lo: 32 fp16] = 128 bytes, fp32 value == hi + lo / 4096 to 2^-23; ld* count 16-bit elements,
  * >= 2 * pad32(K), multiples of 64): three matrix instructions per tile and k-step instead of six.  mode of the split: 0 plain,
  * 1 activation form (lo planes of the odd k-blocks negated), 2 weight form (hi planes of the odd k-blocks negated); alt as in
  * aimnet_debug_gemm_bf3a (1 / 2 want A2 in form 1 and Bt2 in form 2; 0 wants both plain); out2 != 0: C is written in h2 form 1. */
@@ -323,10 +323,11 @@ int aimnet_engine_debug_mlp_sweep(aimnet_engine* engine, int pass, int backward,
  *                   split "bf3" form in memory (written by its producer; csrc/gemm_bf3a.hip streams both operands by DMA), 0: fp32
  *                   activations split inside the GEMM's main loop (csrc/gemm_bf3.hip)
  *   "gemm_h2"       1 (default): wherever the activations are pre-split, they and the weights take the fp16x2-split form "h2"
- *                   (csrc/gemm_h2.hip: fp32 == hi + lo / 4096 to 2^-24, three matrix instructions per tile and k-step instead of six,
+ *                   (csrc/gemm_h2.hip: fp32 == hi + lo / 4096 to 2^-23, three matrix instructions per tile and k-step instead of six,
  *                   4 instead of 6 bytes per element; rms error below the bf16x3 form's, profiles/r5_gemm_h2.md), 0: the bf16x3 form
- *                   (csrc/gemm_bf3a.hip).  fp16 holds |x| < 65504: weights beyond it switch the option off at create time,
- *                   activations beyond it surface as non-finite outputs (the Python layer then repeats the call with 0 and stays there)
+ *                   (csrc/gemm_bf3a.hip).  fp16 holds |x| < 65504, the scaled lo plane |x| < 32768: weights of |w| >= 32768
+ *                   switch the option off at create time, activations beyond it surface as non-finite outputs (the Python layer
+ *                   then repeats the call with 0 and stays there)
  *   "gemm_chain"    1 (default): with fp16x2-split activations every MLP sweep (forward or backward, one per pass) whose layer sizes
  *                   match an instantiated shape is ONE launch (csrc/gemm_chain.hip: a block owns 16 / 32 / 48 rows and the full width
  *                   of every layer, hidden activations stay in LDS, weights stream L2 -> registers in a packed fragment order); 0: one
