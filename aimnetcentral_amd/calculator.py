@@ -14,7 +14,7 @@ Deliberate deviations, all loud:
     file (loader.load_dftd3_tables);
   * caller-supplied neighbour matrices (`nbmat`, `nbmat_lr`, `shifts`, `shifts_lr`) are handed to the engine as the reference
     hands them to the model (no list is built, coordinates as given) for flat 2D input; they must be FULL matrices (both
-    directions of every pair, as the reference's builders emit them - the short-range one is verified on the device); with
+    directions of every pair, as the reference's builders emit them - every one of them is verified on the device); with
     hessian=True / hessian_vector_product they raise NotImplementedError;
   * (per-system `pbc` flags of shape (B, 3) are supported: the engine takes them as a device array);
   * hessian=True and hessian_vector_product run the analytic tangent sweep of csrc/hvp.hip (forward-mode through the

@@ -209,7 +209,10 @@ int launch_import_list(hipStream_t s, const int* ext_idx, const int* ext_shift, 
 // bad |= 16 unless every entry (i -> j, s) has its mirror (j -> i, -s) in the row of j (caller-supplied matrices)
 int launch_list_symmetry_check(hipStream_t s, const int* nb_idx, const int* nb_shift, const int* nb_cnt, int cap, int n_atoms,
                                int* bad,
-                               int max_check = 1 << 30);  // pairs per row that are verified (long-range matrices: a sample);
+                               int max_check = 1 << 30,  // pairs per row that the (quadratic) row scan verifies: "exactly one mirror"
+                               // != NULL (long-range / D3 matrices, 2 * n_atoms words of scratch): the whole matrix is verified by a
+                               // linear pass behind the scan of the first max_check pairs (nlist.hip, list_invariant_kernel)
+                               unsigned long long* part = nullptr);
 
 // ---- conv.hip ---------------------------------------------------------------------------------
 struct BasisParams {  // radial basis of AEVSV (aev.py:66-81), passed by value

@@ -1000,8 +1000,9 @@ __global__ __launch_bounds__(256) void list_symmetry_kernel(const int* __restric
   if (i >= n_atoms) return;
   const int lane = threadIdx.x & 63;
   // max_check: pairs per row that are verified.  The short-range matrix is verified in full (the reverse-pair map needs EXACTLY one
-  // mirror per pair); of a long-range / D3 row (2 000 entries at 15 A) the first max_check pairs are - the test there is against a
-  // HALF list, which fails on the first pairs of almost every row, and the full scan is quadratic in the row length
+  // mirror per pair); of a long-range / D3 row (2 000 entries at 15 A) the first max_check pairs are - a HALF list fails on the first
+  // pairs of almost every row, the full scan is quadratic in the row length, and the rest of such a row is covered by the linear
+  // pass of list_invariant_kernel below
   const int cnt = min(nb_cnt[i], max_check);
   // The wave takes the pairs of row i one after the other and scans row j with all 64 lanes (coalesced; a lane-per-pair scan of
   // 64 different rows took 0.39 s on a 10 080 x 2 064 long-range matrix, this form a few ms)
@@ -1039,11 +1040,92 @@ __global__ __launch_bounds__(256) void list_symmetry_kernel(const int* __restric
   if (__ballot(missing) && lane == 0) atomicOr(bad, 16);
 }
 
+// The complete test of a long-range / D3 matrix at a cost linear in its entries: an order-independent invariant instead of the
+// row scan.  Every entry (i -> j, s) is reduced to the canonical triple of its pair - (i, j, s) when it is the forward direction
+// (i < j, or a self image whose first non-zero shift component is positive), (j, i, -s) otherwise - and adds two independent 64-bit
+// mixes of that triple to two wrapping integer sums, with a plus sign for the forward and a minus sign for the backward direction.
+// A matrix that holds every pair once in either direction sums to zero in both; a missing mirror or an entry that one direction
+// holds more often than the other leaves +-mix (mod 2^64) in each, zero in both with probability 2^-128.  What integer sums cannot
+// see is a pair that BOTH directions hold twice; inside the first max_check entries of a row the scan above still reports it.
+// One wave per row writes the row's two sums with plain stores (part[2 i], part[2 i + 1]); a single block adds them up.
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {  // the finaliser of splitmix64
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27; x *= 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+
+__global__ __launch_bounds__(256) void list_invariant_kernel(const int* __restrict__ nb_idx, const int* __restrict__ nb_shift,
+                                                            const int* __restrict__ nb_cnt, int cap, int n_atoms,
+                                                            unsigned long long* __restrict__ part) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_atoms) return;
+  const int lane = threadIdx.x & 63;
+  const int cnt = min(nb_cnt[i], cap);
+  unsigned long long a1 = 0ull, a2 = 0ull;
+  for (int m = lane; m < cnt; m += 64) {
+    const size_t p = (size_t)i * cap + m;
+    const int j = nb_idx[p];
+    int sx = 0, sy = 0, sz = 0;
+    if (nb_shift) unpack_shift(nb_shift[p], sx, sy, sz);
+    const bool fwd = i < j || (i == j && (sx > 0 || (sx == 0 && (sy > 0 || (sy == 0 && sz >= 0)))));
+    const unsigned lo = (unsigned)min(i, j), hi = (unsigned)max(i, j);
+    const unsigned code = (unsigned)(fwd ? pack_shift(sx, sy, sz) : pack_shift(-sx, -sy, -sz)) & 0xffffffu;
+    const unsigned long long key = ((unsigned long long)lo << 32) | hi;
+    const unsigned long long h1 = mix64(key ^ mix64((unsigned long long)code + 0x9e3779b97f4a7c15ull));
+    const unsigned long long h2 = mix64(key * 0xff51afd7ed558ccdull + ((unsigned long long)code ^ 0xc4ceb9fe1a85ec53ull));
+    a1 += fwd ? h1 : 0ull - h1;
+    a2 += fwd ? h2 : 0ull - h2;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a1 += __shfl_xor(a1, off, 64);
+    a2 += __shfl_xor(a2, off, 64);
+  }
+  if (lane == 0) {
+    part[2 * (size_t)i] = a1;
+    part[2 * (size_t)i + 1] = a2;
+  }
+}
+
+__global__ __launch_bounds__(1024) void list_invariant_reduce_kernel(const unsigned long long* __restrict__ part, int n_atoms,
+                                                                    int* __restrict__ bad) {
+  __shared__ unsigned long long s1[16], s2[16];
+  unsigned long long a1 = 0ull, a2 = 0ull;
+  for (int i = threadIdx.x; i < n_atoms; i += 1024) {
+    a1 += part[2 * (size_t)i];
+    a2 += part[2 * (size_t)i + 1];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a1 += __shfl_xor(a1, off, 64);
+    a2 += __shfl_xor(a2, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s1[threadIdx.x >> 6] = a1;
+    s2[threadIdx.x >> 6] = a2;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  a1 = a2 = 0ull;
+  for (int w = 0; w < 16; ++w) {
+    a1 += s1[w];
+    a2 += s2[w];
+  }
+  if (a1 != 0ull || a2 != 0ull) atomicOr(bad, 16);
+}
+
+// part != NULL (2 * n_atoms 64-bit words of scratch): the invariant above runs behind the scan of the first max_check entries
 int launch_list_symmetry_check(hipStream_t s, const int* nb_idx, const int* nb_shift, const int* nb_cnt, int cap, int n_atoms,
-                               int* bad, int max_check) {
+                               int* bad, int max_check, unsigned long long* part) {
   hipLaunchKernelGGL(list_symmetry_kernel, dim3(ceil_div(n_atoms, 4)), dim3(256), 0, s, nb_idx, nb_shift, nb_cnt, cap, n_atoms, bad,
                      max_check);
   AIMNET_LAUNCH_CHECK();
+  if (part) {
+    hipLaunchKernelGGL(list_invariant_kernel, dim3(ceil_div(n_atoms, 4)), dim3(256), 0, s, nb_idx, nb_shift, nb_cnt, cap, n_atoms, part);
+    AIMNET_LAUNCH_CHECK();
+    hipLaunchKernelGGL(list_invariant_reduce_kernel, dim3(1), dim3(1024), 0, s, part, n_atoms, bad);
+    AIMNET_LAUNCH_CHECK();
+  }
   return 0;
 }
 

@@ -77,6 +77,12 @@ def describe_input_flags(flags: int, n_mol: int | None = None) -> str:
     return " and ".join(what) if what else "no flags"
 
 
+def same_cutoff(a: float, b: float) -> bool:
+    """`d3_cutoff == dsf_rc` as the engine decides it (engine.hip, d3_shares_lr_list / np_walk): on the float32 values of
+    aimnet_eval_options - every host-side copy of that rule goes through here."""
+    return bool(np.float32(a) == np.float32(b))
+
+
 class HipEngine:
     def __init__(self, spec: ModelSpec, device: str | int = 0):
         import torch
@@ -372,8 +378,9 @@ class HipEngine:
             # periodic DSF walks the cell grid (no list); only non-periodic DSF materialises a long-range list
             opt.max_nb_lr = self._lr_capacity(float(dsf_rc)) if (method == _lib.COULOMB_DSF and cell is None) else 0
             # ... and neither do non-periodic systems large enough for the bounding-box cell grid (engine.hip `np_walk`: the same rule)
+            # (the options carry the cutoffs as C floats and the engine compares those: two cutoffs that differ only in float64 are ONE)
             if (opt.max_nb_lr and n >= 1500 * n_mol and nbmat is None and self.get_option("dsf_np_walk") and
-                    not (dftd3 is not None and float(dftd3.get("cutoff", 15.0)) == float(dsf_rc))):
+                    not (dftd3 is not None and same_cutoff(dftd3.get("cutoff", 15.0), dsf_rc))):
                 opt.max_nb_lr = 0
             if method in (_lib.COULOMB_EWALD, _lib.COULOMB_PME):
                 opt.ewald_accuracy = float(ewald_accuracy)

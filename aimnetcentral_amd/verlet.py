@@ -22,16 +22,22 @@ from __future__ import annotations
 
 from typing import Any
 
-from .engine import HipEngine, NeighborOverflowError, _round16, neighbor_list
+from .engine import HipEngine, NeighborOverflowError, _round16, neighbor_list, same_cutoff
 
 
 class VerletSkinLists:
     """`HipEngine.eval` with neighbour matrices that live for as long as no atom has moved more than skin / 2.
 
     sync=True (default): one displacement check per step decides on the host (one scalar D2H, beside the status read the
-    synchronous path pays anyway).  sync=False: nothing is read back - the matrices are rebuilt every `rebuild_every` steps and the
-    per-step "an atom left the skin" flags are verified by `check_deferred()` together with the engine's deferred status words;
-    a raised flag invalidates the steps since the last check (NeighborOverflowError, as for a row overflow)."""
+    synchronous path pays anyway).  sync=False: a reuse step reads nothing back - the matrices are rebuilt every `rebuild_every`
+    steps and the per-step "an atom left the skin" flags are verified by `check_deferred()` together with the engine's deferred
+    status words; a raised flag invalidates the steps since the last check (NeighborOverflowError, as for a row overflow).  A
+    REBUILD step still reads the list builder's status word (longest row, overflow) on the host, in either mode: the kept matrices
+    are cut to the longest row.
+
+    The matrices are kept for as long as what they depend on stays the same: the shapes, `pbc`, the cell, the two cutoffs and the
+    molecule assignment `mol_idx` (compared by content, on the device, beside the displacement test) - not the identity of any
+    caller tensor (a fresh `numbers` / `mol_idx` tensor with the same contents on every step reuses them)."""
 
     def __init__(self, engine: HipEngine, skin: float = 0.5, rebuild_every: int = 20):
         if not skin > 0.0:
@@ -39,7 +45,7 @@ class VerletSkinLists:
         self.engine, self.skin, self.rebuild_every = engine, float(skin), int(rebuild_every)
         self._key = None
         self._lists: dict[str, Any] = {}
-        self._x_ref = self._offset = self._cell_ref = None
+        self._x_ref = self._offset = self._cell_ref = self._mol_ref = None
         self._age = 0
         self._pending_flags: list = []
         self.builds = self.reuses = 0
@@ -72,6 +78,7 @@ class VerletSkinLists:
         self._x_ref = coord.clone()
         self._offset = coord - xw  # per-atom lattice translation of the build-time wrap (zero without a cell)
         self._cell_ref = None if cell is None else cell.clone()
+        self._mol_ref = mol_idx.clone()  # the rows hold same-molecule pairs only: another assignment needs other matrices
         self._age = 0
         self.builds += 1
 
@@ -93,13 +100,16 @@ class VerletSkinLists:
         # with caller-supplied matrices DSF runs over a matrix (no grid walk); 'simple' sums all pairs of a molecule and needs none
         need_lr = float(dsf_rc) if coulomb == "dsf" else None
         # one cutoff for DSF and D3: ONE matrix serves both terms (include/aimnet_hip.h: pass it as nbmat_lr only)
-        need_d3 = d3_rc if (d3_rc is not None and d3_rc != need_lr) else None
-        key = (tuple(coord.shape), numbers.data_ptr(), None if cell is None else tuple(cell.shape), tuple(bool(b) for b in pbc),
+        # (equal as the engine compares them: on the float32 values of its options, engine.same_cutoff)
+        need_d3 = d3_rc if (d3_rc is not None and not (need_lr is not None and same_cutoff(d3_rc, need_lr))) else None
+        # what the matrices depend on, as far as the host knows it without a read: shapes, periodicity, cutoffs; the CONTENTS of
+        # mol_idx and of the cell are compared on the device below (`numbers` does not enter a neighbour matrix at all)
+        key = (tuple(coord.shape), tuple(mol_idx.shape), None if cell is None else tuple(cell.shape), tuple(bool(b) for b in pbc),
                need_lr, need_d3)
         rebuild = key != self._key
         flag = None
         if not rebuild:
-            moved = (coord - self._x_ref).square().sum(dim=1).max() > (0.5 * self.skin) ** 2
+            moved = ((coord - self._x_ref).square().sum(dim=1).max() > (0.5 * self.skin) ** 2) | (mol_idx != self._mol_ref).any()
             if cell is not None:
                 moved = moved | (cell != self._cell_ref).any()  # a changed cell (NPT) moves every image
             if sync:
@@ -129,6 +139,6 @@ class VerletSkinLists:
         self.engine.check_deferred()
         if flags and bool(torch.stack(flags).any()):
             self.invalidate()
-            raise NeighborOverflowError("VerletSkinLists: an atom moved more than skin / 2 on a step that reused the neighbour matrices; "
-                                        "the evaluations since the last check are invalid - repeat them (the matrices will be rebuilt), "
+            raise NeighborOverflowError("VerletSkinLists: an atom moved more than skin / 2 (or the cell / the molecule assignment changed) on "
+                                        "a step that reused the neighbour matrices; the evaluations since the last check are invalid - repeat them (the matrices will be rebuilt), "
                                         "or use a larger skin / a smaller rebuild_every")

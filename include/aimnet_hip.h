@@ -113,8 +113,10 @@ typedef struct aimnet_inputs {
    * lists.  nbmat != NULL: NO list is built; device int32 rows [n_atoms][width], entries outside [0, n_atoms) are padding (the
    * reference pads with n_atoms); shifts int32 [n_atoms][width][3] lattice translations (required iff cell != NULL, |s| <= 127)
    * applied to the coordinates AS GIVEN (nothing is wrapped in this mode).  Every matrix must be FULL (both directions of every
-   * pair present, as the reference's builders emit them): the short-range matrix is verified (status[6] bit 4), the others are
-   * trusted.  nbmat_lr serves the LRCoulomb term (simple: 1/d over every entry, lr.py:311-331; DSF: required) and, without
+   * pair present exactly once, as the reference's builders emit them) and every one of them is verified on the device (status[6]
+   * bit 4): the short-range matrix entry by entry, the others over their first 64 entries per row the same way and as a whole by
+   * an order-independent sum over all entries (the one defect that sum cannot see is a pair that BOTH directions repeat beyond
+   * entry 64).  nbmat_lr serves the LRCoulomb term (simple: 1/d over every entry, lr.py:311-331; DSF: required) and, without
    * nbmat_d3, the DFT-D3 term; with d3_cutoff == dsf_rc one matrix serves both (pass it as nbmat_lr).  The row capacities
    * options.max_nb / max_nb_lr / max_nb_d3 must be >= the widths. */
   const int32_t* nbmat;
@@ -166,7 +168,9 @@ typedef struct aimnet_outputs {
                               4 max neighbours found (D3 list), 5 overflow flag D3 list,
                               6 input sanity flags: bit 0 an atomic number outside [0, 63], bit 1 a mol_idx outside
                                 [0, n_mol), bit 2 mol_idx not sorted, bit 3 a caller-supplied matrix holds a shift outside +-127
-                                or an unshifted self pair, bit 4 the caller-supplied short-range matrix is not symmetric.  The first kernel writes clamped copies (atomic number
+                                or an unshifted self pair, bit 4 a caller-supplied matrix (short-range, long-range or D3) is not a full symmetric one: an entry
+                                i -> j, s without its mirror j -> i, -s anywhere in the row of j, or an entry one direction holds more
+                                often than the other (every entry of every row counts, not a sample).  The first kernel writes clamped copies (atomic number
                                 slots, mol_idx) into the workspace and every later kernel indexes through those, so any device
                                 array is memory-safe; with a flag raised the results are meaningless.
                                 Bit 5 (32) is NOT an input flag: the kernels that write the energies / forces saw a non-finite value.

@@ -73,3 +73,24 @@ def test_small_molecules_keep_the_matrix_form(hip_engine_cold):
     a, b = _both(hip_engine_cold, c, z, mol.astype(np.int32), 4, dsf_rc=9.0)
     for k in a:
         assert np.array_equal(a[k], b[k]), k  # below the threshold the switch changes nothing: bitwise
+
+
+def test_cutoffs_equal_in_float32_only(hip_engine):
+    """The engine's options carry the cutoffs as C floats and its "DSF and DFT-D3 share one matrix" rule compares those; the host
+    has to decide the same way.  12.0 and 12.0 + 1e-9 are one float32: the call evaluates (the shared matrix, no walk), with the
+    result of the call where both are exactly 12.0."""
+    g, t = golden("dftd3"), golden("dftd3_subset")
+    hip_engine.set_dftd3_tables({k: t[k] for k in ("c6ab", "cn_ref", "rcov", "r4r2")})
+    assert np.float32(12.0 + 1e-9) == np.float32(12.0) and 12.0 + 1e-9 != 12.0
+    par = dict(s6=float(g["s6"]), s8=float(g["s8"]), a1=float(g["a1"]), a2=float(g["a2"]), cutoff=12.0 + 1e-9, smoothing_fraction=0.2)
+    c, z = _cluster((4, 2, 2), 5)  # 1 536 atoms: above the walk threshold
+    dev = hip_engine.device
+    args = (torch.as_tensor(c, device=dev), torch.as_tensor(z, device=dev), torch.zeros(len(z), dtype=torch.int32, device=dev),
+            torch.zeros(1, device=dev))
+    a = {k: v.cpu().numpy() for k, v in hip_engine.eval(*args, forces=True, coulomb="dsf", dsf_rc=12.0, dftd3=par).items()}
+    b = {k: v.cpu().numpy() for k, v in hip_engine.eval(*args, forces=True, coulomb="dsf", dsf_rc=12.0, dftd3=dict(par, cutoff=12.0)).items()}
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k  # the same float32 options reach the engine: the same kernels, bitwise
+    a = {k: v.cpu().numpy() for k, v in hip_engine.eval(*args, forces=True, coulomb="dsf", dsf_rc=12.0 + 1e-9, dftd3=dict(par, cutoff=12.0)).items()}
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

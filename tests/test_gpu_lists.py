@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import CHARGE_ATOL, assert_forces_close, energy_tol, golden
+from conftest import CHARGE_ATOL, STRESS_ATOL, assert_forces_close, energy_tol, golden
+
+from oracle import aimnet2_oracle as O
 
 pytestmark = pytest.mark.gpu
 
@@ -202,3 +204,120 @@ def test_duplicates_half_lr_lists_pad_masks_and_cartesian_shifts(calc):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             calc.set_lrcoulomb_method("simple")
+
+
+# ---- long-range / D3 matrices broken BEYOND the first 64 entries of a row ---------------------------------------------------------
+# (the row scan of list_symmetry_kernel verifies the first 64 pairs of such a row; the rest is covered by the linear invariant pass)
+def _far_entry(nb, sh, n):
+    """(i, p, j, q): an entry i -> j at row position p >= 64 whose mirror j -> i sits at position q >= 64 of row j as well - neither
+    end of the pair is inside the part of a row that the sampled scan looks at."""
+    for i in range(n - 1, -1, -1):
+        for p in range(64, nb.shape[1]):
+            j = int(nb[i, p])
+            if j >= n:
+                break
+            hit = nb[j] == i
+            if sh is not None:
+                hit &= (sh[j] == -sh[i, p]).all(-1)
+            q = np.nonzero(hit)[0]
+            if len(q) == 1 and q[0] >= 64:
+                return i, p, j, int(q[0])
+    raise AssertionError("no pair with both directions beyond row position 64")
+
+
+def _dropped(nb, sh, i, p, n):
+    """The matrix without entry p of row i (the row closed up, same width)."""
+    nb, sh = nb.copy(), None if sh is None else sh.copy()
+    nb[i, p:-1] = nb[i, p + 1:]
+    nb[i, -1] = n
+    if sh is not None:
+        sh[i, p:-1] = sh[i, p + 1:]
+        sh[i, -1] = 0
+    return nb, sh
+
+
+def _duplicated(nb, sh, i, p, n):
+    """One more column (padding), with entry p of row i repeated behind the last entry of that row."""
+    nb = np.concatenate([nb, np.full((nb.shape[0], 1), n, dtype=nb.dtype)], axis=1)
+    last = int((nb[i] < n).sum())
+    nb[i, last] = nb[i, p]
+    if sh is not None:
+        sh = np.concatenate([sh, np.zeros((sh.shape[0], 1, 3), dtype=sh.dtype)], axis=1)
+        sh[i, last] = sh[i, p]
+    return nb, sh
+
+
+def test_lr_matrix_of_a_molecule_broken_beyond_entry_64(calc):
+    g = golden("taxol")
+    n = len(g["numbers"])
+    mol = np.zeros(n, dtype=np.int64)
+    nb, _ = O.neighbor_list(g["coord"], 5.0, mol)
+    nbl, _ = O.neighbor_list(g["coord"], float("inf"), mol)  # all pairs: 112 entries per row
+    assert nbl.shape[1] == 112
+    i, p, j, q = _far_entry(nbl, None, n)
+    assert min(p, q) >= 64
+    data = {"coord": g["coord"], "numbers": g["numbers"], "charge": 0.0}
+    with pytest.raises(ValueError, match="not a full symmetric"):
+        calc(dict(data, nbmat=nb, nbmat_lr=_dropped(nbl, None, i, p, n)[0]), forces=True)
+    with pytest.raises(ValueError, match="not a full symmetric"):
+        calc(dict(data, nbmat=nb, nbmat_lr=_duplicated(nbl, None, i, p, n)[0]), forces=True)
+    # correct matrices of the same widths (112, and 113 with a padding column) pass and meet the golden
+    for good in (nbl, np.concatenate([nbl, np.full((n + 1, 1), n, dtype=nbl.dtype)], axis=1)):
+        out = npy(calc(dict(data, nbmat=nb, nbmat_lr=good), forces=True))
+        assert abs(out["energy"][0] - g["energy"][0]) <= energy_tol(n)
+        assert_forces_close(out["forces"], g["forces"], f"taxol, all-pairs matrix of width {good.shape[1]}")
+        assert np.abs(out["charges"] - g["charges"]).max() <= CHARGE_ATOL
+
+
+def test_periodic_15A_matrix_broken_beyond_entry_64(calc, oracle64):
+    g = golden("pbc96_dsf15")
+    n = 96
+    nb, sh, nbl, shl = _periodic_lists(g, g["coord"], 15.0)
+    assert (nbl[:n] < n).sum(1).min() > 900  # rows of about a thousand entries
+    i, p, j, q = _far_entry(nbl, shl, n)
+    assert min(p, q) >= 64
+    data = {"coord": g["coord"], "numbers": g["numbers"], "charge": 0.0, "cell": g["cell"], "nbmat": nb, "shifts": sh}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        calc.set_lrcoulomb_method("dsf", cutoff=15.0, dsf_alpha=float(g["dsf_alpha"]))
+    try:
+        for what, (bnb, bsh) in (("dropped", _dropped(nbl, shl, i, p, n)), ("duplicated", _duplicated(nbl, shl, i, p, n))):
+            with pytest.raises(ValueError, match="not a full symmetric"):
+                calc(dict(data, nbmat_lr=bnb, shifts_lr=bsh), forces=True, stress=True)
+        # the correct matrix, at the width of the duplicated one (a padding column more): the golden, at the gates
+        # test_gpu_parity.py::test_periodic_dsf_forces_stress holds the engine's own lists to on this fixture
+        wide = np.concatenate([nbl, np.full((n + 1, 1), n, dtype=nbl.dtype)], axis=1)
+        wide_sh = np.concatenate([shl, np.zeros((n + 1, 1, 3), dtype=shl.dtype)], axis=1)
+        out = npy(calc(dict(data, nbmat_lr=wide, shifts_lr=wide_sh), forces=True, stress=True))
+        e64 = O.evaluate(oracle64, g["coord"], g["numbers"], g["charge"], np.zeros(n, np.int64), cell=g["cell"], coulomb="dsf",
+                         forces=False, dsf_rc=15.0, dsf_alpha=float(g["dsf_alpha"]))["energy"]
+        assert abs(out["energy"][0] - g["energy"][0]) <= energy_tol(n) + abs(g["energy"][0] - e64[0])
+        assert_forces_close(out["forces"], g["forces"], "pbc96 dsf15, caller lists")
+        assert np.abs(out["stress"] - g["stress"]).max() <= STRESS_ATOL and np.abs(out["charges"] - g["charges"]).max() <= CHARGE_ATOL
+    finally:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            calc.set_lrcoulomb_method("simple")
+
+
+def test_d3_matrix_broken_beyond_entry_64(hip_engine):
+    """A D3 matrix of its own (`nbmat_d3`) with one mirror missing far into a row, next to intact short-range and Coulomb matrices."""
+    gd, t = golden("dftd3"), golden("dftd3_subset")
+    hip_engine.set_dftd3_tables({k: t[k] for k in ("c6ab", "cn_ref", "rcov", "r4r2")})
+    par = dict(s6=float(gd["s6"]), s8=float(gd["s8"]), a1=float(gd["a1"]), a2=float(gd["a2"]), cutoff=15.0, smoothing_fraction=0.2)
+    g = golden("taxol")
+    n = len(g["numbers"])
+    mol = np.zeros(n, dtype=np.int64)
+    nb, _ = O.neighbor_list(g["coord"], 5.0, mol)
+    nbl, _ = O.neighbor_list(g["coord"], float("inf"), mol)
+    nb3, _ = O.neighbor_list(g["coord"], 15.0, mol)
+    i, p, j, q = _far_entry(nb3, None, n)
+    dev = hip_engine.device
+    args = (torch.from_numpy(g["coord"]).to(dev), torch.from_numpy(g["numbers"]).to(dev), torch.from_numpy(mol).to(dev),
+            torch.zeros(1, device=dev))
+    kw = dict(forces=True, coulomb="simple", dftd3=par, nbmat=torch.from_numpy(nb[:n]), nbmat_lr=torch.from_numpy(nbl[:n]))
+    with pytest.raises(ValueError, match="not a full symmetric"):
+        hip_engine.eval(*args, nbmat_d3=torch.from_numpy(_dropped(nb3, None, i, p, n)[0][:n]), **kw)
+    ext = npy(hip_engine.eval(*args, nbmat_d3=torch.from_numpy(nb3[:n]), **kw))  # the intact one: same as the engine's own lists
+    own = npy(hip_engine.eval(*args, forces=True, coulomb="simple", dftd3=par))
+    assert abs(ext["energy"][0] - own["energy"][0]) <= 2e-5 and np.abs(ext["forces"] - own["forces"]).max() <= 5e-5
