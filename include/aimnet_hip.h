@@ -135,7 +135,9 @@ typedef struct aimnet_eval_options {
   int32_t coulomb;         /* AIMNET_COULOMB_* */
   float dsf_rc;            /* 15.0 */
   float dsf_alpha;         /* 0.2 */
-  int32_t max_nb;          /* row capacity of the short-range (rc) neighbour matrix */
+  int32_t max_nb;          /* row capacity of the short-range (rc) neighbour matrix.  A row of EXACTLY max_nb entries is complete:
+                            * the overflow flag (status[2]; [3], [5] for the other lists) is raised only when a row needs MORE
+                            * than its capacity (status[0] > max_nb) - such rows were truncated and the results are invalid */
   int32_t max_nb_lr;       /* row capacity of the DSF neighbour matrix (0 if unused) */
   /* external DFT-D3(BJ) two-body dispersion, DFTD3 of aimnet/modules/lr.py:1335-1820 as wired by
    * calculator.py:234-247,999-1032; needs aimnet_engine_set_dftd3 first.  0 = off. */

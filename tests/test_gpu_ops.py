@@ -23,14 +23,26 @@ def reference_conv_sv_2d_sp_einsum(a, idx, g):
 
 
 def make_idx(B, M, n_real, gen):
+    """Rows packed real-first, the sentinel B - 1 after the valid entries (the reference's format).  When there are rows enough, the
+    first ones hold 0, 1, 63, 64, 65 and M valid entries (clipped to the row width: empty, one entry, one short of / exactly / one
+    over a 64-entry index word, full); the others a random number."""
     idx = torch.full((B, M), B - 1, dtype=torch.int64)
+    fixed = sorted({min(c, n_real, M) for c in (0, 1, 63, 64, 65, M)})
+    if B - 1 <= len(fixed):
+        fixed = []
     for b in range(B):
-        n = int(torch.randint(0, min(n_real, M) + 1, (1,), generator=gen))
+        n = fixed[b] if b < len(fixed) else int(torch.randint(0, min(n_real, M) + 1, (1,), generator=gen))
         idx[b, :n] = torch.randint(0, B - 1, (n,), generator=gen)
     return idx
 
 
-@pytest.mark.parametrize("B,A,G,M", [(8, 16, 12, 10), (113, 16, 16, 62), (33, 4, 8, 5), (2, 16, 16, 1)])
+# M <= 256 with A = G = 16: the register-resident index path (csrc/conv.hip SV_MAXW = 4 index words of 64 entries), above: the generic
+# kernels; 64 / 65, 200, 256 / 257: a full first word, the first entry of the second, a partial fourth, the last entry of the fast
+# path and the first shape of the generic one
+DENSE_SHAPES = [(40, 16, 16, 64), (40, 16, 16, 65), (24, 16, 16, 200), (16, 16, 16, 256), (16, 16, 16, 257)]
+
+
+@pytest.mark.parametrize("B,A,G,M", [(8, 16, 12, 10), (113, 16, 16, 62), (33, 4, 8, 5), (2, 16, 16, 1), *DENSE_SHAPES])
 def test_conv_sv_fwd_bwd_match_einsum_reference(B, A, G, M):
     gen = torch.Generator().manual_seed(B * 1000 + M)
     a = torch.randn(B, A, G, generator=gen)
@@ -51,7 +63,7 @@ def test_conv_sv_fwd_bwd_match_einsum_reference(B, A, G, M):
     torch.testing.assert_close(gg.cpu(), g_r.grad, atol=1e-4, rtol=1e-3)
 
 
-@pytest.mark.parametrize("B,A,G,M", [(8, 16, 12, 10), (57, 16, 16, 31), (33, 4, 8, 5)])
+@pytest.mark.parametrize("B,A,G,M", [(8, 16, 12, 10), (57, 16, 16, 31), (33, 4, 8, 5), *DENSE_SHAPES])
 def test_conv_sv_double_backward_matches_autograd(B, A, G, M):
     """conv_sv_2d_sp_bwd_bwd against torch's double backward of the einsum reference (the reference pins its Warp
     kernels the same way, tests/test_conv_sv_2d_sp.py:197-253): cotangents v_a, v_g of (grad_a, grad_g)."""
