@@ -11,7 +11,7 @@ import os
 from functools import lru_cache
 
 MAX_PASS, MAX_LAYERS, MAX_SHIFTS = 4, 6, 32
-ABI_VERSION = 11  # AIMNET_ABI_VERSION of include/aimnet_hip.h this binding was written against
+ABI_VERSION = 12  # AIMNET_ABI_VERSION of include/aimnet_hip.h this binding was written against
 FORCES, STRESS = 1, 2
 COULOMB_NONE, COULOMB_SIMPLE, COULOMB_DSF, COULOMB_EWALD, COULOMB_PME = 0, 1, 2, 3, 4
 E_INVALID, E_HIP, E_WORKSPACE = -1, -2, -3
@@ -42,7 +42,6 @@ EXPORTED_SYMBOLS = (
     "aimnet_debug_gemm_h2",
     "aimnet_engine_debug_mlp_sweep",
     "aimnet_debug_pme_recip",
-    "aimnet_debug_mfma4_probe",
     "aimnet_engine_set_option",
     "aimnet_engine_get_option",
     "aimnet_engine_set_dftd3",
@@ -235,8 +234,6 @@ def load() -> C.CDLL:
                                                   C.POINTER(vp), C.POINTER(C.c_int), vp]
     lib.aimnet_debug_pme_recip.restype = C.c_int
     lib.aimnet_debug_pme_recip.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_double), vp]
-    lib.aimnet_debug_mfma4_probe.restype = C.c_int
-    lib.aimnet_debug_mfma4_probe.argtypes = [vp, vp]
     lib.aimnet_neighbor_list_workspace_bytes.restype = sz
     lib.aimnet_neighbor_list_workspace_bytes.argtypes = [i32, i32, i32]
     lib.aimnet_neighbor_list.restype = C.c_int

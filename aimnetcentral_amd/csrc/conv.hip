@@ -58,14 +58,11 @@ struct FwdWaveLds {
 //   S_i[a,g,c] = sum_z afv[z][a,g] M_i[z][g,c],   M_i[z][g,c] = sum_{j: Z_j = z} gs_g(d_ij) (1,u_ij)_c :
 // the chunk's neighbours are ordered by element, the pair loop accumulates ONE number per lane (g,c) and pair (no row gather,
 // no 16 FMAs per lane), and each element present costs one 16-FMA flush.  The forward twin of the species-moment backward.
-#ifndef AIMNET_PROBE_FWD_OCC
-#define AIMNET_PROBE_FWD_OCC 4
-#endif
 // X3: the MLP input row is written pre-split instead of fp32 - 1: for gemm_bf3a.hip ("bf3" layout: per 32 columns [plane 0][plane 1]
 // [plane 2] x 32 bf16, fp32 == p0 + p1 + p2 exactly; `x` then points at bf16 elements, 3 * ldx per row); 2: for gemm_h2.hip ("h2"
 // layout, activation form: per 32 columns [hi][lo] x 32 fp16, 2 * ldx elements per row; gemm_h2_common.h).
 template <int NQ, bool SPLIT, bool P0M = false, int X3 = 0>
-__global__ __launch_bounds__(256, SPLIT ? 3 : AIMNET_PROBE_FWD_OCC) void conv_fwd_kernel(const float* __restrict__ a, const int* __restrict__ row_of,
+__global__ __launch_bounds__(256, SPLIT ? 3 : 4) void conv_fwd_kernel(const float* __restrict__ a, const int* __restrict__ row_of,
                                                       const float* __restrict__ q,
                                                       const int* __restrict__ nb_idx, const int* __restrict__ nb_cnt,
                                                       const float4* __restrict__ pg, int cap,
@@ -201,11 +198,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : AIMNET_PROBE_FWD_OCC) void conv_fw
         float v = 0.0f;
         if (mm < nch) {
           const float dd = L.ud[mm].w - shift_l;
-#ifdef AIMNET_PROBE_FWD_NO_EXP  // measurement builds only: what the 16 exponentials per pair cost
-          v = (1.0f - bp.eta * dd * dd) * L.fc[mm];
-#else
-          v = exp_neg(-bp.eta * dd * dd) * L.fc[mm];
-#endif
+          v = exp_neg(-bp.eta * dd * dd) * L.fc[mm];  // (the 16 exponentials per pair are 8 % of the kernel: profiles/r6_conv_fwd.md)
         }
         L.gs[mm][g] = v;
       }
@@ -214,9 +207,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : AIMNET_PROBE_FWD_OCC) void conv_fw
       // instructions per 1 KiB row), so keep four row loads in flight per wave
       const int qc_f = lane & 3;
       const int qsel = max(qc_f - 1, 0);
-      (void)qsel;
-      const float fm0 = qc_f == 0 ? 1.f : 0.f, fm1 = qc_f == 1 ? 1.f : 0.f, fm2 = qc_f == 2 ? 1.f : 0.f,
-                  fm3 = qc_f == 3 ? 1.f : 0.f;
+      const bool qc0 = qc_f == 0;  // lanes of the scalar component (the pass-0 moment loop below)
       auto rowj = [&](int j) {  // j wave-uniform -> scalar address
         return reinterpret_cast<const float4*>(a + (size_t)__builtin_amdgcn_readfirstlane(j) * NF)[lane];
       };
@@ -225,26 +216,18 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : AIMNET_PROBE_FWD_OCC) void conv_fw
         const float4 u = L.ud[mm];
         const f2 t0 = mk2(av.x, av.y) * mk2(gv.x, gv.y), t1 = mk2(av.z, av.w) * mk2(gv.z, gv.w);
         acc[0][0] += t0;       acc[0][1] += t1;
-#ifdef AIMNET_PROBE_FWD_SPLAT_MOV  // measurement build: the compiler's form (a v_mov pair per component builds the {u, u} splat)
-        acc[1][0] += t0 * u.x; acc[1][1] += t1 * u.x;
-        acc[2][0] += t0 * u.y; acc[2][1] += t1 * u.y;
-        acc[3][0] += t0 * u.z; acc[3][1] += t1 * u.z;
-#else
+        // (t * u.x / u.y / u.z written plainly costs a v_mov pair per component for the {u, u} splat; the op_sel broadcast and the
+        // charge block's select below: 67.8 -> 61.7 us per dispatch, profiles/r6_conv_fwd.md)
         const f2 uxy = mk2(u.x, u.y), uzw = mk2(u.z, u.w);  // (halves of the 16-byte LDS read: no instruction)
         pk_fma_bcast<false>(acc[1][0], t0, uxy); pk_fma_bcast<false>(acc[1][1], t1, uxy);
         pk_fma_bcast<true>(acc[2][0], t0, uxy);  pk_fma_bcast<true>(acc[2][1], t1, uxy);
         pk_fma_bcast<false>(acc[3][0], t0, uzw); pk_fma_bcast<false>(acc[3][1], t1, uzw);
-#endif
         if (HAS_Q) {
-#ifdef AIMNET_PROBE_FWD_QSEL_FMA  // measurement build: the component selected by three FMAs with 0 / 1 weights (rounds 1 - 5)
-          const float w = L.gs[mm][lane >> 2] * (fm0 + fm1 * u.x + fm2 * u.y + fm3 * u.z);
-#else
           // the lane's component (1, ux, uy, uz)[lane & 3] read straight from the staged pair record: one 4-byte LDS read and a
           // select instead of three FMAs with 0 / 1 weights
           float uc = reinterpret_cast<const float*>(&L.ud[mm])[qsel];
           uc = qc_f == 0 ? 1.0f : uc;
           const float w = L.gs[mm][lane >> 2] * uc;
-#endif
 #pragma unroll
           for (int ch = 0; ch < NQ; ++ch) accq[ch] += L.qj[ch][mm] * w;
         }
@@ -275,36 +258,20 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : AIMNET_PROBE_FWD_OCC) void conv_fw
           float accm = 0.f;
           for (int mm = start; mm < end; ++mm) {
             float uc = reinterpret_cast<const float*>(&L.ud[mm])[cidx];
-            uc = qc_f == 0 ? 1.f : uc;
+            uc = qc0 ? 1.f : uc;
             accm += L.gs[mm][gq] * uc;
           }
           flush(z, accm);
           start = end;
         }
       } else {
-#ifdef AIMNET_PROBE_FWD_DEEP  // measurement builds only: eight row loads in flight per wave instead of four
-        const int nch8 = (nch + 7) & ~7;
-        int4 jj = *reinterpret_cast<const int4*>(&L.j[0]);
-        int4 jk = *reinterpret_cast<const int4*>(&L.j[4]);
-        float4 r0 = rowj(jj.x), r1 = rowj(jj.y), r2 = rowj(jj.z), r3 = rowj(jj.w);
-        float4 r4 = rowj(jk.x), r5 = rowj(jk.y), r6 = rowj(jk.z), r7 = rowj(jk.w);
-        for (int mm = 0; mm < nch8; mm += 8) {
-          const float4 c0 = r0, c1 = r1, c2 = r2, c3 = r3, c4 = r4, c5 = r5, c6 = r6, c7 = r7;
-          if (mm + 8 < nch8) {
-            jj = *reinterpret_cast<const int4*>(&L.j[mm + 8]);
-            jk = *reinterpret_cast<const int4*>(&L.j[mm + 12]);
-            r0 = rowj(jj.x); r1 = rowj(jj.y); r2 = rowj(jj.z); r3 = rowj(jj.w);
-            r4 = rowj(jk.x); r5 = rowj(jk.y); r6 = rowj(jk.z); r7 = rowj(jk.w);
-          }
-          use(mm, c0); use(mm + 1, c1); use(mm + 2, c2); use(mm + 3, c3);
-          use(mm + 4, c4); use(mm + 5, c5); use(mm + 6, c6); use(mm + 7, c7);
-        }
-#else
+        // (eight row loads in flight per wave instead of four push the kernel past 128 VGPRs: 29 % slower, profiles/r6_conv_fwd.md)
         const int nch4 = (nch + 3) & ~3;  // rows >= nch have gs = 0 and a valid (clamped) index: harmless
         // (the four ids of a group come with one uniform-address ds_read_b128; mm + 4 <= 60 inside the guard)
         int4 jj = *reinterpret_cast<const int4*>(&L.j[0]);
         float4 r0 = rowj(jj.x), r1 = rowj(jj.y), r2 = rowj(jj.z), r3 = rowj(jj.w);
-#ifndef AIMNET_PROBE_FWD_PINGPONG  // one register set, rotated by copies (two 64-bit moves per pair)
+        // one register set, rotated by copies (two 64-bit moves per pair); two sets in turn need no copies but 64 B of scratch at
+        // 128 VGPRs: 65.7 against 61.7 us per dispatch (profiles/r6_conv_fwd.md)
         for (int mm = 0; mm < nch4; mm += 4) {
           const float4 c0 = r0, c1 = r1, c2 = r2, c3 = r3;
           if (mm + 4 < nch4) {
@@ -313,25 +280,6 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : AIMNET_PROBE_FWD_OCC) void conv_fw
           }
           use(mm, c0); use(mm + 1, c1); use(mm + 2, c2); use(mm + 3, c3);
         }
-#else
-        // measurement build: two register sets in turn (r and s), no copies - 55 instead of 67 vector instructions per four pairs, but
-        // the kernel then needs 64 B of scratch at 128 VGPRs: 65.7 against 63.4 us per dispatch (profiles/r6_conv_fwd.md)
-        float4 s0 = r0, s1 = r1, s2 = r2, s3 = r3;
-        for (int mm = 0; mm < nch4; mm += 8) {
-          if (mm + 4 < nch4) {
-            jj = *reinterpret_cast<const int4*>(&L.j[mm + 4]);
-            s0 = rowj(jj.x); s1 = rowj(jj.y); s2 = rowj(jj.z); s3 = rowj(jj.w);
-          }
-          use(mm, r0); use(mm + 1, r1); use(mm + 2, r2); use(mm + 3, r3);
-          if (mm + 4 >= nch4) break;
-          if (mm + 8 < nch4) {
-            jj = *reinterpret_cast<const int4*>(&L.j[mm + 8]);
-            r0 = rowj(jj.x); r1 = rowj(jj.y); r2 = rowj(jj.z); r3 = rowj(jj.w);
-          }
-          use(mm + 4, s0); use(mm + 5, s1); use(mm + 6, s2); use(mm + 7, s3);
-        }
-#endif
-#endif
       }
     }
     if (!SPLIT) prefetch_atom(i0 + al.step);  // lands under the epilogue below
@@ -406,13 +354,8 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : AIMNET_PROBE_FWD_OCC) void conv_fw
         const int o = lane + 64 * t;  // (a, h) = (o / 12, o % 12)
         const int aa = o / H_;
         float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-#ifdef AIMNET_PROBE_FWD_NO_EPI  // measurement builds only (tests/tools/variant.sh): what the agh contraction costs
-#pragma unroll 1
-        for (int g = 0; g < 1; ++g) {
-#else
 #pragma unroll UNR_G
         for (int g = 0; g < G_; ++g) {
-#endif
           const float w = s_agh[g * (A_ * H_) + o];  // o = aa * H + hh
           const float* s3 = &sv[(aa * G_ + g) * 3];
           v0 += w * s3[0];
@@ -472,7 +415,7 @@ int launch_conv_fwd(hipStream_t s, int nq, const float* a, const int* row_of, co
 
   // (one-wave-per-atom form: exactly the 4 blocks per CU that are resident - with twice as many the second half only queues
   // behind the first and pays the block prologue again: 0.217 -> 0.207 ms/step over the three launches)
-  const int grid = split ? n_atoms : min(ceil_div(n_atoms, APB), device_cus() * AIMNET_PROBE_FWD_OCC);
+  const int grid = split ? n_atoms : min(ceil_div(n_atoms, APB), device_cus() * 4);
   if (species_moments && row_of && nq == 0 && !split) {  // pass 0 of a large system: per-element moments instead of row gathers
     if (x_split == 2)
       hipLaunchKernelGGL((conv_fwd_kernel<0, false, true, 2>), dim3(grid), dim3(256), 0, s, a, row_of, q, nb_idx, nb_cnt, pg, cap,
@@ -612,9 +555,6 @@ __global__ __launch_bounds__(256) void unconcat_kernel(const float* __restrict__
           v1 += w * v3[1];
           v2 += w * v3[2];
         }
-#ifdef AIMNET_PROBE_SBAR16  // measurement builds only: what storing the vector planes of Sbar in fp16 would do to the forces
-        v0 = (float)(_Float16)v0; v1 = (float)(_Float16)v1; v2 = (float)(_Float16)v2;
-#endif
         vv[0][gi] = v0; vv[1][gi] = v1; vv[2][gi] = v2;
       }
       // (plane 0, the scalar part of xbar, is not stored: conv_bwd_kernel reads it from the xbar row itself)
@@ -712,10 +652,9 @@ __global__ __launch_bounds__(256, 4) void conv_bwd_kernel(const float* __restric
   const int g4 = (lane & 3) * 4;
   const float shift_l = bp.shifts[lane & 15];  // the table loop below gives lane l the shift l & 15 in every iteration
   const int qg = lane >> 2, qc = lane & 3;
-  const float qm0 = qc == 0 ? 1.f : 0.f, qm1 = qc == 1 ? 1.f : 0.f, qm2 = qc == 2 ? 1.f : 0.f, qm3 = qc == 3 ? 1.f : 0.f;
+  const float qm1 = qc == 1 ? 1.f : 0.f, qm2 = qc == 2 ? 1.f : 0.f, qm3 = qc == 3 ? 1.f : 0.f;
   const float qsgn = qc == 0 ? 1.f : -1.f;
   const int qc_sel = max(qc - 1, 0);  // word of the staged (ux, uy, uz, d) record that holds the lane's component (qc == 0: 1)
-  (void)qc_sel;
 
   __shared__ float s_red[SPLIT ? 3 * (4 * 64 + 14) : 1];  // SPLIT: per-lane abar partials + 14 reduced scalars of waves 1..3
 
@@ -846,20 +785,16 @@ __global__ __launch_bounds__(256, 4) void conv_bwd_kernel(const float* __restric
                              {mk2(R.s2.x, R.s2.y), mk2(R.s2.z, R.s2.w)}, {mk2(R.s3.x, R.s3.y), mk2(R.s3.z, R.s3.w)}};
         f2 Dv = mk2(0.f, 0.f), U0v = mk2(0.f, 0.f), U1v = mk2(0.f, 0.f), U2v = mk2(0.f, 0.f);
         const f2 uxy = mk2(u.x, u.y), uzw = mk2(u.z, u.w);  // (halves of the 16-byte LDS read: no instruction)
-        (void)uxy; (void)uzw;
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-#ifdef AIMNET_PROBE_BWD_SPLAT_MOV  // measurement build: the compiler's form (v_mov pairs build the {u, u} splats)
-          const f2 Pp = Sj[0][hf] - (u.x * Sj[1][hf] + u.y * Sj[2][hf] + u.z * Sj[3][hf]);
-#else
           // the component of u taken from its register pair by the packed instructions' op_sel modifiers (conv_common.h,
           // pk_fma_bcast): no splat moves.  (Not bit-identical to the compiler's form - it contracts the sums differently - but the
-          // same arithmetic to fp32 rounding: checksums differ in the last bits, every parity test unchanged.)
+          // same arithmetic to fp32 rounding: checksums differ in the last bits, every parity test unchanged.  7 of 11 moves per two
+          // pairs go, 147.5 -> 146.2 us per dispatch: profiles/r6_conv_fwd.md)
           f2 Tj = pk_mul_bcast<false>(Sj[1][hf], uxy);
           pk_fma_bcast<true>(Tj, Sj[2][hf], uxy);
           pk_fma_bcast<false>(Tj, Sj[3][hf], uzw);
           const f2 Pp = Sj[0][hf] - Tj;
-#endif
           if (NEED_ABAR) ab[hf] += gsv[hf] * Pp;
           const f2 tp = gsv[hf] * ai[hf];
           if (XE) {
@@ -868,14 +803,10 @@ __global__ __launch_bounds__(256, 4) void conv_bwd_kernel(const float* __restric
             U1v += tp * Sj[2][hf];
             U2v += tp * Sj[3][hf];
           } else {
-#ifdef AIMNET_PROBE_BWD_SPLAT_MOV
-            const f2 P = Si[0][hf] + (u.x * Si[1][hf] + u.y * Si[2][hf] + u.z * Si[3][hf]);
-#else
             f2 Ti = pk_mul_bcast<false>(Si[1][hf], uxy);
             pk_fma_bcast<true>(Ti, Si[2][hf], uxy);
             pk_fma_bcast<false>(Ti, Si[3][hf], uzw);
             const f2 P = Si[0][hf] + Ti;
-#endif
             Dv += dg[hf] * (aj[hf] * P + ai[hf] * Pp);
             const f2 t = gsv[hf] * aj[hf];
             U0v += tp * Sj[1][hf] - t * Si[1][hf];
@@ -886,15 +817,11 @@ __global__ __launch_bounds__(256, 4) void conv_bwd_kernel(const float* __restric
         D = Dv.x + Dv.y; U0 = U0v.x + U0v.y; U1 = U1v.x + U1v.y; U2 = U2v.x + U2v.y;
         if (HAS_Q) {
           // lane (g, c) of the charge convolution Sq[g,c] = sum_m q_j gs_g (1,u)_c, branch-free:
-          // qm0..qm3 are the lane's one-hot component selectors, qsgn = (1,-1,-1,-1)[c] for the reverse pair
+          // qm1..qm3 are the lane's one-hot selectors of the vector components, qsgn = (1,-1,-1,-1)[c] for the reverse pair
           const float gq = L.gs[mm][qg], dgq = L.dgs[mm][qg];
-#ifdef AIMNET_PROBE_BWD_SPLAT_MOV
-          const float uc = qm0 + qm1 * u.x + qm2 * u.y + qm3 * u.z;
-#else
           // (1, ux, uy, uz)[c] read from the staged pair record and a select, instead of three FMAs with 0 / 1 weights
           float uc = reinterpret_cast<const float*>(&L.ud[mm])[qc_sel];
           uc = qc == 0 ? 1.0f : uc;
-#endif
 #pragma unroll
           for (int ch = 0; ch < NQ; ++ch) {
             const float sqj = R.sq[ch];

@@ -1,4 +1,4 @@
-// conv_common.h - constants and helpers shared by the gather-contract kernels (conv.hip, conv_mfma.hip).
+// conv_common.h - constants and helpers shared by the gather-contract kernels (conv.hip).
 #pragma once
 
 #include "common.h"
@@ -98,9 +98,7 @@ __device__ __forceinline__ void lds_sync() {
   }
 }
 
-// v_mfma_f32_4x4x1_16B_f32: 16 independent 4x4 outer products, A: lane 4b + r, B: lane 4b + col, C: VGPR r of lane 4b + col
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 
 template <int CTRL>
 __device__ __forceinline__ float dpp0(float v) {  // DPP move, lanes without a source read 0

@@ -313,11 +313,7 @@ __global__ __launch_bounds__(256) void d3_pair_kernel(const float4* __restrict__
       pe = fmaf(pe, tt, 2.301390953e-01f);
       pe = fmaf(pe, tt, 2.838921720e-01f);
       pe = fmaf(pe, tt, 2.820105286e-01f);
-#ifdef AIMNET_PROBE_D3_ERFCF  // measurement build: the library erfc of rounds 1 - 5 (tests/tools/d3prof.sh)
-      const float ec = erfcf(al * P.d);
-#else
       const float ec = pe * tt * ex;
-#endif
       const float w = ec * inv - sv + (P.d - Rc) * slope;
       A.ec += (double)(w * qc_i * qj);
       if (GRAD) {

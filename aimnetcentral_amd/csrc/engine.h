@@ -59,13 +59,13 @@ struct aimnet_engine {
   int nq = 1;  // charge channels (arch.n_charge_channels, 0 -> 1)
   int device;
   std::vector<void*> allocs;
-  float *afv, *afv_t, *agh_a, *agh_q;  // afv_t: the embedding rows in the operand layout of the MFMA conv kernels
+  float *afv, *agh_a, *agh_q;
   // Pass 0, first MLP layer: the first 256 input columns are the constant embedding row afv[Z_i], so their product with the
   // weights is one of 64 constant vectors: emb_bias0[z] = b + W[:, :256] . afv[z] (fp64 sums at create time).  The GEMM then
   // runs over the 448 conv columns only (K 704 -> 448) with this table as a row-indexed bias.  set_option("emb_bias", 0) keeps
   // the full-width GEMM (A/B and parity runs).
   float* emb_bias0 = nullptr;
-  bool emb_bias = true;
+  int emb_bias = 1;
   // MLP GEMMs: 1 (default) = bf16x3-split operands on the bf16 matrix pipe (gemm_bf3.hip: fp32 == three bf16 planes exactly, six
   // products per tile, fp32 accumulation - the fp32 result to within the fp32 rounding of the accumulation itself) for batches above
   // 256 rows, the exact-fp32 skinny kernel below; 2 = bf3 for every batch size (parity runs on small fixtures); 0 = the exact-fp32
@@ -133,18 +133,13 @@ struct aimnet_engine {
   std::vector<int> z_of_slot_h;  // host copy (slot -> atomic number)
   // DFT-D3 tables re-indexed by species slot (aimnet_engine_set_dftd3); d3.ns == 0 until set
   D3Tables d3{0, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool spatial_order = true;  // AIMNET_SPATIAL_ORDER=0: conv kernels walk the atoms in input order
+  int spatial_order = 1;  // AIMNET_SPATIAL_ORDER=0: conv kernels walk the atoms in input order
   // AIMNET_KEEP_INTERMEDIATES=1: every MLP input row x[p] and hidden activation h[p][l] gets its own buffer (debug views of
   // all of them stay valid after an evaluation).  Default: they share one / two buffers - each is dead as soon as the next
   // GEMM has consumed it (the backward reads GELU', not the activations), and a buffer that is rewritten while its lines
   // are still in the Infinity Cache never costs HBM write bandwidth
-  bool keep_intermediates = false;
-  bool p0_moments = true;  // AIMNET_P0_MOMENTS=0 keeps the generic conv_fwd / conv_bwd for pass 0 (A/B and parity runs)
-  // AIMNET_CONV_MFMA / set_option("conv_mfma"): bit 0 = conv_fwd, bit 1 = conv_bwd (+ unconcat T layout) on the 4x4x1 MFMA
-  // kernels of conv_mfma.hip for systems above the split threshold; 0 (default) = the packed-FMA VALU kernels of conv.hip.
-  // Measured on config 3 (profiles/r2_conv_mfma.md): forward 81 us either way, backward 293 vs 226 us - neither form is
-  // arithmetic-bound, so the matrix pipe buys nothing here and the VALU kernels stay the default.
-  int conv_mfma = 0;
+  int keep_intermediates = 0;
+  int p0_moments = 1;  // AIMNET_P0_MOMENTS=0 keeps the generic conv_fwd / conv_bwd for pass 0 (A/B and parity runs)
   // AIMNET_CONV_XE / set_option("conv_xe"): the reverse-pair form of the conv backward (conv.hip, conv_bwd_kernel<.., XE>) for
   // passes >= 1 of systems above the split threshold: every ordered pair evaluates only its own half of the pair adjoints (no
   // a_j gather, 4 KiB per pair instead of 5.25 KiB), F1 goes through a pair buffer and a reverse-pair map (per-atom hash tables of the rows).
@@ -156,7 +151,7 @@ struct aimnet_engine {
   // AIMNET_OVERLAP_COULOMB / set_option("overlap_coulomb"): the Coulomb / DFT-D3 pair kernels (VALU-bound, they need only the
   // final charges) run on a second HIP stream next to the last pass' MLP, the energy head and the first backward GEMMs
   // (MFMA-bound): forked after the last charge update, joined in front of the first conv backward
-  bool overlap_coulomb = false;  // measured (profiles/r2_summary.md): 2.135 vs 2.118 ms/step - concurrent kernels of one process slow each other down here too
+  int overlap_coulomb = 0;  // measured (profiles/r2_summary.md): 2.135 vs 2.118 ms/step - concurrent kernels of one process slow each other down here too
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   std::vector<Layer> mlp[AIMNET_MAX_PASS];

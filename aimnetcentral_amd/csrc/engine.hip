@@ -111,6 +111,57 @@ int upload_layer(aimnet_engine* e, const float* w, const float* b, int n_in, int
   return 0;
 }
 
+// ---- engine switches: one row per switch.  The environment (once, at engine create), aimnet_engine_set_option and
+// aimnet_engine_get_option all walk this table; what each switch does is described next to its member in engine.h, the
+// user-facing list is in include/aimnet_hip.h.
+enum OptKind { OPT_BOOL, OPT_RANGE, OPT_RETIRED };  // stored as value != 0 / clamped to [lo, hi] / reads 0 and accepts only 0
+struct OptionRow {
+  const char* name;  // option name (NULL: environment only)
+  const char* env;   // environment variable read at engine create (OPT_RETIRED: where the removal is recorded)
+  int aimnet_engine::*field;
+  OptKind kind;
+  int lo, hi;
+};
+const OptionRow OPTIONS[] = {
+    {"conv_xe", "AIMNET_CONV_XE", &aimnet_engine::conv_xe, OPT_BOOL, 0, 1},
+    {"emb_bias", "AIMNET_EMB_BIAS", &aimnet_engine::emb_bias, OPT_BOOL, 0, 1},
+    {"gemm_bf3", "AIMNET_GEMM_BF3", &aimnet_engine::gemm_bf3, OPT_RANGE, 0, 2},
+    {"gemm_presplit", "AIMNET_GEMM_PRESPLIT", &aimnet_engine::gemm_presplit, OPT_BOOL, 0, 1},
+    {"gemm_h2", "AIMNET_GEMM_H2", &aimnet_engine::gemm_h2, OPT_BOOL, 0, 1},
+    {"head_fused", "AIMNET_HEAD_FUSED", &aimnet_engine::head_fused, OPT_BOOL, 0, 1},
+    {"prep_fused", "AIMNET_PREP_FUSED", &aimnet_engine::prep_fused, OPT_BOOL, 0, 1},
+    {"energy_rides", "AIMNET_ENERGY_RIDES", &aimnet_engine::energy_rides, OPT_BOOL, 0, 1},
+    {"status_rides", "AIMNET_STATUS_RIDES", &aimnet_engine::status_rides, OPT_BOOL, 0, 1},
+    {"setup_rides", "AIMNET_SETUP_RIDES", &aimnet_engine::setup_rides, OPT_BOOL, 0, 1},
+    {"status_owned", "AIMNET_STATUS_OWNED", &aimnet_engine::status_owned, OPT_BOOL, 0, 1},
+    {"sums_whole", "AIMNET_SUMS_WHOLE", &aimnet_engine::sums_whole, OPT_BOOL, 0, 1},
+    {"nse_merged", "AIMNET_NSE_MERGED", &aimnet_engine::nse_merged, OPT_BOOL, 0, 1},
+    {"gemm_chain", "AIMNET_GEMM_CHAIN", &aimnet_engine::gemm_chain, OPT_BOOL, 0, 1},
+    {"d3_cn_rides", "AIMNET_D3_CN_RIDES", &aimnet_engine::d3_cn_rides, OPT_BOOL, 0, 1},
+    {"dsf_np_walk", "AIMNET_DSF_NP_WALK", &aimnet_engine::dsf_np_walk, OPT_BOOL, 0, 1},
+    {"split_max", "AIMNET_SPLIT_MAX", &aimnet_engine::split_max, OPT_RANGE, 0, INT32_MAX},
+    {"p0_moments", "AIMNET_P0_MOMENTS", &aimnet_engine::p0_moments, OPT_BOOL, 0, 1},
+    {"overlap_coulomb", "AIMNET_OVERLAP_COULOMB", &aimnet_engine::overlap_coulomb, OPT_BOOL, 0, 1},
+    {"spatial_order", "AIMNET_SPATIAL_ORDER", &aimnet_engine::spatial_order, OPT_BOOL, 0, 1},
+    {nullptr, "AIMNET_KEEP_INTERMEDIATES", &aimnet_engine::keep_intermediates, OPT_BOOL, 0, 1},
+    {"conv_mfma", "profiles/r2_conv_mfma.md", nullptr, OPT_RETIRED, 0, 0},
+};
+const OptionRow* find_option(const char* name) {
+  for (const OptionRow& r : OPTIONS)
+    if (r.name && !strcmp(r.name, name)) return &r;
+  return nullptr;
+}
+// the value a switch stores for a request from either source
+int option_value(const OptionRow& r, int v) {
+  if (r.field == &aimnet_engine::split_max && v < 0) return conv_split_max_default();
+  return r.kind == OPT_BOOL ? v != 0 : std::min(r.hi, std::max(r.lo, v));
+}
+void apply_env_options(aimnet_engine* e) {
+  for (const OptionRow& r : OPTIONS) {
+    const char* env = r.kind == OPT_RETIRED ? nullptr : getenv(r.env);
+    if (env) e->*r.field = option_value(r, atoi(env));
+  }
+}
 
 // ---- chain plans (gemm_chain.hip): match an MLP sweep against the instantiated shapes and pack its weight streams ----------------
 constexpr int CHAIN_NW = 8;  // waves per block of the instantiated shapes
@@ -215,7 +266,7 @@ bool head_fusable(const aimnet_engine* e) {
 // activations in split form for this batch? (layout() and eval() must agree)
 bool presplit_active(const aimnet_engine* e, int N) {
   const bool bf3 = e->gemm_bf3 == 2 || (e->gemm_bf3 == 1 && N > 256);  // the batches that take the split GEMMs at all (mlp_gemm)
-  return e->gemm_presplit != 0 && bf3 && !e->keep_intermediates && !(e->conv_mfma & 1);
+  return e->gemm_presplit != 0 && bf3 && !e->keep_intermediates;
 }
 int split_format(const aimnet_engine* e, int n_rows) {
   if (!presplit_active(e, n_rows)) return 0;
@@ -355,7 +406,6 @@ struct Workspace {
   int *lr_idx, *lr_shift, *lr_cnt;
   float4* pg;
   float* a[AIMNET_MAX_PASS];       // features entering pass p
-  float* at[AIMNET_MAX_PASS];      // the same in the MFMA operand layout (conv_mfma.hip), NULL when those kernels are off
   float* q[AIMNET_MAX_PASS];       // charges after pass p (p < n_pass-1)
   float* x[AIMNET_MAX_PASS];       // MLP input rows
   float* V[AIMNET_MAX_PASS];
@@ -412,8 +462,7 @@ void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options*
   const bool grad = (opt->flags & (AIMNET_FORCES | AIMNET_STRESS)) != 0;
   const size_t n = (size_t)N;
   const int cap = std::max(1, opt->max_nb), cap_lr = std::max(0, opt->max_nb_lr);
-  const bool mfma_rows = e->conv_mfma != 0 && N > e->split_max;
-  W.xe = e->conv_xe != 0 && !(e->conv_mfma & 2) && grad && np > 1 && N > e->split_max &&
+  W.xe = e->conv_xe != 0 && grad && np > 1 && N > e->split_max &&
          pair_rev_supported(N, cap) && n * (size_t)cap < (size_t)INT32_MAX;
   char* nl_base = c.take<char>(nlist_scratch_bytes(N, n_mol));
   if (base) nlist_carve(W.nl, nl_base, N, n_mol);
@@ -473,7 +522,6 @@ void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options*
   for (int p = 0; p < np; ++p) {
     snprintf(name, sizeof name, "a%d", p);
     W.a[p] = p == 0 ? nullptr : c.take<float>(n * 256, name, 256);  // pass 0 reads the embedding table itself
-    W.at[p] = (p == 0 || !mfma_rows) ? nullptr : c.take<float>(n * 256);
     snprintf(name, sizeof name, "q%d", p);
     W.q[p] = c.take<float>(n * e->nq, name, 1);
     const int ldx = e->mlp[p][0].k_in;
@@ -563,13 +611,6 @@ int aimnet_engine_create(const aimnet_arch* arch, const aimnet_weights* w, int d
   const int AG = 256;
   if ((rc = dev_upload(e, w->afv, (size_t)64 * AG, &e->afv))) goto fail;
   {
-    std::vector<float> t((size_t)64 * AG);
-    for (int z = 0; z < 64; ++z)
-      for (int aa = 0; aa < 16; ++aa)
-        for (int g = 0; g < 16; ++g) t[(size_t)z * AG + g * 16 + aa] = w->afv[(size_t)z * AG + aa * 16 + g];
-    if ((rc = dev_upload(e, t.data(), t.size(), &e->afv_t))) goto fail;
-  }
-  {
     int soz[64], zos[64];
     int ns = 0, bad_row = -1;
     for (int z = 0; z < 64; ++z) {
@@ -585,51 +626,8 @@ int aimnet_engine_create(const aimnet_arch* arch, const aimnet_weights* w, int d
     e->z_of_slot_h.assign(zos, zos + ns);
     if ((rc = dev_upload(e, soz, (size_t)64, &e->slot_of_z))) goto fail;
     if ((rc = dev_upload(e, zos, (size_t)ns, &e->z_of_slot))) goto fail;
-    const char* env = getenv("AIMNET_P0_MOMENTS");
-    if (env) e->p0_moments = atoi(env) != 0;
-    env = getenv("AIMNET_SPATIAL_ORDER");
-    if (env) e->spatial_order = atoi(env) != 0;
-    env = getenv("AIMNET_KEEP_INTERMEDIATES");
-    if (env) e->keep_intermediates = atoi(env) != 0;
-    env = getenv("AIMNET_CONV_MFMA");
-    if (env) e->conv_mfma = atoi(env);
-    env = getenv("AIMNET_EMB_BIAS");
-    if (env) e->emb_bias = atoi(env) != 0;
-    env = getenv("AIMNET_GEMM_BF3");
-    if (env) e->gemm_bf3 = std::min(2, std::max(0, atoi(env)));
-    env = getenv("AIMNET_GEMM_PRESPLIT");
-    if (env) e->gemm_presplit = atoi(env) != 0;
-    env = getenv("AIMNET_GEMM_H2");
-    if (env) e->gemm_h2 = atoi(env) != 0;
-    env = getenv("AIMNET_HEAD_FUSED");
-    if (env) e->head_fused = atoi(env) != 0;
-    env = getenv("AIMNET_PREP_FUSED");
-    if (env) e->prep_fused = atoi(env) != 0;
-    env = getenv("AIMNET_ENERGY_RIDES");
-    if (env) e->energy_rides = atoi(env) != 0;
-    env = getenv("AIMNET_STATUS_RIDES");
-    if (env) e->status_rides = atoi(env) != 0;
-    env = getenv("AIMNET_SETUP_RIDES");
-    if (env) e->setup_rides = atoi(env) != 0;
-    env = getenv("AIMNET_STATUS_OWNED");
-    if (env) e->status_owned = atoi(env) != 0;
-    env = getenv("AIMNET_SUMS_WHOLE");
-    if (env) e->sums_whole = atoi(env) != 0;
-    env = getenv("AIMNET_NSE_MERGED");
-    if (env) e->nse_merged = atoi(env) != 0;
-    env = getenv("AIMNET_GEMM_CHAIN");
-    if (env) e->gemm_chain = atoi(env) != 0;
+    apply_env_options(e);
     (void)gemm_h2_set_attributes();  // AIMNET_H2_TILE / AIMNET_H2_DEEP (gemm_h2.hip)
-    env = getenv("AIMNET_D3_CN_RIDES");
-    if (env) e->d3_cn_rides = atoi(env) != 0;
-    env = getenv("AIMNET_DSF_NP_WALK");
-    if (env) e->dsf_np_walk = atoi(env) != 0;
-    env = getenv("AIMNET_CONV_XE");
-    if (env) e->conv_xe = atoi(env);
-    env = getenv("AIMNET_SPLIT_MAX");
-    if (env) e->split_max = std::max(0, atoi(env));
-    env = getenv("AIMNET_OVERLAP_COULOMB");
-    if (env) e->overlap_coulomb = atoi(env) != 0;
   }
   if ((rc = dev_upload(e, w->agh_a, (size_t)16 * 16 * 12, &e->agh_a))) goto fail;
   if ((rc = dev_upload(e, w->agh_q, (size_t)e->nq * 16 * 12, &e->agh_q))) goto fail;
@@ -773,63 +771,29 @@ int aimnet_engine_profile_read(aimnet_engine* e, double* ms, int n_families, int
 
 int aimnet_engine_set_option(aimnet_engine* e, const char* name, int value) {
   if (!e || !name) return AIMNET_E_INVALID;
-  const std::string n(name);
-  if (n == "conv_mfma") e->conv_mfma = value & 3;
-  else if (n == "conv_xe") e->conv_xe = value != 0;
-  else if (n == "emb_bias") e->emb_bias = value != 0;
-  else if (n == "gemm_bf3") e->gemm_bf3 = std::min(2, std::max(0, value));
-  else if (n == "gemm_presplit") e->gemm_presplit = value != 0;
-  else if (n == "gemm_h2") e->gemm_h2 = value != 0;
-  else if (n == "head_fused") e->head_fused = value != 0;
-  else if (n == "prep_fused") e->prep_fused = value != 0;
-  else if (n == "energy_rides") e->energy_rides = value != 0;
-  else if (n == "status_rides") e->status_rides = value != 0;
-  else if (n == "setup_rides") e->setup_rides = value != 0;
-  else if (n == "status_owned") e->status_owned = value != 0;
-  else if (n == "sums_whole") e->sums_whole = value != 0;
-  else if (n == "nse_merged") e->nse_merged = value != 0;
-  else if (n == "gemm_chain") e->gemm_chain = value != 0;
-  else if (n == "d3_cn_rides") e->d3_cn_rides = value != 0;
-  else if (n == "dsf_np_walk") e->dsf_np_walk = value != 0;
-  else if (n == "split_max") e->split_max = value < 0 ? conv_split_max_default() : value;
-  else if (n == "p0_moments") e->p0_moments = value != 0;
-  else if (n == "overlap_coulomb") e->overlap_coulomb = value != 0;
-  else if (n == "spatial_order") e->spatial_order = value != 0;
-  else {
+  const OptionRow* r = find_option(name);
+  if (!r) {
     set_last_error("set_option: unknown option '%s'", name);
     return AIMNET_E_INVALID;
   }
+  if (r->kind == OPT_RETIRED) {
+    if (value == 0) return AIMNET_OK;
+    set_last_error("%s was removed (%s)", r->name, r->env);
+    return AIMNET_E_INVALID;
+  }
+  e->*r->field = option_value(*r, value);
   return AIMNET_OK;
 }
 
 int aimnet_engine_get_option(const aimnet_engine* e, const char* name, int* value) {
   if (!e || !name || !value) return AIMNET_E_INVALID;
-  const std::string n(name);
-  if (n == "conv_mfma") *value = e->conv_mfma;
-  else if (n == "conv_xe") *value = e->conv_xe;
-  else if (n == "emb_bias") *value = e->emb_bias ? 1 : 0;
-  else if (n == "gemm_bf3") *value = e->gemm_bf3;
-  else if (n == "gemm_presplit") *value = e->gemm_presplit;
-  else if (n == "gemm_h2") *value = e->gemm_h2 && e->h2_fits;
-  else if (n == "head_fused") *value = e->head_fused;
-  else if (n == "prep_fused") *value = e->prep_fused;
-  else if (n == "energy_rides") *value = e->energy_rides;
-  else if (n == "status_rides") *value = e->status_rides;
-  else if (n == "setup_rides") *value = e->setup_rides;
-  else if (n == "status_owned") *value = e->status_owned;
-  else if (n == "sums_whole") *value = e->sums_whole;
-  else if (n == "nse_merged") *value = e->nse_merged;
-  else if (n == "gemm_chain") *value = e->gemm_chain;
-  else if (n == "d3_cn_rides") *value = e->d3_cn_rides;
-  else if (n == "dsf_np_walk") *value = e->dsf_np_walk;
-  else if (n == "split_max") *value = e->split_max;
-  else if (n == "p0_moments") *value = e->p0_moments ? 1 : 0;
-  else if (n == "overlap_coulomb") *value = e->overlap_coulomb ? 1 : 0;
-  else if (n == "spatial_order") *value = e->spatial_order ? 1 : 0;
-  else {
+  const OptionRow* r = find_option(name);
+  if (!r) {
     set_last_error("get_option: unknown option '%s'", name);
     return AIMNET_E_INVALID;
   }
+  *value = r->kind == OPT_RETIRED ? 0 : e->*r->field;
+  if (r->field == &aimnet_engine::gemm_h2) *value = e->gemm_h2 && e->h2_fits;  // what eval() runs (split_format)
   return AIMNET_OK;
 }
 
@@ -1139,8 +1103,6 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
   const bool ps = sfmt != 0;
   const int pm = sfmt == 2 ? 2 : 3;  // 16-bit elements per fp32 value of a split row
   const bool hfused = ps && head_fusable(e);  // energy head forward + backward in one launch (gemm_head.hip)
-  const bool mfma_fwd = (e->conv_mfma & 1) && N > e->split_max;
-  const bool mfma_bwd = (e->conv_mfma & 2) && N > e->split_max;
   // reverse-pair map through per-atom hash tables of the rows (once per neighbour list)
   // (its only reader is launch_pair_force, the last kernel of the backward.  On one stream the two small kernels ride on later
   // launches instead of standing in front of the forward pass: the hash build on the SR-Coulomb launch, the lookup on the DSF walk
@@ -1250,14 +1212,9 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
     const std::vector<Layer>& Ls = e->mlp[p];
     const int nl = (int)Ls.size();
     RC(prof_mark(e, s, FAM_CONV_FWD));
-    if (mfma_fwd)
-      RC(launch_conv_fwd_mfma(s, p > 0 ? nq : 0, p == 0 ? e->afv : W.a[p], p == 0 ? e->afv_t : W.at[p], p == 0 ? in->numbers : nullptr,
-                              p > 0 ? W.q[p - 1] : nullptr, W.nb_idx, W.nb_cnt, W.pg, cap, e->agh_a, e->agh_q, e->bp, W.x[p],
-                              Ls[0].k_in, W.V[p], W.Vq[p], N, order));
-    else
-      RC(launch_conv_fwd(s, p > 0 ? nq : 0, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr, p > 0 ? W.q[p - 1] : nullptr,
-                         W.nb_idx, W.nb_cnt, W.pg, cap, e->agh_a, e->agh_q, e->bp, W.x[p], Ls[0].k_in, W.V[p], W.Vq[p], N, order,
-                         p == 0 && e->p0_moments, e->split_max, sfmt));
+    RC(launch_conv_fwd(s, p > 0 ? nq : 0, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr, p > 0 ? W.q[p - 1] : nullptr,
+                       W.nb_idx, W.nb_cnt, W.pg, cap, e->agh_a, e->agh_q, e->bp, W.x[p], Ls[0].k_in, W.V[p], W.Vq[p], N, order,
+                       p == 0 && e->p0_moments, e->split_max, sfmt));
     const float* hin = W.x[p];
     int ld_in = Ls[0].k_in;
     RC(prof_mark(e, s, FAM_GEMM));
@@ -1280,7 +1237,7 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
       // (the feature update a^{p+1} = a^p + delta_a rides on the NSE launch: independent work, one kernel boundary less)
       RC(launch_nse_fwd(s, W.H[p][nl - 1], Ls[nl - 1].k_out, nq, p > 0 ? W.q[p - 1] : nullptr, W.nl.mol_start, in->charge,
                         n_mol, N, W.S, (float*)W.part, W.q[p], W.Fm[p], W.Dm[p], p == 0 ? e->afv : W.a[p],
-                        p == 0 ? in->numbers : nullptr, W.a[p + 1], W.at[p + 1], dd));
+                        p == 0 ? in->numbers : nullptr, W.a[p + 1], dd));
       // domain decomposition: the final charges of halo copies are exact only within one cutoff of the owned region, the Coulomb
       // sums reach further - the owners' values come in through the exchange function
       if (dd && p == np - 2 && dd->fn(dd->ctx, AIMNET_DD_CHARGES, W.q[p], (int64_t)nq * N, (void*)s) != 0) {
@@ -1437,19 +1394,12 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
                             order, (W.xe && want_f) ? W.pairbuf : nullptr));
       break;
     }
-    RC((mfma_bwd ? launch_unconcat_t : launch_unconcat)(s, p > 0 ? nq : 0, zcur, ld, W.V[p], W.Vq[p], e->agh_a, e->agh_q, W.Sbar,
-                                                         W.Sqbar, N));
+    RC(launch_unconcat(s, p > 0 ? nq : 0, zcur, ld, W.V[p], W.Vq[p], e->agh_a, e->agh_q, W.Sbar, W.Sqbar, N));
     RC(prof_mark(e, s, FAM_CONV_BWD));
-    if (mfma_bwd) {
-      RC(launch_conv_bwd_mfma(s, p > 0 ? nq : 0, p > 0, want_s, p == 0 ? e->afv_t : W.at[p], p == 0 ? in->numbers : nullptr,
-                              p > 0 ? W.q[p - 1] : nullptr, W.Sbar, W.Sqbar, W.nb_idx, W.nb_cnt, W.pg, cap, e->bp, zcur, ld,
-                              (p < np - 1) ? W.abar : nullptr, W.abar, W.qbar, W.qbar, W.fgrad, W.virial_atom, N, order));
-    } else {
-      RC(launch_conv_bwd(s, p > 0 ? nq : 0, p > 0, want_s, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr,
-                         p > 0 ? W.q[p - 1] : nullptr, W.Sbar, W.Sqbar, W.nb_idx, W.nb_cnt, W.pg, cap, e->bp, zcur, ld,
-                         (p < np - 1) ? W.abar : nullptr, W.abar, W.qbar, W.qbar, W.fgrad, W.virial_atom, N, order,
-                         (W.xe && p > 0) ? W.pairbuf : nullptr, p < np - 1, e->split_max));
-    }
+    RC(launch_conv_bwd(s, p > 0 ? nq : 0, p > 0, want_s, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr,
+                       p > 0 ? W.q[p - 1] : nullptr, W.Sbar, W.Sqbar, W.nb_idx, W.nb_cnt, W.pg, cap, e->bp, zcur, ld,
+                       (p < np - 1) ? W.abar : nullptr, W.abar, W.qbar, W.qbar, W.fgrad, W.virial_atom, N, order,
+                       (W.xe && p > 0) ? W.pairbuf : nullptr, p < np - 1, e->split_max));
     if (p == 0) break;
     // NSE adjoint of pass p-1, then the adjoint of its MLP output
     const std::vector<Layer>& Lq = e->mlp[p - 1];
@@ -1633,15 +1583,6 @@ int aimnet_engine_debug_mlp_sweep(aimnet_engine* e, int pass, int backward, int 
   return rc;
 }
 
-#ifdef AIMNET_PREP_TIMING
-int aimnet_debug_prep_stamps(unsigned long long* host16) { return aimnet::prep_read_stamps(host16); }
-#endif
-#ifdef AIMNET_BF3_TIMING
-int aimnet_debug_bf3a_stamps(unsigned long long* host1024) { return aimnet::gemm_bf3a_read_stamps(host1024); }
-int aimnet_debug_h2_stamps(unsigned long long* host1024) { return aimnet::gemm_h2_read_stamps(host1024); }
-int aimnet_debug_bf3_stamps(unsigned long long* host1024) { return aimnet::gemm_bf3_read_stamps(host1024); }
-#endif
-
 int aimnet_debug_pme_recip(const float* xw, const float* q, const int* order, const float* cell, float total_charge, int n_atoms,
                            float accuracy,
                            int max_mesh, double* e_atom, float* qbar, float* fgrad, float* virial_atom, double* host_info,
@@ -1692,11 +1633,6 @@ done:
   (void)hipFree(b.sys); (void)hipFree(b.frac); (void)hipFree(b.meshq); (void)hipFree(b.ma); (void)hipFree(b.mb); (void)hipFree(b.bmod);
   (void)hipFree(b.vpart); (void)hipFree(mol_idx); (void)hipFree(mol_start); (void)hipFree(status); (void)hipFree(charge);
   return rc;
-}
-
-int aimnet_debug_mfma4_probe(float* out, void* hip_stream) {
-  if (!out) return AIMNET_E_INVALID;
-  return launch_mfma4_probe((hipStream_t)hip_stream, out);
 }
 
 int aimnet_conv_sv_2d_sp_fwd(const float* a, const int32_t* idx, const float* g, float* out, int32_t B, int32_t A,

@@ -162,9 +162,6 @@ constexpr int bf3_lds_bytes(int SM, int SN, int WM, int WN, int NSTB) {
   return 2 * bf3_a_rows(16 * SM * WM) * ROWB + NSTB * bf3_b_passes(16 * SN * WN) * 8192;
 }
 
-#ifdef AIMNET_BF3_TIMING
-__device__ unsigned long long g_bf3_stamps[1024];
-#endif
 
 // Accumulation bias.  v_mfma_f32_16x16x32_bf16 aligns its 32 products and the accumulator in a fixed-point adder and TRUNCATES
 // what falls below its width - two's-complement truncation, i.e. always towards minus infinity.  One instruction loses ~2^-7.5 of
@@ -305,26 +302,6 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(232))) void 
   // unconditional: a conditional asm load makes the compiler merge "loaded" and "not loaded" registers with copies placed right
   // behind the load, i.e. before the data has arrived.
   auto kc = [&](int k) __attribute__((always_inline)) { return min(k, nk - 1); };
-#ifdef AIMNET_BF3_TIMING
-  // measurement build: waves 0 and 4 of block 0 stamp s_memtime at every segment boundary (g_bf3_stamps, 2 x 512 entries)
-  int n_ts = 0;
-  auto TS = [&]() __attribute__((always_inline)) {
-    if (blockIdx.x == 0 && (wid & 3) == 0 && n_ts < 512) {
-      const unsigned long long t = __builtin_readcyclecounter();
-      if (lane == 0) g_bf3_stamps[(wid >> 2) * 512 + n_ts] = t;
-      ++n_ts;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#else
-  auto TS = [&]() __attribute__((always_inline)) {};
-#endif
-#ifdef AIMNET_BF3_TIMING_FINE
-#define TSF() TS()
-#else
-#define TSF()
-#endif
-  TS();  // kernel entry
   // ---- prologue.  VMEM issue order of a wave in the steady state (g = group, A_L / A_C = the quads split in the load / compute
   // segment): ... B(j+1), A_L(j+2) [L(j-1)], A_C(j+2+g) [C(j-1)], B(j+2), A_L(j+3) [L(j)], A_C(j+3+g) [C(j)] ...; the prologue
   // continues that pattern backwards so that the constant wait counts hold from step 0 on.
@@ -337,7 +314,6 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(232))) void 
   if (QC > 0 && late) load_q(I1{}, QL{}, QE{}, kc(1));
   wait_vm<0>();
   __builtin_amdgcn_sched_barrier(0);
-  TS();
   split_r(I0{}, I0{}, QE{}, 0);  // SA[0]
   if (QC > 0 && late) split_r(I1{}, QL{}, QE{}, SA_BYTES);
   load_q(I1{}, I0{}, QL{}, kc(1));                  // "L(-2)": A_L(1)
@@ -367,39 +343,28 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(232))) void 
     constexpr int PAR = decltype(par_c)::value;
     using NPAR = std::integral_constant<int, PAR ^ 1>;
     const unsigned oa = adA + PAR * SA_BYTES, ob = adB + st * BST_BYTES;
-#ifdef AIMNET_BF3_PRIO_L  // measurement builds: issue priority of the load / split segment against the partner's matrix segment
-    __builtin_amdgcn_s_setprio(AIMNET_BF3_PRIO_L);
-#endif
     read_strips<0, SN, 0>(fb, ob);
     read_strips<0, SM, 0>(fa, oa);
     read_strips<0, SN, 1>(fb, ob);
     read_strips<0, SM, 1>(fa, oa);
     read_strips<0, SN, 2>(fb, ob);
     read_strips<0, SM, 2>(fa, oa);
-    TSF();
     dma_b(st == 0 ? 2 : st - 1, kc(j + 2));
-    TSF();
     if constexpr (NL > 0) {
       wait_vm<2 * NPB + NL + 2 * QC>();  // A_L(j+1); younger: A_C(j+1+g), B(j+1), A_L(j+2), A_C(j+2+g), B(j+2)
       __builtin_amdgcn_sched_barrier(0);
-      TSF();
       split_r(NPAR{}, I0{}, QL{}, (PAR ^ 1) * SA_BYTES);
-      TSF();
       load_q(NPAR{}, I0{}, QL{}, kc(j + 3));
     }
     wait_vm<2 * NL + QC + NPB>();  // this wave's pieces of weight stage j+1; younger: A_L(j+2), A_C(j+2+g), B(j+2), A_L(j+3)
     wait_lgkm<0>();                // fragments in registers, split planes written
     __builtin_amdgcn_sched_barrier(0);
-    TSF();
   };
   // C(j): the 6 x SM x SN matrix instructions of step j on registers, and among them the split of the last QC quads of A(m),
   // m = j + 1 + g (set m & 1 = MPAR), into SA[m & 1], followed by the loads of the same quads of A(m + 2).  At step kneg the sign
   // of the accumulators flips: the weight blocks from there on are stored negated ("Accumulation bias" above).
   auto seg_compute = [&](int j, int m, auto mpar_c) __attribute__((always_inline)) {
     constexpr int MPAR = decltype(mpar_c)::value;
-#ifdef AIMNET_BF3_PRIO_C
-    __builtin_amdgcn_s_setprio(AIMNET_BF3_PRIO_C);
-#endif
     if (j == kneg && j > 0) {
 #pragma unroll
       for (int i = 0; i < SM; ++i)
@@ -433,10 +398,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(232))) void 
     __builtin_amdgcn_sched_barrier(0);
   };
   auto bar = [&]() __attribute__((always_inline)) {
-    TS();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    TS();
   };
   // the two groups run the same step sequence, group 1 one barrier later; m = j + 1 + g: its parity is fixed per code path
   auto run = [&](auto g_c) __attribute__((always_inline)) {
@@ -469,7 +432,6 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(232))) void 
   }
   wait_vm<0>();  // the clamped look-ahead of the last steps is still in flight; the wave must not end (LDS released) under its DMA
   __builtin_amdgcn_sched_barrier(0);
-  TS();  // main loop done
 
   // epilogue: sfin * acc[i][j][r] = C[m0 + wm*16*SM + 16 i + (lane&15)][n0 + wn*16*SN + 16 j + 4 (lane>>4) + r]
   const float sfin = kneg < nk ? -1.0f : 1.0f;  // the accumulators ended in the negated phase
@@ -508,13 +470,6 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(232))) void 
       }
     }
   }
-#ifdef AIMNET_BF3_TIMING
-  __builtin_amdgcn_sched_barrier(0);
-  TS();  // epilogue stores issued
-  wait_vm<0>();
-  __builtin_amdgcn_sched_barrier(0);
-  TS();  // ... and acknowledged
-#endif
 }
 
 template <int SM, int SN, int WN, int QC>
@@ -604,12 +559,6 @@ int launch_gemm_bf3_cfg(hipStream_t stream, int cfg, int epi, const float* A, in
   }
 }
 
-#ifdef AIMNET_BF3_TIMING
-int gemm_bf3_read_stamps(unsigned long long* host1024) {
-  AIMNET_HIP_CHECK(hipMemcpyFromSymbol(host1024, HIP_SYMBOL(g_bf3_stamps), 1024 * sizeof(unsigned long long)));
-  return 0;
-}
-#endif
 
 int gemm_bf3_set_attributes() {
   const char* env = getenv("AIMNET_BF3_TILE");

@@ -33,9 +33,6 @@ namespace aimnet {
 constexpr int bf3a_passes(int rows) { return (rows * 12 + 255) / 256; }  // DMA wave-instructions per wave of the issuing group
 constexpr int bf3a_lds_bytes(int TM, int TN) { return 2 * bf3a_passes(TM) * 4096 + 3 * bf3a_passes(TN) * 4096; }
 
-#ifdef AIMNET_BF3_TIMING
-__device__ unsigned long long g_bf3a_stamps[1024];
-#endif
 
 template <int EPI, int SM, int SN, int WN, bool OUT3>
 __global__ __launch_bounds__(512, 2) void gemm_bf3a_kernel(const unsigned short* __restrict__ A3, int lda3,
@@ -126,20 +123,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf3a_kernel(const unsigned short*
   // every step issues the same operations: k-steps past the end of K are clamped to the last one (redundant tiles nothing reads)
   auto kc = [&](int k) __attribute__((always_inline)) { return min(k, nk - 1); };
 
-#ifdef AIMNET_BF3_TIMING
-  int n_ts = 0;
-  auto TS = [&]() __attribute__((always_inline)) {
-    if (blockIdx.x == 0 && (wid & 3) == 0 && n_ts < 512) {
-      const unsigned long long t = __builtin_readcyclecounter();
-      if (lane == 0) g_bf3a_stamps[(wid >> 2) * 512 + n_ts] = t;
-      ++n_ts;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#else
-  auto TS = [&]() __attribute__((always_inline)) {};
-#endif
-  TS();
   // ---- prologue: A(0) by group 0; B(0), B(1) by group 1
   if (!late) {
     dma_a(0, 0);
@@ -150,7 +133,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf3a_kernel(const unsigned short*
     wait_vm<NPB>();
   }
   __builtin_amdgcn_sched_barrier(0);
-  TS();
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 
@@ -192,10 +174,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf3a_kernel(const unsigned short*
     __builtin_amdgcn_sched_barrier(0);
   };
   auto bar = [&]() __attribute__((always_inline)) {
-    TS();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    TS();
   };
   auto run = [&](auto g_c) __attribute__((always_inline)) {
     int st = 0, j = 0;
@@ -226,7 +206,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf3a_kernel(const unsigned short*
   }
   wait_vm<0>();  // the clamped look-ahead of the last steps: the wave must not end (LDS released) under its DMA
   __builtin_amdgcn_sched_barrier(0);
-  TS();
 
   // epilogue: sfin * acc[i][j][r] = C[m0 + wm*16*SM + 16 i + (lane&15)][n0 + wn*16*SN + 16 j + 4 (lane>>4) + r]
   // even-step set +/- odd-step set: alt 0 = plain weights (sum), 1 = BF3_ALT weights from an even k-block (difference), 2 = from an odd one
@@ -299,13 +278,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf3a_kernel(const unsigned short*
       }
     }
   }
-#ifdef AIMNET_BF3_TIMING
-  __builtin_amdgcn_sched_barrier(0);
-  TS();
-  wait_vm<0>();
-  __builtin_amdgcn_sched_barrier(0);
-  TS();
-#endif
 }
 
 template <int SM, int SN, int WN>
@@ -399,12 +371,6 @@ int launch_gemm_bf3a_cfg(hipStream_t stream, int cfg, int epi, bool out3, const 
   }
 }
 
-#ifdef AIMNET_BF3_TIMING
-int gemm_bf3a_read_stamps(unsigned long long* host1024) {
-  AIMNET_HIP_CHECK(hipMemcpyFromSymbol(host1024, HIP_SYMBOL(g_bf3a_stamps), 1024 * sizeof(unsigned long long)));
-  return 0;
-}
-#endif
 
 int gemm_bf3a_set_attributes() {
   const char* env = getenv("AIMNET_BF3A_TILE");

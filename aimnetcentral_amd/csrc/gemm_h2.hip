@@ -34,9 +34,6 @@ constexpr int h2_passes(int rows) { return (rows + 31) / 32; }  // DMA wave-inst
 constexpr int h2_nsb(int NSA) { return NSA == 4 ? 4 : 3; }  // weight ring depth that goes with an activation ring depth
 constexpr int h2_lds_bytes(int TM, int TN, int NSA) { return NSA * h2_passes(TM) * 4096 + h2_nsb(NSA) * h2_passes(TN) * 4096; }
 
-#ifdef AIMNET_BF3_TIMING
-__device__ unsigned long long g_h2_stamps[1024];
-#endif
 
 template <int EPI, int SM, int SN, int WN, bool OUT3, int NSA>
 __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* __restrict__ A3, int lda3,
@@ -128,24 +125,10 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* _
   // every step issues the same operations: k-steps past the end of K are clamped to the last one (redundant tiles nothing reads)
   auto kc = [&](int k) __attribute__((always_inline)) { return min(k, nk - 1); };
 
-#ifdef AIMNET_BF3_TIMING
-  int n_ts = 0;
-  auto TS = [&]() __attribute__((always_inline)) {
-    if (blockIdx.x == 0 && (wid & 3) == 0 && n_ts < 512) {
-      const unsigned long long t = __builtin_readcyclecounter();
-      if (lane == 0) g_h2_stamps[(wid >> 2) * 512 + n_ts] = t;
-      ++n_ts;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#else
-  auto TS = [&]() __attribute__((always_inline)) {};
-#endif
   f16x8 fa[SM][2], fb[SN][2];
 #define AIMNET_H2_PRODUCT(SET, PA, PB)                                                                                      \
   _Pragma("unroll") for (int i = 0; i < SM; ++i) _Pragma("unroll") for (int jj = 0; jj < SN; ++jj) acc[SET][i][jj] = \
       __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[jj][PB], fa[i][PA], acc[SET][i][jj], 0, 0, 0);
-  TS();
   // ---- prologue: A(0) by group 0; B(0), B(1) by group 1
   constexpr int NSB = h2_nsb(NSA);  // lead of the requests: NSA - 1 steps for activation tiles, NSB - 1 for weight tiles
   if (!late) {
@@ -158,7 +141,6 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* _
     wait_vm<(NSB - 2) * NPB>();  // B(0) has landed
   }
   __builtin_amdgcn_sched_barrier(0);
-  TS();
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 
@@ -191,10 +173,8 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* _
     __builtin_amdgcn_sched_barrier(0);
   };
   auto bar = [&]() __attribute__((always_inline)) {
-    TS();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    TS();
   };
   auto run = [&](auto g_c) __attribute__((always_inline)) {
     int sa = 0, sb = 0, j = 0;
@@ -230,7 +210,6 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* _
 #undef AIMNET_H2_PRODUCT
   wait_vm<0>();  // the clamped look-ahead of the last steps: the wave must not end (LDS released) under its DMA
   __builtin_amdgcn_sched_barrier(0);
-  TS();
 
   // epilogue: sfin * acc[i][j][r] = C[m0 + wm*16*SM + 16 i + (lane&15)][n0 + wn*16*SN + 16 j + 4 (lane>>4) + r]
   // even-step set +/- odd-step set: alt 0 = plain weights (sum), 1 = BF3_ALT weights from an even k-block (difference), 2 = from an odd one
@@ -303,13 +282,6 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* _
       }
     }
   }
-#ifdef AIMNET_BF3_TIMING
-  __builtin_amdgcn_sched_barrier(0);
-  TS();
-  wait_vm<0>();
-  __builtin_amdgcn_sched_barrier(0);
-  TS();
-#endif
 }
 
 // (A one-instruction-stream-per-wave schedule - fragments of step j+1 fetched into the registers step j's products release, one
@@ -420,12 +392,6 @@ int launch_gemm_h2_cfg(hipStream_t stream, int cfg, int epi, bool out3, const un
   }
 }
 
-#ifdef AIMNET_BF3_TIMING
-int gemm_h2_read_stamps(unsigned long long* host1024) {
-  AIMNET_HIP_CHECK(hipMemcpyFromSymbol(host1024, HIP_SYMBOL(g_h2_stamps), 1024 * sizeof(unsigned long long)));
-  return 0;
-}
-#endif
 
 // ---- fp32 [M][ld] (K columns) -> h2 [M][Kp/32][2][32]; columns >= K of the last block are zero; mode: H2_PLAIN / H2_ACT / H2_WEIGHT
 __global__ __launch_bounds__(256) void split_h2_kernel(const float* __restrict__ src, int ld, int M, int K, int Kp,

@@ -670,20 +670,6 @@ __global__ __launch_bounds__(256) void hvp_conv_bwd_kernel(bool need_abar, const
     stage_chunk(st, i, m0, cnt, nb_idx, pg, cap, tvk, bp);
     const float shift = s_shift[g];
     const int mc = min(HCH, cnt - m0);
-#ifdef AIMNET_PROBE_HVP_PREFETCH  // measurement builds: the next neighbour's four rows requested ahead of this one's arithmetic
-    auto rows = [&](int m, float& aj, float& taj, float4& Sbj, float4& tSbj) __attribute__((always_inline)) {
-      const int j = st.j[m];
-      const size_t rj = row_of ? (size_t)min(63, max(0, row_of[j])) : (size_t)j;
-      const size_t trj = (size_t)k * N + j;
-      aj = a[rj * NF + f];
-      taj = ta ? ta[trj * NF + f] : 0.0f;
-      Sbj = reinterpret_cast<const float4*>(Sbar)[(size_t)j * NF + f];
-      tSbj = reinterpret_cast<const float4*>(tSbar)[trj * NF + f];
-    };
-    float aj_n = 0.f, taj_n = 0.f;
-    float4 Sbj_n = make_float4(0, 0, 0, 0), tSbj_n = Sbj_n;
-    if (mc > 0) rows(0, aj_n, taj_n, Sbj_n, tSbj_n);
-#endif
     // (requesting the NEXT neighbour's four rows before this one's arithmetic was measured slower: 3.0 -> 4.5 ms per sweep on
     // 10 080 atoms - ten more live registers across ~250 instructions of product-rule terms)
     for (int m = 0; m < mc; ++m) {
@@ -693,16 +679,10 @@ __global__ __launch_bounds__(256) void hvp_conv_bwd_kernel(bool need_abar, const
       basis_g2(bp.eta, shift, u.w, make_float3(fc.x, fc.y, fc.z), gs, dgs, d2gs);
       const float tgs = dgs * tu.w, tdgs = d2gs * tu.w;
       const size_t trj = (size_t)k * N + j;
-#ifdef AIMNET_PROBE_HVP_PREFETCH
-      const float aj = aj_n, taj = taj_n;
-      const float4 Sbj = Sbj_n, tSbj = tSbj_n;
-      if (m + 1 < mc) rows(m + 1, aj_n, taj_n, Sbj_n, tSbj_n);
-#else
       const size_t rj = row_of ? (size_t)min(63, max(0, row_of[j])) : (size_t)j;
       const float aj = a[rj * NF + f], taj = ta ? ta[trj * NF + f] : 0.0f;
       const float4 Sbj = reinterpret_cast<const float4*>(Sbar)[(size_t)j * NF + f];
       const float4 tSbj = reinterpret_cast<const float4*>(tSbar)[trj * NF + f];
-#endif
       pair_terms(aj, taj, ai, tai, Sbi, tSbi, Sbj, tSbj, u, tu, gs, dgs, tgs, tdgs, ab, tab);
       if (qthr) {
         const float qj = q[(size_t)qc * N + j], tqj = tq[((size_t)k * NQ + qc) * N + j];

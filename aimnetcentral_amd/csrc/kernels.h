@@ -65,9 +65,6 @@ int gemm_h2_set_attributes();
 enum { H2_PLAIN = 0, H2_ACT = 1, H2_WEIGHT = 2 };
 bool split_h2_host(const float* w, int rows, int K, unsigned short* out, int mode);  // false: an entry does not fit fp16's range
 int launch_split_h2(hipStream_t s, const float* src, int ld, int M, int K, unsigned short* dst, int ldd, int mode, int* ovf = nullptr);
-#ifdef AIMNET_BF3_TIMING
-int gemm_h2_read_stamps(unsigned long long* host1024);
-#endif
 
 // ---- gemm_chain.hip: one MLP (forward or backward sweep) as ONE launch.  A block owns a panel of 16 / 32 / 48 rows and the full width
 // of every layer; hidden activations stay in LDS (h2 form), weights stream L2 -> registers in a host-packed fragment order
@@ -119,10 +116,6 @@ struct HeadFusedArgs {
   int fmt = 1;  // 1: operands in the bf16x3 form (BF3_ALT weights), 2: in the fp16x2 form (H2_WEIGHT weights, H2_ACT activations)
 };
 int launch_head_fused(hipStream_t s, const HeadFusedArgs& a);
-#ifdef AIMNET_BF3_TIMING
-int gemm_bf3_read_stamps(unsigned long long* host1024);  // measurement build only (tests/tools/bf3_timing.sh)
-int gemm_bf3a_read_stamps(unsigned long long* host1024);
-#endif
 
 // ---- nlist.hip --------------------------------------------------------------------------------
 struct NlistBuffers {      // all device pointers, carved from the caller's workspace
@@ -171,9 +164,6 @@ bool prep_small_applies(int n_atoms, int n_mol, bool periodic);
 int launch_prep_small(hipStream_t s, const float* coord, const int* mol_idx, const int* numbers, int n_atoms, int n_mol,
                       const float* cell, int n_cell, const int pbc[3], const int* pbc_sys, float bin_width, int* status,
                       const int* slot_of_z, int* aslot, unsigned long long* present_part, NlistBuffers& b);
-#ifdef AIMNET_PREP_TIMING
-int prep_read_stamps(unsigned long long* host16);  // measurement build only (tests/tools/prep_timing.sh)
-#endif
 // non-periodic systems: give every molecule the cell grid of its bounding box (after launch_wrap), so that launch_nlist
 // takes the cell-list path instead of the O(n^2) per-molecule scan; worth it from ~10^3 atoms per molecule
 int launch_bbox(hipStream_t s, int n_mol, NlistBuffers& b);
@@ -256,19 +246,6 @@ int launch_conv_bwd_p0(hipStream_t s, bool stress, const float* T, int nslots, c
                        const int* nb_cnt, const float4* pg, int cap, BasisParams bp, float* fgrad, float* virial_atom,
                        int n_atoms, const int* order,
                        float4* pairbuf = nullptr);  // pairbuf: reverse-pair form (own moments only, G1 added to the pair buffer)
-// ---- conv_mfma.hip: the same three steps with the pair contractions on v_mfma_f32_4x4x1_16B_f32 (one wave per centre atom,
-// systems above SPLIT_MAX_ATOMS).  SbarT is the Sbar buffer in the lane-(g,c) plane layout that conv_bwd_mfma reads.
-// a_t: the feature table transposed to [g][a] (the MFMA operand layout), a: the natural [a][g] one
-int launch_conv_fwd_mfma(hipStream_t s, int nq, const float* a, const float* a_t, const int* row_of, const float* q, const int* nb_idx,
-                         const int* nb_cnt, const float4* pg, int cap, const float* agh_a, const float* agh_q, BasisParams bp,
-                         float* x, int ldx, float* Vsave, float* Vqsave, int n_atoms, const int* order);
-int launch_unconcat_t(hipStream_t s, int nq, const float* xbar, int ldx, const float* Vsave, const float* Vqsave,
-                      const float* agh_a, const float* agh_q, float* SbarT, float* Sqbar, int n_atoms);
-int launch_conv_bwd_mfma(hipStream_t s, int nq, bool need_abar, bool stress, const float* a_t, const int* row_of, const float* q,
-                         const float* SbarT, const float* Sqbar, const int* nb_idx, const int* nb_cnt, const float4* pg, int cap,
-                         BasisParams bp, const float* xbar, int ldx, const float* abar_in, float* abar_out, const float* qbar_in,
-                         float* qbar_out, float* fgrad, float* virial_atom, int n_atoms, const int* order);
-int launch_mfma4_probe(hipStream_t s, float* out);  // lane-layout probe of the 4x4x1 16-block MFMA (tests)
 int conv_split_max_default();  // 1024
 // stand-alone reference-op forms (conv_sv_2d_sp_wp.py:90-164)
 int launch_conv_sv_fwd(hipStream_t s, const float* a, const int* idx, const float* g, float* out, int B, int A, int G,
@@ -301,11 +278,9 @@ int launch_nse_fwd(hipStream_t s, const float* y, int ldy, int nq, const float* 
                    const float* charge, int n_mol, int n_atoms, int S, float* part, float* q_new, float* Fm, float* Dm,
                    // upd_a_new != NULL: a_new = a + delta_a (launch_update_a with these arguments) rides on the same launch
                    const float* upd_a = nullptr, const int* upd_row_of = nullptr, float* upd_a_new = nullptr,
-                   float* upd_a_t = nullptr,
                    const DdLink* dd = nullptr);  // != NULL: sums over owned atoms, all-reduced by dd->fn between the two launches
 int launch_charge_sum(hipStream_t s, const float* q2, int n_atoms, float* q_tot, float* q_spin);
-int launch_update_a(hipStream_t s, const float* a, const int* row_of, const float* y, int ldy, int nq, int n_atoms, float* a_new,
-                    float* a_t = nullptr);  // a_t: optional copy in the operand layout of the MFMA conv kernels
+int launch_update_a(hipStream_t s, const float* a, const int* row_of, const float* y, int ldy, int nq, int n_atoms, float* a_new);
 // d / zbar (may be NULL): also writes the backward seed zbar = w * d (d = GELU' of the layer below, ldh wide)
 int launch_head_last(hipStream_t s, const float* h, int ldh, const float* w, const float* b, int k, int n_atoms,
                      float* e_atom, const float* d, float* zbar);

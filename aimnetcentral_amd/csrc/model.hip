@@ -37,7 +37,6 @@ struct UpdateA {  // a_new = a + delta_a (+ the transposed copy): arguments of u
   const float* y;
   int ldy, col0, n_atoms;
   float* a_new;
-  float* a_t;
 };
 
 __device__ __forceinline__ void update_a_block(const UpdateA& u, size_t block) {
@@ -46,12 +45,7 @@ __device__ __forceinline__ void update_a_block(const UpdateA& u, size_t block) {
   const size_t i = e >> 8;
   const int k = (int)(e & 255);
   const size_t ri = u.row_of ? (size_t)min(63, max(0, u.row_of[i])) : i;
-  const float v = u.a[ri * 256 + k] + u.y[i * u.ldy + u.col0 + k];
-  u.a_new[e] = v;
-  if (u.a_t) {
-    const int aa = k >> 4, g = k & 15;
-    u.a_t[i * 256 + g * 16 + aa] = v;
-  }
+  u.a_new[e] = u.a[ri * 256 + k] + u.y[i * u.ldy + u.col0 + k];
 }
 
 // ---- NSE forward -------------------------------------------------------------------------------
@@ -164,10 +158,10 @@ __global__ __launch_bounds__(256) void nse_fwd_apply_kernel(const float* __restr
 
 int launch_nse_fwd(hipStream_t s, const float* y, int ldy, int nq, const float* q_prev, const int* mol_start,
                    const float* charge, int n_mol, int n_atoms, int S, float* part, float* q_new, float* Fm, float* Dm,
-                   const float* upd_a, const int* upd_row_of, float* upd_a_new, float* upd_a_t, const DdLink* dd) {
+                   const float* upd_a, const int* upd_row_of, float* upd_a_new, const DdLink* dd) {
   // upd_a_new != NULL: the feature update a_new = a + delta_a (launch_update_a) rides on the launch of channel 0
-  const UpdateA none{nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr};
-  const UpdateA upd{upd_a, upd_row_of, y, ldy, 2 * nq, n_atoms, upd_a_new, upd_a_t};
+  const UpdateA none{nullptr, nullptr, nullptr, 0, 0, 0, nullptr};
+  const UpdateA upd{upd_a, upd_row_of, y, ldy, 2 * nq, n_atoms, upd_a_new};
   const int n_upd = upd_a_new ? (int)(((size_t)n_atoms * 256 + 255) / 256) : 0;
   for (int ch = 0; ch < nq; ++ch) {  // channels are independent (ops.nse works on the trailing channel axis)
     const float* qp = q_prev ? q_prev + (size_t)ch * n_atoms : nullptr;
@@ -222,14 +216,11 @@ int launch_charge_sum(hipStream_t s, const float* q2, int n_atoms, float* q_tot,
 
 // row_of (may be NULL): feature row of atom i inside `a` - pass 0 adds delta_a to the embedding row afv[Z_i] directly, so
 // the initial features a^0 = afv[Z] (aimnet2.py:145-148) are never materialised
-// a_t (may be NULL): second copy of the new feature row in the operand layout of the MFMA conv kernels (conv_mfma.hip):
-// the transpose [g][a], feature (a, g) at float g * 16 + a
 __global__ void update_a_kernel(UpdateA u) { update_a_block(u, blockIdx.x); }
 
-int launch_update_a(hipStream_t s, const float* a, const int* row_of, const float* y, int ldy, int nq, int n_atoms, float* a_new,
-                    float* a_t) {
+int launch_update_a(hipStream_t s, const float* a, const int* row_of, const float* y, int ldy, int nq, int n_atoms, float* a_new) {
   const size_t n = (size_t)n_atoms * 256;
-  const UpdateA u{a, row_of, y, ldy, 2 * nq, n_atoms, a_new, a_t};
+  const UpdateA u{a, row_of, y, ldy, 2 * nq, n_atoms, a_new};
   hipLaunchKernelGGL(update_a_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, u);
   AIMNET_LAUNCH_CHECK();
   return 0;

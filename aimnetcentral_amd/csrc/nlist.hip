@@ -560,15 +560,6 @@ __device__ __forceinline__ unsigned wave_or_to_lane63(unsigned v) {  // OR over 
   v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true);  // row_bcast:31 into rows 2, 3
   return v;
 }
-#ifdef AIMNET_PREP_TIMING  // measurement build (tests/tools/prep_timing.sh): wall-clock stamps (100 MHz) of thread 0 per phase
-__device__ unsigned long long g_prep_stamps[16];
-#define PREP_STAMP(k) do { if (threadIdx.x == 0) g_prep_stamps[k] = wall_clock64(); } while (0)
-int prep_read_stamps(unsigned long long* host16) {
-  return hipMemcpyFromSymbol(host16, HIP_SYMBOL(g_prep_stamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
-#else
-#define PREP_STAMP(k)
-#endif
 
 __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
   extern __shared__ int s_prep[];
@@ -581,7 +572,6 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
   __shared__ unsigned long long s_mask[PREP_SMALL_MAX_ATOMS / 256];
   __shared__ int s_slot_of_z[64];
   __shared__ NlistSystem s_sys[PREP_SMALL_MAX_MOL];
-  PREP_STAMP(0);
   if (t < 8) a.status[t] = 0;
   if (t < PREP_SMALL_MAX_ATOMS / 256) s_mask[t] = 0ull;
   if (t < 64) s_slot_of_z[t] = a.slot_of_z ? a.slot_of_z[t] : 0;
@@ -590,7 +580,6 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
   if (a.cell)
     for (int s = t; s < n_mol; s += 1024) cell_setup_one(a.cell, a.n_cell, s, a.p0, a.p1, a.p2, a.pbc_sys, a.sys);
   __syncthreads();
-  PREP_STAMP(1);
   // ---- mol_start_kernel's three jobs
   int cur[PS_K];
   {
@@ -633,7 +622,6 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
     }
   }
   __syncthreads();
-  PREP_STAMP(2);
   if (a.slot_of_z)
     for (int g = t; g * 256 < n_atoms; g += 1024) a.present_part[g] = s_mask[g];
   if (a.cell == nullptr) {  // molecules: no cell, no bins - the coordinates as they are (launch_wrap's copy)
@@ -642,14 +630,12 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
   }
   bins_setup_block(a.sys, a.mol_start, n_mol, a.w);
   __syncthreads();
-  PREP_STAMP(3);
   {
     const int* src = (const int*)a.sys;
     int* dst = (int*)s_sys;
     for (int k = t; k < n_mol * (int)(sizeof(NlistSystem) / sizeof(int)); k += 1024) dst[k] = src[k];
   }
   __syncthreads();
-  PREP_STAMP(4);
   // ---- wrap + count (wrap_bin_count_kernel)
   int bin[PS_K], slot[PS_K];
   auto wrap4 = [&](auto K0) {
@@ -679,7 +665,6 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
   wrap4(std::integral_constant<int, 0>{});
   static_assert(PS_K == 4, "one batch of four atoms per thread");
   __syncthreads();
-  PREP_STAMP(5);
   // ---- exclusive scan over the bins in use, in place (scan_kernel)
   const int n = s_sys[n_mol - 1].bin_offset + s_sys[n_mol - 1].n_bins;
   {
@@ -704,7 +689,6 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
     if (t == 1023) s_bin[n] = part[1023];
   }
   __syncthreads();
-  PREP_STAMP(6);
   for (int k = t; k <= n; k += 1024) a.bin_start[k] = s_bin[k];
 #pragma unroll
   for (int k = 0; k < PS_K; ++k) {
@@ -712,7 +696,6 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
     if (i < n_atoms) s_tmp[s_bin[bin[k]] + slot[k]] = i;
   }
   __syncthreads();
-  PREP_STAMP(7);
   // ---- order every bin by atom id, emit the bin-ordered coordinate stream (bin_sort_kernel)
   auto sort4 = [&](auto K0) {
     constexpr int k0 = decltype(K0)::value;
@@ -746,7 +729,6 @@ __global__ __launch_bounds__(1024) void prep_small_kernel(PrepSmallArgs a) {
     }
   };
   sort4(std::integral_constant<int, 0>{});
-  PREP_STAMP(8);
 }
 
 // periodic: the systems' cell / bin descriptors live in LDS (PREP_SMALL_MAX_MOL of them); molecules need none

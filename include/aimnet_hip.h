@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define AIMNET_ABI_VERSION 11
+#define AIMNET_ABI_VERSION 12
 
 #define AIMNET_OK 0
 #define AIMNET_E_INVALID (-1)   /* bad argument / unsupported architecture */
@@ -320,7 +320,7 @@ int aimnet_engine_debug_mlp_sweep(aimnet_engine* engine, int pass, int backward,
                                   const int32_t* numbers, float* const* H, float* const* D, float* const* zb, int* which,
                                   void* hip_stream);
 
-/* Engine switches for A/B and parity runs (all have an AIMNET_* environment twin read at create time):
+/* Engine switches for A/B and parity runs (every live one has an AIMNET_* environment twin read at create time):
  *   "conv_xe"       1 (default): reverse-pair form of the conv backward for systems above the split threshold, 0: combined form
  *   "gemm_bf3"      1 (default): MLP GEMMs of batches above 256 rows with bf16x3-split operands on the bf16 matrix pipe
  *                   (csrc/gemm_bf3.hip: fp32 == three bf16 planes exactly, six products, fp32 accumulation), 2: for every batch
@@ -353,9 +353,12 @@ int aimnet_engine_debug_mlp_sweep(aimnet_engine* engine, int pass, int backward,
  *                   the rider block stores all eight words; 0: memset + atomics
  *   "sums_whole"    1 (default): up to 16 384 atoms, energy sums riding on the stress launch beside the force gather: one block per
  *                   cell / molecule sums everything, no finish launch; 0: sliced sums + finish launch
+ *   "nse_merged"    1 (default): systems of up to 1 024 atoms form the molecule sums of the NSE adjoint inside the kernel that uses
+ *                   them; 0: a partial-sum launch in front of it
+ *   "d3_cn_rides"   1 (default): the DFT-D3 coordination numbers are formed by the cell-grid list build that serves D3; 0: by a pass
+ *                   over the finished matrix
  *   "emb_bias"      1 (default): pass 0's first GEMM runs over the conv columns, the embedding block is a per-element bias table
- *   "conv_mfma"     bit 0: conv forward, bit 1: conv backward on the v_mfma_f32_4x4x1_16B_f32 kernels (csrc/conv_mfma.hip)
- *                   instead of the packed-FMA VALU kernels (default 0; systems above the split threshold only)
+ *   "conv_mfma"     retired (the 4x4x1 MFMA conv kernels were removed): reads 0, accepts only 0
  *   "split_max"     atoms up to which the 4-waves-per-atom "split" conv kernels are used (default 1024; per engine; < 0 = default)
  *   "p0_moments"    0: generic row-gather conv kernels in pass 0 instead of the element-moment forward / species-moment backward
  *   "dsf_np_walk" 0: non-periodic systems of >= 1 500 atoms per molecule evaluate DSF over a neighbour matrix (options.max_nb_lr) instead of
@@ -366,8 +369,6 @@ int aimnet_engine_set_option(aimnet_engine* e, const char* name, int value);
 /* current value of a switch (what a measurement should record instead of guessing from the environment) */
 int aimnet_engine_get_option(const aimnet_engine* e, const char* name, int* value);
 
-/* Test hook: lane layout of v_mfma_f32_4x4x1_16B_f32 as the conv kernels assume it.  out: f32[64][4][64] (device),
- * out[lb][r][l] = VGPR r, lane l of D = A x B with A[l] = l + 1 and B = one-hot(lb), C = 0. */
 /* aimnet_debug_pme_recip (csrc/pme.hip): the reciprocal-space part of AIMNET_COULOMB_PME alone, for ONE system - what
  * particle_mesh_ewald's mesh half computes (aimnet/modules/lr.py:752-775) - with unit prefactor: device xw [n][3] (any image of
  * the atoms), q [n], order [n] (device, a permutation: the sequence in which the charge assignment groups the atoms; NULL = as
@@ -378,7 +379,6 @@ int aimnet_debug_pme_recip(const float* xw, const float* q, const int* order, co
                            float accuracy,
                            int max_mesh, double* e_atom, float* qbar, float* fgrad, float* virial_atom, double* host_info,
                            void* hip_stream);
-int aimnet_debug_mfma4_probe(float* out, void* hip_stream);
 
 /* Stand-alone neighbour list with the nvalchemiops contract.  nbmat [n_atoms, max_nb] int32 is
  * filled with `fill_value` beyond each row's count; shifts [n_atoms, max_nb, 3] int32 may be NULL

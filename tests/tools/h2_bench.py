@@ -2,8 +2,7 @@
 """fp16x2-split GEMM (csrc/gemm_h2.hip) against the bf16x3-split one (gemm_bf3a.hip) on the MLP layer shapes (GPU box): time,
 error against fp64 (max, rms, MEAN = accumulation bias) of both and of the exact-fp32 MFMA kernel.
 
-Env: M, CFGS (tile ids, 0 = automatic), EPI (2 GELU / 3 chain rule / 0 / 1), OUT (1: split output), SHAPES=all|one, STAT=randn|pos|gelu,
-STAMPS=1 (timing build).
+Env: M, CFGS (tile ids, 0 = automatic), EPI (2 GELU / 3 chain rule / 0 / 1), OUT (1: split output), SHAPES=all|one, STAT=randn|pos|gelu.
 """
 import ctypes as C
 import os
@@ -130,14 +129,3 @@ for (N, K) in shapes:
             line += f" dD {(D2 - D3).abs().max().item():.1e} |"
     print(line, flush=True)
 print("sum over shapes (us): bf3a", round(tot3, 1), "h2", {c: round(v, 1) for c, v in tot2.items()})
-
-if os.environ.get("STAMPS") and hasattr(lib, "aimnet_debug_h2_stamps"):
-    buf = (C.c_ulonglong * 1024)()
-    lib.aimnet_debug_h2_stamps.argtypes = [C.c_void_p]
-    assert lib.aimnet_debug_h2_stamps(buf) == 0
-    t = np.array(buf[:], dtype=np.int64).reshape(2, 512)
-    t0 = t[0][0]
-    for g in range(2):
-        n = int((t[g] > 0).sum())
-        rel = t[g][:n] - t0
-        print(f"group {g}: {n} stamps; first {rel[0]} last {rel[-1]}; deltas:", " ".join(str(int(d)) for d in np.diff(rel)))

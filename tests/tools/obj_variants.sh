@@ -1,6 +1,6 @@
 #!/bin/bash
 # probe builds of ONE source file (one set of -D flags each) linked against the shipped objects -> gpurun_in/<stem>_<name>.so
-# usage (build container): bash tests/tools/obj_variants.sh conv deep:-DAIMNET_PROBE_FWD_DEEP "occ3:-DAIMNET_PROBE_FWD_OCC=3"
+# usage (build container): bash tests/tools/obj_variants.sh gemm_h2 noslp:-fno-slp-vectorize   (one library per name:flags pair)
 R=$(cd "$(dirname "$0")/../.." && pwd)
 C=$R/aimnetcentral_amd/csrc
 stem=$1; shift

@@ -9,7 +9,7 @@ mkdir -p $D /tmp/include && cp $R/aimnetcentral_amd/csrc/*.hip $R/aimnetcentral_
 cd $D && sed -i 's#../../include/aimnet_hip.h#/tmp/include/aimnet_hip.h#' *.hip *.h
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function $flags -c $stem.hip -o $stem.o
 objs=""
-for o in engine hvp gemm gemm_bf3 nlist conv conv_mfma model d3; do
+for o in engine hvp gemm gemm_bf3 nlist conv model d3; do
   if [ $o = $stem ]; then objs="$objs $D/$o.o"; else objs="$objs $R/aimnetcentral_amd/csrc/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs -o $D/libaimnet_hip.so
