@@ -112,6 +112,11 @@ struct aimnet_engine {
   // instead of one GEMM launch per layer (bitwise-equal results).  0 = the per-layer launches.  chain_fwd[p][e]: e = 1 with the
   // embedding block of pass 0 folded into the bias table; chain_bwd[p][m]: m = 1 when only the conv columns of xbar_0 are formed.
   int gemm_chain = 1;
+  // AIMNET_CHAIN_PREFETCH / set_option("chain_prefetch"): the blocks of a one-launch sweep that share an XCD request the sweep's whole
+  // packed weight stream into their L2 at kernel entry (gemm_chain_prefetch.h) instead of meeting every line as a miss in the
+  // weight ring, on grids with enough blocks per XCD for that to pay (pf_pays).  0 = no such requests, 2 = on every grid (tests).
+  // Bitwise-equal results whatever the value: the requests deliver nothing the kernel reads.
+  int chain_prefetch = 1;
   ChainPlan chain_fwd[AIMNET_MAX_PASS][2], chain_bwd[AIMNET_MAX_PASS][2];
   // AIMNET_D3_CN_RIDES / set_option("d3_cn_rides"): the DFT-D3 coordination numbers are formed by the cell-grid list build that serves
   // D3 (kernels.h, D3CnRider) instead of by a pass over the finished matrix

@@ -137,6 +137,7 @@ const OptionRow OPTIONS[] = {
     {"sums_whole", "AIMNET_SUMS_WHOLE", &aimnet_engine::sums_whole, OPT_BOOL, 0, 1},
     {"nse_merged", "AIMNET_NSE_MERGED", &aimnet_engine::nse_merged, OPT_BOOL, 0, 1},
     {"gemm_chain", "AIMNET_GEMM_CHAIN", &aimnet_engine::gemm_chain, OPT_BOOL, 0, 1},
+    {"chain_prefetch", "AIMNET_CHAIN_PREFETCH", &aimnet_engine::chain_prefetch, OPT_RANGE, 0, 2},
     {"d3_cn_rides", "AIMNET_D3_CN_RIDES", &aimnet_engine::d3_cn_rides, OPT_BOOL, 0, 1},
     {"dsf_np_walk", "AIMNET_DSF_NP_WALK", &aimnet_engine::dsf_np_walk, OPT_BOOL, 0, 1},
     {"split_max", "AIMNET_SPLIT_MAX", &aimnet_engine::split_max, OPT_RANGE, 0, INT32_MAX},
@@ -288,6 +289,7 @@ int mlp_sweep_fwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N,
     ca.x = reinterpret_cast<const unsigned short*>(x) + (emb0 ? (256 / 32) * 64 : 0);
     ca.ldx = 2 * Ls[0].k_in;
     ca.M = N;
+    ca.prefetch = e->chain_prefetch;
     for (int i = 0; i < cf.n_pass; ++i) {
       const int l = cf.pass[i].layer, ko = Ls[l].k_out;
       const bool last = l == nl - 1, linear = last && ar.last_linear[p];
@@ -343,6 +345,7 @@ int mlp_sweep_bwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N,
     ca.x = reinterpret_cast<const unsigned short*>(zcur);
     ca.ldx = 2 * ld;
     ca.M = N;
+    ca.prefetch = e->chain_prefetch;
     for (int i = 0; i < cb.n_pass; ++i) {
       const int l = cb.pass[i].layer;
       ChainPass& cp = ca.p[i];

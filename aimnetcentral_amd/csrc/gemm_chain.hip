@@ -17,6 +17,12 @@
 //   Cost model (config 3, 10 080 rows = 210 panels): a panel streams the chain's weights once (2.1 - 3.3 MB from L2 at <= 64 B/clk per
 //   CU) against ~12 000 matrix instructions (17 clk each on four SIMDs): both ~20 - 25 us per chain; the per-layer launches took
 //   62 - 84 us per chain (fill, epilogue store of 41 MB per layer, write-back, dispatch ramp - profiles/r5_gemm_h2.md).
+//   "From L2" holds for a launch repeated back to back.  In a step the weights were last read a whole step - ~2.5 GB through a 4 MiB
+//   L2 per XCD and the 256 MiB Infinity Cache - earlier: the first touch of every weight line on an XCD goes to HBM, and the ring meets
+//   those misses in 33 - 50 dependent round trips per wave, all ~26 blocks of the XCD on the same miss front: +45 us over the six
+//   sweeps, of +79 us for all operands cold (profiles/r7_chain_cold.md).  So at kernel entry the blocks of an XCD together request
+//   the whole stream once, every line in parallel (ChainArgs::prefetch, plan in gemm_chain_prefetch.h): the ring then finds the lines in
+//   L2 or on their way, and the weights' share of the cold gap goes away.
 #include <stdlib.h>
 #include <string.h>
 
@@ -29,100 +35,17 @@
 
 namespace aimnet {
 
-namespace {
-constexpr int CH_MAX_SM = 3;               // 16-row strips per panel: 3 (48 rows) when the batch fills the chip, fewer below
-#ifndef CH_RING8
-#define CH_RING8 4
-#endif
+using namespace chain;  // the instantiated shapes, their units and the prefetch plan (gemm_chain_prefetch.h)
 
+namespace {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// ---- chain shapes: k-steps and tile slots per wave of every pass (a pass = one layer, or one column range of a wide layer).
-// Static, so that the register ring, the accumulators and the loop trip counts are: the launcher matches the engine's layer sizes
-// against this list (chain_find_shape) and the engine falls back to the per-layer launches when nothing fits.
-template <int ID>
-struct Shape;
-#define AIMNET_CHAIN_SHAPE(ID, NW_, BWD_, NP_, NH_, ...)                  \
-  template <>                                                             \
-  struct Shape<ID> {                                                      \
-    static constexpr int NW = NW_; /* waves per block (two per SIMD, <= 256 registers each) */ \
-    static constexpr int R = CH_RING8; /* ring positions (items in flight per wave) */ \
-    static constexpr bool BWD = BWD_;                                     \
-    static constexpr int NP = NP_, NH = NH_; /* passes; passes that write the LDS operand (the others write global fp32) */ \
-    static constexpr int V[2][CHAIN_MAX_PASS] = {__VA_ARGS__};            \
-    static constexpr int nk(int i) { return V[0][i]; }                    \
-    static constexpr int nt(int i) { return V[1][i]; }                    \
-  };
-//                 id NW bwd NP NH   k-steps                 tile slots per wave
-AIMNET_CHAIN_SHAPE(0, 8, false, 3, 2, {14, 16, 12, 0, 0}, {4, 3, 3, 0, 0})      // pass 0 forward, embedding block folded into the bias table: 448 -> 512 -> 384 -> 288
-AIMNET_CHAIN_SHAPE(1, 8, false, 3, 2, {23, 16, 12, 0, 0}, {4, 3, 3, 0, 0})      // pass 1 forward: 736 -> 512 -> 384 -> 288
-AIMNET_CHAIN_SHAPE(2, 8, false, 4, 3, {23, 16, 12, 12, 0}, {4, 3, 3, 2, 0})     // pass 2 forward: 736 -> 512 -> 384 -> 384 -> 256
-AIMNET_CHAIN_SHAPE(3, 8, true, 3, 2, {9, 12, 16, 0, 0}, {3, 4, 4, 0, 0})        // pass 0 backward (conv columns only): 288 -> 384 -> 512 -> 448
-AIMNET_CHAIN_SHAPE(4, 8, true, 4, 2, {9, 12, 16, 16, 0}, {3, 4, 3, 3, 0})       // pass 1 backward: 288 -> 384 -> 512 -> 736 (two column passes)
-AIMNET_CHAIN_SHAPE(5, 8, true, 5, 3, {8, 12, 12, 16, 16}, {3, 3, 4, 3, 3})      // pass 2 backward: 256 -> 384 -> 384 -> 512 -> 736 (two column passes)
-#undef AIMNET_CHAIN_SHAPE
-constexpr int N_SHAPES = 6;
-constexpr int CH_MAX_NT = 4, CH_NTG = 2;  // tile slots per wave: of a pass, of a column group
-
-template <int J, int N, class F>
-__host__ __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (J < N) {
-    f(std::integral_constant<int, J>{});
-    static_for<J + 1, N>(f);
-  }
+// one 4-byte LDS-DMA request per lane (64 x 4 B land at lds_wave_base): a load that needs no register to land in
+__device__ __forceinline__ void glds4b(const void* g, void* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
-
-// A pass runs as one or two COLUMN GROUPS (group A = the first nt / 2 tile slots of every wave when nt >= 3, group B = the rest): each
-// group is a k-loop of its own over the whole operand, and the epilogue work of group A (GELU, GELU' stores / loads, output stores)
-// runs as side jobs between the matrix instructions of group B's k-loop.  A "unit" is one group of one pass; the weight stream and the
-// register ring run over the units in order.
-__host__ __device__ constexpr int chain_nta(int nt) { return chain_group_a(nt); }
-template <class S>
-constexpr int n_units() {
-  int n = 0;
-  for (int i = 0; i < S::NP; ++i) n += chain_nta(S::nt(i)) ? 2 : 1;
-  return n;
-}
-template <class S>
-constexpr int unit_pass(int u) {
-  for (int i = 0; i < S::NP; ++i) {
-    const int k = chain_nta(S::nt(i)) ? 2 : 1;
-    if (u < k) return i;
-    u -= k;
-  }
-  return S::NP;
-}
-template <class S>
-constexpr int unit_group(int u) {  // 0 = group A, 1 = group B (a pass without a group A has only group B)
-  for (int i = 0; i < S::NP; ++i) {
-    const int k = chain_nta(S::nt(i)) ? 2 : 1;
-    if (u < k) return k == 2 ? u : 1;
-    u -= k;
-  }
-  return 0;
-}
-template <class S>
-constexpr int unit_nt(int u) {
-  if (u >= n_units<S>()) return 1;
-  const int nt = S::nt(unit_pass<S>(u)), na = chain_nta(nt);
-  return unit_group<S>(u) == 0 ? na : nt - na;
-}
-template <class S>
-constexpr int unit_nk(int u) { return u >= n_units<S>() ? 0 : S::nk(unit_pass<S>(u)); }
-template <class S>
-constexpr int items_before(int u0, int u1) {  // items of the units u0 .. u1 - 1
-  int n = 0;
-  for (int q = u0; q < u1 && q < n_units<S>(); ++q) n += unit_nk<S>(q) * unit_nt<S>(q);
-  return n;
-}
-template <class S>
-constexpr int item_unit(int u, int qi) {  // unit that holds item qi counted from the first item of unit u (n_units: beyond the stream)
-  while (u < n_units<S>() && qi >= unit_nk<S>(u) * unit_nt<S>(u)) {
-    qi -= unit_nk<S>(u) * unit_nt<S>(u);
-    ++u;
-  }
-  return u;
-}
+static_assert(H2_STRIP == CHAIN_STRIP_BYTES, "gemm_chain_prefetch.h lays the LDS out in strips of H2_STRIP bytes");
 }  // namespace
 
 #ifdef CH_TIMING
@@ -176,6 +99,28 @@ __global__ __launch_bounds__(64 * S::NW, 1) void gemm_chain_kernel(ChainArgs a) 
     for (int q0 = 0; q0 < XC0 * PPK; q0 += NW) {
       const int q = q0 + wid;
       if (q < XC0 * PPK) glds16b(piece_src(q) + in_row, smem_c + (q / PPK) * CH_KB + ((q % PPK) >> 1) * H2_STRIP + (q & 1) * 1024);
+    }
+  }
+  // ---- weight prefetch (ChainArgs::prefetch).  In a step the chain's weights were last used one step - ~2.5 GB of traffic - ago:
+  // every first touch of a weight line on an XCD misses to HBM / the Infinity Cache, and the ring below reaches them in 33 - 50
+  // DEPENDENT round trips per wave, with all blocks of the XCD on the same miss front.  So the blocks of an XCD request the whole
+  // stream here, once, all lines in parallel: one 4-byte load per 128-byte line, dealt over the XCD's blocks and threads by
+  // pf_thread / pf_line (gemm_chain_prefetch.h: every offset lies inside its unit's packed buffer - tests/test_chain_prefetch_plan.py
+  // proves that on the CPU for the same functions).  The loads are LDS-DMA requests into a spare 256 bytes: they need no registers
+  // (the kernel has none to spare) whatever the count per thread (2 at 26 blocks per XCD, 51 for a lone block), and they are drained
+  // by the wait the panel's DMA requests need anyway, in front of the first product.  Nothing reads what they deliver.  The launcher
+  // asks for them only where they pay (pf_pays: few lines per thread); with a.prefetch == 0 the loop below runs zero times.
+  {
+    const PfThread t = pf_thread((int)gridDim.x, (int)blockIdx.x, tid, NTH);
+    const int n_lines = a.prefetch ? stream_lines<S>() : 0;
+    for (int g = t.first; g < n_lines; g += t.stride) {
+      const PfLine pl = pf_line<S>(g);
+      const unsigned char* src = nullptr;
+      static_for<0, NU>([&](auto u_c) __attribute__((always_inline)) {
+        constexpr int U = decltype(u_c)::value;
+        if (pl.unit == U) src = reinterpret_cast<const unsigned char*>(a.p[unit_pass<S>(U)].w[unit_group<S>(U)]);
+      });
+      if (src) glds4b(src + pl.offset, smem_c + chain_pf_lds_offset(CH_SM));
     }
   }
   u32x4 xr[XP];  // pieces of the chunk in flight (this wave's)
@@ -626,13 +571,15 @@ int launch_gemm_chain(hipStream_t stream, int shape, const ChainArgs& a) {
     if (ID != shape || SM != sm) return;
     static PerDeviceOnce once;
     if (once.first() && hipFuncSetAttribute((const void*)gemm_chain_kernel<Shape<ID>, SM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024) != hipSuccess) {
+                                            CHAIN_LDS_LIMIT) != hipSuccess) {
       set_last_error("gemm_chain: cannot raise the dynamic LDS limit");
       rc = -2;
       return;
     }
-    hipLaunchKernelGGL((gemm_chain_kernel<Shape<ID>, SM>), dim3(ceil_div(a.M, 16 * SM)), dim3(64 * Shape<ID>::NW), CHAIN_MAX_KB * SM * H2_STRIP,
-                       stream, a);
+    const int grid = ceil_div(a.M, 16 * SM);
+    ChainArgs b = a;  // prefetch: 0 never, 1 where the XCD's blocks share the stream thinly enough to gain (pf_pays), 2 always
+    b.prefetch = a.prefetch >= 2 || (a.prefetch == 1 && pf_pays<Shape<ID>>(grid));
+    hipLaunchKernelGGL((gemm_chain_kernel<Shape<ID>, SM>), dim3(grid), dim3(64 * Shape<ID>::NW), chain_lds_bytes(SM), stream, b);
   });
   if (rc) return rc;
   AIMNET_LAUNCH_CHECK();

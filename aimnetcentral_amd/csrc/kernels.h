@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "gemm_chain_prefetch.h"
+
 namespace aimnet {
 
 struct DdLink;  // domain decomposition of one system over ranks (below)
@@ -69,9 +71,7 @@ int launch_split_h2(hipStream_t s, const float* src, int ld, int M, int K, unsig
 // ---- gemm_chain.hip: one MLP (forward or backward sweep) as ONE launch.  A block owns a panel of 16 / 32 / 48 rows and the full width
 // of every layer; hidden activations stay in LDS (h2 form), weights stream L2 -> registers in a host-packed fragment order
 // (chain_pack_weights).  Same products and accumulation order as gemm_h2.hip: bitwise-equal results.
-constexpr int CHAIN_MAX_KB = 23, CHAIN_MAX_PASS = 5;
-// tile slots per wave of a pass' column group A (group B takes the rest; gemm_chain.hip)
-constexpr int chain_group_a(int nt) { return nt >= 3 ? 2 : 0; }
+// (CHAIN_MAX_KB, CHAIN_MAX_PASS, chain_group_a and the instantiated shapes: gemm_chain_prefetch.h)
 enum { CH_BIAS_F32 = 0, CH_GELU_F32 = 1, CH_GELU_H2G = 2 };  // epilogue of a forward chain's LAST pass (hidden passes: GELU -> LDS)
 struct ChainPass {          // a layer, or a column range of a wide layer
   const void* w[2];         // packed weight streams of the pass' column groups A and B (chain_pack_weights; w[0] NULL: no group A)
@@ -91,6 +91,8 @@ struct ChainPass {          // a layer, or a column range of a wide layer
 struct ChainArgs {
   const unsigned short* x;  // input rows, h2 form, at the first k-block pass 0 reads; ldx 16-bit elements per row
   int ldx, M;
+  int prefetch;             // the blocks of an XCD warm the whole weight stream into their L2 at entry (engine option "chain_prefetch": 0 never,
+                            // 1 on grids where it pays, 2 always; the kernel itself sees 0 / 1)
   ChainPass p[CHAIN_MAX_PASS];
 };
 // id of the instantiated shape that has these k-steps / tile slots per pass (-1: none - use the per-layer launches)

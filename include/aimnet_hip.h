@@ -338,6 +338,10 @@ int aimnet_engine_debug_mlp_sweep(aimnet_engine* engine, int pass, int backward,
  *                   match an instantiated shape is ONE launch (csrc/gemm_chain.hip: a block owns 16 / 32 / 48 rows and the full width
  *                   of every layer, hidden activations stay in LDS, weights stream L2 -> registers in a packed fragment order); 0: one
  *                   launch per layer (csrc/gemm_h2.hip).  Bitwise-identical results (tests/test_gpu_chain.py)
+ *                   and its companion "chain_prefetch" (AIMNET_CHAIN_PREFETCH), 1 (default): the blocks of such a launch that share an
+ *                   XCD request the sweep's whole weight stream into their L2 at kernel entry, on grids with enough blocks per XCD for
+ *                   that to pay (about 1 700 rows and up); 0: every weight line is first met as a miss of the weight ring; 2: the
+ *                   requests on every grid (tests).  Bitwise-identical results (tests/test_gpu_chain_prefetch.py)
  *   "head_fused"    1 (default): with pre-split activations the energy head 256 -> 128 -> 128 -> 1 runs forward and backward in one
  *                   launch (csrc/gemm_head.hip), 0: four GEMM launches + the last-layer rider
  *   "prep_fused"    1 (default): periodic batches of <= 4 096 atoms / 64 systems prepare their cell grid (status zeroing, molecule
