@@ -9,7 +9,7 @@ outputs.  Torch tensors are device buffers, nothing here is differentiated by au
 Deliberate deviations, all loud:
   * no CPU device and no torch fallback - constructing without a ROCm GPU raises HipLibraryError;
   * inputs carrying requires_grad raise (the reference keeps the autograd graph, :1458-1461);
-  * Ewald / PME, torch.compile and training mode raise NotImplementedError (SURVEY.md 8f "next" rows); open-shell NSE
+  * torch.compile and training mode raise NotImplementedError (SURVEY.md 8f "next" rows; Ewald and PME are supported); open-shell NSE
     (2-channel) models ARE supported (`mult` input, `spin_charges` output); external DFT-D3 needs the reference's table
     file (loader.load_dftd3_tables);
   * caller-supplied neighbour matrices (`nbmat`, `nbmat_lr`, `shifts`, `shifts_lr`) are handed to the engine as the reference
@@ -19,7 +19,8 @@ Deliberate deviations, all loud:
   * (per-system `pbc` flags of shape (B, 3) are supported: the engine takes them as a device array);
   * hessian=True and hessian_vector_product run the analytic tangent sweep of csrc/hvp.hip (forward-mode through the
     forward and backward sweep, all directions at once; `hvp_method`), not autograd double backward: exact second derivatives
-    at fp32 round-off (the external DFT-D3 block: a central difference of the D3 gradient alone, inside the same call).  The
+    at fp32 round-off (the external DFT-D3 block: a central difference of the D3 gradient alone, inside the same call), for
+    every Coulomb method but "pme" - the exact Ewald sum is carried by the sweep, the mesh takes differences of forces.  The
     finite-difference operator over the analytic forces (`_fd_hvp`, `hvp_method = "fd"`) is kept as the cross-check;
     create_graph=True raises (there is no autograd graph).
 """
@@ -674,7 +675,8 @@ class AIMNet2Calculator:
     # round-off (2e-6 relative to the fp64 specification, 6e-5 eV/A^2 from the reference's Hessian on config 4);
     # with an external DFT-D3 term its block is a central difference of the D3 gradient alone inside the same call (smooth, ~1 % of
     # the curvature: ~1e-6 eV/A^2);  "fd": the central-difference operator over the analytic forces (`_fd_hvp`), the independent
-    # cross-check.
+    # cross-check.  The sweep carries "simple", DSF and the exact Ewald sum ("ewald": real space on a list, structure factors and
+    # their tangents in double); "pme" always takes the finite-difference operator.
     hvp_method = "analytic"
 
     def _hvp(self, d: dict[str, Any], dirs, eps: float | None = None):
@@ -683,9 +685,9 @@ class AIMNet2Calculator:
 
         if self.hvp_method not in ("analytic", "fd"):
             raise ValueError(f"hvp_method must be 'analytic' or 'fd', got {self.hvp_method!r}")
-        if self.hvp_method == "fd" or self._coulomb_method in ("ewald", "pme"):
-            # Ewald: differences of the analytic forces (what the reference does for its PME block, lr.py:903-926); the tangent
-            # sweep of csrc/hvp.hip covers the pair-wise Coulomb methods only
+        if self.hvp_method == "fd" or self._coulomb_method == "pme":
+            # particle-mesh Ewald: differences of the analytic forces (what the reference does for its PME block, lr.py:903-926);
+            # the tangent sweep of csrc/hvp.hip carries the pair-wise Coulomb methods and the exact Ewald sum, not the mesh
             return self._fd_hvp(d, dirs, eps)
         cell = d.get("cell")
         method = self._coulomb_method
@@ -697,7 +699,8 @@ class AIMNet2Calculator:
         n = d["coord"].shape[0]
         res = self.engine.hvp(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
                               self._engine_charge(d["charge"], d.get("mult")), dirs, cell=cell, pbc=pbc3, coulomb=method or "none",
-                              dsf_rc=self._dsf_rc, dsf_alpha=self._dsf_alpha, dftd3=self._dftd3_options())
+                              dsf_rc=self._dsf_rc, dsf_alpha=self._dsf_alpha, dftd3=self._dftd3_options(),
+                              **({"ewald_accuracy": self._ewald_accuracy} if method == "ewald" else {}))
         return res["hv"]
 
     def _eval_hessian(self, data, *, forces: bool, stress: bool, validate_species: bool) -> dict[str, Any]:

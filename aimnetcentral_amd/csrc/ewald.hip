@@ -258,6 +258,190 @@ __global__ __launch_bounds__(256) void ewald_atom_kernel(const double* __restric
   }
 }
 
+// ---- tangents for the Hessian-vector sweep (hvp.hip) ---------------------------------------------------------------------------
+// A direction carries t_r (the caller's vector) and t_q (the tangent of the final charges; two channels: their sum).  With
+// t_theta_i = k . t_r_i:   t_S(k) = sum_j (t_q_j + i q_j t_theta_j) e^{i theta_j},   t_P = A Re t_S,   t_Q = A Im t_S   (the cell is
+// fixed: A and k carry no tangent; neither does the background, sum_j t_q_j = 0 under the NSE normalisation).
+constexpr int EWALD_TD = 4;  // directions whose sums one block holds in registers: the sin / cos of an (atom, k) pair is formed once
+
+__device__ __forceinline__ void total_charge_tangent(const float* __restrict__ tq, int nq, int n_atoms, int k, int i, double& tqi) {
+  tqi = (double)tq[((size_t)k * nq) * n_atoms + i];
+  if (nq == 2) tqi += (double)tq[((size_t)k * nq + 1) * n_atoms + i];
+}
+
+// entry r of a system's k box: its integer triplet, k, k^2 and whether it lies inside the slice and the half-space sphere.  One
+// definition for the accumulation and the write phase of ewald_tsfac_kernel (k^2 by explicit fma: both decide alike).  The primal
+// kernel keeps its own copy untouched; the per-atom pass trusts the primal's vfac, so an entry the two should ever judge differently at
+// exactly |k| = kc either carries a zero tangent or is skipped - never read unwritten.
+__device__ __forceinline__ bool ewald_k_entry(const EwaldSystem& E, int r, int& n1, int& n2, int& n3, double kv[3], double& k2) {
+  const long box = (long)(E.nmax[0] + 1) * E.n2w * E.n3w;
+  n1 = r / (E.n2w * E.n3w);
+  const int rem = r - n1 * (E.n2w * E.n3w);
+  n2 = rem / E.n3w - E.nmax[1];
+  n3 = rem % E.n3w - E.nmax[2];
+  const bool half = n1 > 0 || (n1 == 0 && (n2 > 0 || (n2 == 0 && n3 > 0)));
+  k2 = 0.0;
+  for (int c = 0; c < 3; ++c) {
+    kv[c] = fma((double)n3, E.b[6 + c], fma((double)n2, E.b[3 + c], (double)n1 * E.b[c]));
+    k2 = fma(kv[c], kv[c], k2);
+  }
+  return r < box && r < E.n_box && half && k2 <= (double)E.kc2;
+}
+
+// block = (EWALD_KB entries of one system's k box - the mapping of ewald_sfac_kernel -, EWALD_TD directions); the sums of a
+// direction are the same expressions in the same order whichever slot of whichever block holds it (explicit fma: no contraction
+// left to the compiler), so a direction's numbers do not depend on how the directions were grouped.
+__global__ __launch_bounds__(256) void ewald_tsfac_kernel(const double* __restrict__ frac, const float* __restrict__ q,
+                                                         const float* __restrict__ tq, int nq, const float* __restrict__ tv,
+                                                         int n_atoms, int n_dir, const int* __restrict__ mol_start, int n_mol,
+                                                         const EwaldSystem* __restrict__ es, int max_k, double2* __restrict__ tk) {
+  const int e0 = blockIdx.x * EWALD_KB, d0 = blockIdx.y * EWALD_TD;
+  if (e0 >= es[n_mol - 1].k_offset + es[n_mol - 1].n_box) return;
+  int s = 0;
+  while (s + 1 < n_mol && e0 >= es[s].k_offset + es[s].n_box) ++s;  // (block-uniform, as in ewald_sfac_kernel)
+  const EwaldSystem& E = es[s];
+  const int nd = min(EWALD_TD, n_dir - d0);
+  int n1[EWALD_KB], n2[EWALD_KB], n3[EWALD_KB];
+  bool ok[EWALD_KB];
+  double kv[EWALD_KB][3];
+#pragma unroll
+  for (int j = 0; j < EWALD_KB; ++j) {
+    double k2;
+    ok[j] = ewald_k_entry(E, e0 + j - E.k_offset, n1[j], n2[j], n3[j], kv[j], k2);
+  }
+  double re[EWALD_KB][EWALD_TD], im[EWALD_KB][EWALD_TD];
+#pragma unroll
+  for (int j = 0; j < EWALD_KB; ++j)
+#pragma unroll
+    for (int d = 0; d < EWALD_TD; ++d) re[j][d] = im[j][d] = 0.0;
+  for (int i = mol_start[s] + (int)threadIdx.x; i < mol_start[s + 1]; i += 256) {
+    const double f0 = frac[(size_t)i * 3], f1 = frac[(size_t)i * 3 + 1], f2 = frac[(size_t)i * 3 + 2];
+    const double qi = q[i];
+    double tr[EWALD_TD][3], tqi[EWALD_TD];
+#pragma unroll
+    for (int d = 0; d < EWALD_TD; ++d) {
+      tr[d][0] = tr[d][1] = tr[d][2] = tqi[d] = 0.0;
+      if (d < nd) {  // (block-uniform)
+        const float* t = tv + ((size_t)(d0 + d) * n_atoms + i) * 3;
+        tr[d][0] = t[0]; tr[d][1] = t[1]; tr[d][2] = t[2];
+        total_charge_tangent(tq, nq, n_atoms, d0 + d, i, tqi[d]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < EWALD_KB; ++j) {
+      if (!ok[j]) continue;  // (block-uniform)
+      float snf, csf;
+      phase_sincos(f0, f1, f2, n1[j], n2[j], n3[j], snf, csf);
+      const double sn = snf, cs = csf;
+#pragma unroll
+      for (int d = 0; d < EWALD_TD; ++d) {
+        if (d >= nd) continue;
+        const double tth = fma(kv[j][2], tr[d][2], fma(kv[j][1], tr[d][1], kv[j][0] * tr[d][0]));
+        const double qt = qi * tth;
+        re[j][d] = fma(-qt, sn, fma(tqi[d], cs, re[j][d]));
+        im[j][d] = fma(qt, cs, fma(tqi[d], sn, im[j][d]));
+      }
+    }
+  }
+  __shared__ double sh[4][2 * EWALD_KB * EWALD_TD];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < EWALD_KB; ++j)
+#pragma unroll
+    for (int d = 0; d < EWALD_TD; ++d) {
+      const double a = wave_sum(re[j][d]), b = wave_sum(im[j][d]);
+      if (lane == 0) {
+        sh[w][2 * (j * EWALD_TD + d)] = a;
+        sh[w][2 * (j * EWALD_TD + d) + 1] = b;
+      }
+    }
+  __syncthreads();
+  if (threadIdx.x < EWALD_KB * EWALD_TD) {
+    const int j = threadIdx.x / EWALD_TD, d = threadIdx.x % EWALD_TD;
+    const int r = e0 + j - E.k_offset;
+    if (r >= E.n_box || d >= nd) return;
+    // (the unrolled per-j registers are indexed dynamically here: recompute this entry's constants)
+    int m1, m2, m3;
+    double kx[3], kq;
+    double2 T = make_double2(0.0, 0.0);
+    if (ewald_k_entry(E, r, m1, m2, m3, kx, kq)) {
+      const int o = 2 * (j * EWALD_TD + d);
+      const double sre = sh[0][o] + sh[1][o] + sh[2][o] + sh[3][o];
+      const double sim = sh[0][o + 1] + sh[1][o + 1] + sh[2][o + 1] + sh[3][o + 1];
+      const double A = E.pref * exp(-kq * (double)E.inv4a2) / kq;
+      T = make_double2(A * sre, A * sim);
+    }
+    tk[(size_t)(d0 + d) * max_k + e0 + j] = T;
+  }
+}
+
+// one wave per (atom, direction), lanes over the system's k entries.  With t = cs P + sn Q and d = cs Q - sn P (phi_i = sum t,
+// g_i = sum d k):   t_phi_i = sum_k (cs t_P + sn t_Q + t_theta_i d),   t_g_i = sum_k k (cs t_Q - sn t_P - t_theta_i t).
+// ADDS onto the seeds of the sweep in the convention of hvp.hip's coul_store (E_rec = factor sum_i q_i phi_i):
+//   qbar_i += 2 factor (phi_i + phi_bg)   t_qbar_i += 2 factor t_phi_i     (every charge channel: the term sees their sum)
+//   xbar_i += 2 factor q_i g_i            t_xbar_i += 2 factor (t_q_i g_i + q_i t_g_i)
+// An entry is valid by its own vfac (0 outside the half-space sphere): S = 0 with t_S != 0 is a valid entry.
+__global__ __launch_bounds__(256) void ewald_tatom_kernel(const double* __restrict__ frac, const float* __restrict__ q,
+                                                         const float* __restrict__ tq, int nq, const float* __restrict__ tv,
+                                                         const int* __restrict__ mol_idx, int n_atoms,
+                                                         const EwaldSystem* __restrict__ es, const EwaldK* __restrict__ kk, int max_k,
+                                                         const double2* __restrict__ tk, float factor, float* __restrict__ qbar,
+                                                         float* __restrict__ tqbar, float* __restrict__ xbar,
+                                                         float* __restrict__ txbar) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), k = blockIdx.y;
+  if (i >= n_atoms) return;
+  const int lane = threadIdx.x & 63;
+  const EwaldSystem& E = es[mol_idx[i]];
+  const double f0 = frac[(size_t)i * 3], f1 = frac[(size_t)i * 3 + 1], f2 = frac[(size_t)i * 3 + 2];
+  const float* t = tv + ((size_t)k * n_atoms + i) * 3;
+  const double tr0 = t[0], tr1 = t[1], tr2 = t[2];
+  const double2* __restrict__ tkk = tk + (size_t)k * max_k;
+  double phi = 0.0, tphi = 0.0, g[3] = {0.0, 0.0, 0.0}, tg[3] = {0.0, 0.0, 0.0};
+  const int e1 = E.k_offset + E.n_box;
+  for (int e = E.k_offset + lane; e < e1; e += 64) {
+    const EwaldK K = kk[e];
+    if (K.vfac == 0.0f) continue;
+    const double2 T = tkk[e];
+    double kx[3];
+    for (int c = 0; c < 3; ++c)  // (the expression of ewald_k_entry: the same k bit for bit)
+      kx[c] = fma((double)K.n3, E.b[6 + c], fma((double)K.n2, E.b[3 + c], (double)K.n1 * E.b[c]));
+    float snf, csf;
+    phase_sincos(f0, f1, f2, K.n1, K.n2, K.n3, snf, csf);
+    const double sn = snf, cs = csf;
+    const double tth = fma(kx[2], tr2, fma(kx[1], tr1, kx[0] * tr0));
+    const double tt = fma(sn, K.Q, cs * K.P), d = fma(-sn, K.P, cs * K.Q);
+    const double tp = fma(tth, d, fma(sn, T.y, cs * T.x));
+    const double td = fma(-tth, tt, fma(-sn, T.x, cs * T.y));
+    phi += tt;
+    tphi += tp;
+    for (int c = 0; c < 3; ++c) {
+      g[c] = fma(d, kx[c], g[c]);
+      tg[c] = fma(td, kx[c], tg[c]);
+    }
+  }
+  phi = wave_sum(phi);
+  tphi = wave_sum(tphi);
+  for (int c = 0; c < 3; ++c) {
+    g[c] = wave_sum(g[c]);
+    tg[c] = wave_sum(tg[c]);
+  }
+  if (lane != 0) return;
+  const double qi = q[i], f2x = 2.0 * (double)factor;
+  double tqi;
+  total_charge_tangent(tq, nq, n_atoms, k, i, tqi);
+  const float qv = (float)(f2x * (phi + (double)E.phi_bg)), tqv = (float)(f2x * tphi);
+  for (int ch = 0; ch < nq; ++ch) {
+    const size_t pe = (size_t)ch * n_atoms + i, te = ((size_t)k * nq + ch) * n_atoms + i;
+    if (k == 0) qbar[pe] += qv;
+    tqbar[te] += tqv;
+  }
+  for (int c = 0; c < 3; ++c) {
+    const size_t pe = (size_t)i * 3 + c, te = ((size_t)k * n_atoms + i) * 3 + c;
+    if (k == 0) xbar[pe] += (float)(f2x * qi * g[c]);
+    txbar[te] += (float)(f2x * fma(tqi, g[c], qi * tg[c]));
+  }
+}
+
 }  // namespace
 
 int launch_ewald_setup(hipStream_t s, const float* cell, int n_cell, const int* mol_start, const int* mol_idx, const float* xw,
@@ -274,10 +458,27 @@ int launch_ewald_frac(hipStream_t s, const float* xw, const int* mol_idx, int n_
   return 0;
 }
 
-int launch_ewald_recip(hipStream_t s, bool grad, bool stress, const float* q, const int* mol_idx, const int* mol_start, int n_atoms,
-                       int n_mol, const EwaldBuffers& b, float factor, double* ecoul, float* qbar, float* fgrad, float* virial_atom) {
+int launch_ewald_sfac(hipStream_t s, const float* q, const int* mol_start, int n_mol, const EwaldBuffers& b) {
   hipLaunchKernelGGL(ewald_sfac_kernel, dim3(ceil_div(b.max_k, EWALD_KB)), dim3(256), 0, s, b.frac, q, mol_start, n_mol, b.sys, b.k);
   AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ewald_tangent(hipStream_t s, const float* q, const float* tq, int nq, const float* tv, const int* mol_idx,
+                         const int* mol_start, int n_atoms, int n_mol, int n_dir, const EwaldBuffers& b, double* tk, float factor,
+                         float* qbar, float* tqbar, float* xbar, float* txbar) {
+  hipLaunchKernelGGL(ewald_tsfac_kernel, dim3(ceil_div(b.max_k, EWALD_KB), ceil_div(n_dir, EWALD_TD)), dim3(256), 0, s, b.frac, q, tq,
+                     nq, tv, n_atoms, n_dir, mol_start, n_mol, b.sys, b.max_k, (double2*)tk);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ewald_tatom_kernel, dim3(ceil_div(n_atoms, 4), n_dir), dim3(256), 0, s, b.frac, q, tq, nq, tv, mol_idx, n_atoms,
+                     b.sys, b.k, b.max_k, (const double2*)tk, factor, qbar, tqbar, xbar, txbar);
+  AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ewald_recip(hipStream_t s, bool grad, bool stress, const float* q, const int* mol_idx, const int* mol_start, int n_atoms,
+                       int n_mol, const EwaldBuffers& b, float factor, double* ecoul, float* qbar, float* fgrad, float* virial_atom) {
+  if (const int rc = launch_ewald_sfac(s, q, mol_start, n_mol, b)) return rc;
   const dim3 grid(ceil_div(n_atoms, 4)), block(256);
   if (grad && stress)
     hipLaunchKernelGGL((ewald_atom_kernel<true, true>), grid, block, 0, s, b.frac, q, mol_idx, n_atoms, b.sys, b.k, factor, ecoul, qbar,

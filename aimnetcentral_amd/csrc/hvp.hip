@@ -15,12 +15,14 @@
 // centre's own moments) and applies the product rule.  A block with k == 0 also WRITES the primal outputs, so one sweep
 // produces the forces as well; no kernel reads a primal array that the same launch writes.  All pair kernels keep the
 // centre-major gather form of the force kernels (conv.hip): every ordered pair is visited from its centre, both halves of
-// its adjoint are evaluated there, nothing is scattered, no atomics - results are bitwise reproducible.
+// its adjoint are evaluated there, nothing is scattered, no atomics - results are bitwise reproducible.  (The one atomic of the
+// sweep is on a FLAG: the Ewald mode of hvp_coulomb_lr_kernel ORs a constant into status[6], the idiom of nlist.hip / model.hip.)
 //
 // The second-order pieces: GELU''(z) = phi(z) (2 - z^2) in the backward of every hidden layer (hvp_act_bwd), the second
 // derivative of the radial basis gs''(d) (the cosine envelope's jumps at rc: the Hessian is discontinuous where a pair crosses
 // the cutoff, as the reference's is), the tangent of the unit vector t_u = (t_r - u (u . t_r)) / d, second derivatives of the
-// Coulomb pair weights, and the tangent of the NSE charge normalisation and of its adjoint.
+// Coulomb pair weights, the tangent structure factors of Ewald summation (ewald.hip: launch_ewald_tangent), and the tangent of
+// the NSE charge normalisation and of its adjoint.
 //
 // These kernels are written for clarity and exactness, not for the roofline: a Hessian of a 40-atom molecule is 120
 // directions x 40 atoms = 4 800 tangent rows (the GEMMs see a 4 800-row batch), everything else is far below a millisecond.
@@ -438,8 +440,18 @@ __global__ __launch_bounds__(256) void hvp_coulomb_sr_kernel(bool enabled, const
   coul_store(A, i, k, N, nq, lane, -cp.factor, 0.0f, qi, tqi, false, qbar, tqbar, xbar, txbar);
 }
 
-// "simple" (every other atom of the molecule, w = 1/d; lr.py:311-331) or DSF over the long-range list (lr.py:559-615)
-template <bool DSF>
+__global__ void hvp_qtot_kernel(const float* __restrict__ q, int N, float* __restrict__ qtot) {  // two channels: alpha + beta
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) qtot[i] = q[i] + q[(size_t)N + i];
+}
+
+// "simple" (every other atom of the molecule, w = 1/d; lr.py:311-331), DSF over the long-range list (lr.py:559-615), or the
+// real-space term of Ewald summation over that list (lr.py:617-720): w = erfc(alpha d) / d inside the SYSTEM's own (alpha, rc)
+// (cp.ewald) - the DSF expressions without the shift and the force shift - and the self term of -alpha / sqrt(pi) q^2; the
+// reciprocal-space block follows in ewald.hip.  status6 (read by the Ewald mode alone): takes STATUS_EWALD_LIST_SHORT when the
+// list cutoff cp.dsf_rc is below rc.
+enum class LrMode { Simple, Dsf, Ewald };
+template <LrMode MODE>
 __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __restrict__ q, const float* __restrict__ tq, int nq,
                                                             const float* __restrict__ xw, const int* __restrict__ mol_idx,
                                                             const int* __restrict__ mol_start, const float* __restrict__ cell,
@@ -447,7 +459,10 @@ __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __rest
                                                             const int* __restrict__ nb_shift, const int* __restrict__ nb_cnt,
                                                             int cap, const float* __restrict__ tv, CoulombParams cp, int N,
                                                             float* __restrict__ qbar, float* __restrict__ tqbar,
-                                                            float* __restrict__ xbar, float* __restrict__ txbar) {
+                                                            float* __restrict__ xbar, float* __restrict__ txbar,
+                                                            int* __restrict__ status6) {
+  constexpr bool DSF = MODE != LrMode::Simple;  // a pair term over the long-range list
+  constexpr bool EW = MODE == LrMode::Ewald;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), k = blockIdx.y;
   if (i >= N) return;
   const int lane = threadIdx.x & 63;
@@ -455,12 +470,13 @@ __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __rest
   float qi, tqi;
   q_total(q, tq, nq, N, k, i, qi, tqi);
   const float xi = xw[3 * i], yi = xw[3 * i + 1], zi = xw[3 * i + 2];
-  const float al = cp.dsf_alpha, Rc = cp.dsf_rc;
-  const float cpi = 2.0f * al * 0.56418958354775629f;
-  const float erfc_rc = erfcf(al * Rc);
-  const float sv = erfc_rc / Rc;
-  const float slope = erfc_rc / (Rc * Rc) + cpi * expf(-al * al * Rc * Rc) / Rc;
   const int mi = mol_idx[i];
+  const float al = EW ? cp.ewald[mi].alpha : cp.dsf_alpha, Rc = EW ? cp.ewald[mi].rc : cp.dsf_rc;
+  const float cpi = 2.0f * al * 0.56418958354775629f;
+  const float erfc_rc = EW ? 0.0f : erfcf(al * Rc);  // (Ewald: neither shift nor force shift)
+  const float sv = EW ? 0.0f : erfc_rc / Rc;
+  const float slope = EW ? 0.0f : erfc_rc / (Rc * Rc) + cpi * expf(-al * al * Rc * Rc) / Rc;
+  if (EW && k == 0 && lane == 0 && i == mol_start[mi] && !(cp.dsf_rc >= Rc)) atomicOr(status6, STATUS_EWALD_LIST_SHORT);
   const float* c = (DSF && cell) ? cell + (n_cell == 1 ? 0 : (size_t)mi * 9) : nullptr;
   const int lo = DSF ? 0 : mol_start[mi], hi = DSF ? nb_cnt[i] : mol_start[mi + 1];
   CoulAcc A;
@@ -868,6 +884,9 @@ struct HvpWs {
   float *h[2], *g[2];    // activations between GEMMs / adjoint ping-pong (stacked: tangent rows follow the N primal rows)
   float *Sbar, *tSbar, *Sqbar, *tSqbar, *abar, *tabar, *qbar[2], *tqbar[2], *xbar, *txbar;
   float* wlast;
+  EwaldBuffers ew;  // Ewald summation: per-system parameters, fractional coordinates, k entries (ewald.hip)
+  double* ew_tk;    // [K][max_k][2] tangent structure factors (t_P, t_Q)
+  float* ew_qtot;   // [N] alpha + beta of a two-channel model
   // external DFT-D3 block (4 K displaced copies as one batch)
   int *d3_idx, *d3_shift, *d3_cnt, *aslot, *d3c_idx, *d3c_shift, *d3c_cnt, *d3c_mol, *d3c_aslot;
   unsigned long long* present_part;
@@ -948,6 +967,16 @@ void hvp_layout(const aimnet_engine* e, int N, int n_mol, int K, const aimnet_ev
   W.xbar = c.take<float>(n * 3);
   W.txbar = c.take<float>(kn * 3);
   W.wlast = c.take<float>((size_t)mw);
+  {  // Ewald summation: the buffers of aimnet_engine_eval + the tangent structure factors of every direction
+    const bool ew = opt->coulomb == AIMNET_COULOMB_EWALD;
+    W.ew = EwaldBuffers{};
+    W.ew.max_k = ew ? std::max(EWALD_KB, opt->ewald_max_k / EWALD_KB * EWALD_KB) : 0;
+    W.ew.sys = c.take<EwaldSystem>(ew ? (size_t)n_mol : 0);
+    W.ew.frac = c.take<double>(ew ? n * 3 : 0);
+    W.ew.k = c.take<EwaldK>(ew ? (size_t)W.ew.max_k : 0);
+    W.ew_tk = c.take<double>(ew ? 2 * (size_t)K * W.ew.max_k : 0);
+    W.ew_qtot = c.take<float>(ew && nq == 2 ? n : 0);
+  }
   if (opt->dftd3 != 0) {
     const int cap_d3 = std::max(1, opt->max_nb_d3);
     const size_t cn = 4 * kn;
@@ -1088,10 +1117,26 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
     set_last_error("hvp: DSF Coulomb needs max_nb_lr > 0 (the tangent sweep runs on the neighbour list, also for periodic input)");
     return AIMNET_E_INVALID;
   }
-  if (coulomb == AIMNET_COULOMB_EWALD || coulomb == AIMNET_COULOMB_PME) {
-    set_last_error("hvp: the analytic tangent sweep does not cover Ewald summation (use DSF, or differences of forces as the reference "
-                   "does for its PME block, lr.py:903-926)");
+  if (coulomb == AIMNET_COULOMB_PME) {
+    set_last_error("hvp: the analytic tangent sweep does not cover particle-mesh Ewald (use the exact Ewald sum or DSF, or differences "
+                   "of forces as the reference does for its PME block, lr.py:903-926)");
     return AIMNET_E_INVALID;
+  }
+  const bool ewald = coulomb == AIMNET_COULOMB_EWALD;
+  if (ewald) {
+    if (!pbc || in->pbc_sys || !(in->pbc[0] && in->pbc[1] && in->pbc[2])) {
+      set_last_error("hvp: Ewald summation needs a cell that is periodic along all three axes (lr.py:655-657)");
+      return AIMNET_E_INVALID;
+    }
+    if (!(opt->ewald_accuracy > 0.0f && opt->ewald_accuracy < 1.0f) || opt->ewald_max_k < EWALD_KB) {
+      set_last_error("hvp: Ewald summation needs 0 < ewald_accuracy < 1 and ewald_max_k >= %d", EWALD_KB);
+      return AIMNET_E_INVALID;
+    }
+    if (opt->max_nb_lr <= 0 || !(opt->dsf_rc > 0.0f)) {
+      set_last_error("hvp: Ewald summation runs its real-space term on the neighbour list: dsf_rc (the list cutoff, at least every "
+                     "system's real-space cutoff) and max_nb_lr must be > 0");
+      return AIMNET_E_INVALID;
+    }
   }
   if (coulomb == AIMNET_COULOMB_SIMPLE && pbc) {
     set_last_error("hvp: 'simple' Coulomb is undefined for periodic input");
@@ -1128,9 +1173,12 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
   if (!pbc && (long)N >= 1500L * n_mol) RC(launch_bbox(s, n_mol, W.nl));
   RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, ar.rc, ar.rc, cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
                   status + 0, status + 2, W.pg));
-  if (coulomb == AIMNET_COULOMB_DSF)
+  if (coulomb == AIMNET_COULOMB_DSF || ewald)
     RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->dsf_rc, -1.0f, cap_lr, N, 0, W.nl, W.lr_idx, W.lr_shift,
                     W.lr_cnt, status + 1, status + 3));
+  if (ewald)  // per-system (alpha, rc, kc) and k boxes from the cell, fractional coordinates in double; status[7] = k entries needed
+    RC(launch_ewald_setup(s, in->cell, n_cell, W.nl.mol_start, mol_c, W.nl.xw, in->charge, nq, N, n_mol, opt->ewald_accuracy, W.ew,
+                          status + 7));
 
   // ---- forward + tangent ----
   const dim3 gik(N, K), gmk(n_mol, K), gwk(ceil_div(N, 4), K), b256(256);
@@ -1179,13 +1227,30 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
                      vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar);
   AIMNET_LAUNCH_CHECK();
   if (coulomb == AIMNET_COULOMB_SIMPLE) {
-    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<false>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start, in->cell,
-                       n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar);
+    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<LrMode::Simple>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start,
+                       in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar,
+                       W.txbar, status + 6);
     AIMNET_LAUNCH_CHECK();
   } else if (coulomb == AIMNET_COULOMB_DSF) {
-    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<true>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start, in->cell,
-                       n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar);
+    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<LrMode::Dsf>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start,
+                       in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar,
+                       W.txbar, status + 6);
     AIMNET_LAUNCH_CHECK();
+  } else if (ewald) {  // real space over the list, then reciprocal space + background (ewald.hip): both add onto the seeds
+    cp.ewald = W.ew.sys;
+    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<LrMode::Ewald>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start,
+                       in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar,
+                       W.txbar, status + 6);
+    AIMNET_LAUNCH_CHECK();
+    const float* q_tot = q_fin;
+    if (nq == 2) {  // the structure factors see alpha + beta
+      hipLaunchKernelGGL(hvp_qtot_kernel, grid1((size_t)N), b256, 0, s, q_fin, N, W.ew_qtot);
+      AIMNET_LAUNCH_CHECK();
+      q_tot = W.ew_qtot;
+    }
+    RC(launch_ewald_sfac(s, q_tot, W.nl.mol_start, n_mol, W.ew));
+    RC(launch_ewald_tangent(s, q_tot, tq_fin, nq, vectors, mol_c, W.nl.mol_start, N, n_mol, K, W.ew, W.ew_tk, cp.factor, W.qbar[qb],
+                            W.tqbar[qb], W.xbar, W.txbar));
   }
 
   // ---- backward + tangent ----

@@ -343,6 +343,16 @@ int launch_pme_recip(hipStream_t s, bool grad, bool stress, const float* xw, con
 // reciprocal-space sum + neutralising background, ACCUMULATED onto the per-atom energies / adjoints the pair kernels have stored
 int launch_ewald_recip(hipStream_t s, bool grad, bool stress, const float* q, const int* mol_idx, const int* mol_start, int n_atoms,
                        int n_mol, const EwaldBuffers& b, float factor, double* ecoul, float* qbar, float* fgrad, float* virial_atom);
+// the first half of launch_ewald_recip alone: the structure factors (b.k) of the total charges q [n_atoms]
+int launch_ewald_sfac(hipStream_t s, const float* q, const int* mol_start, int n_mol, const EwaldBuffers& b);
+// the tangent sweep's reciprocal-space block (hvp.hip), after launch_ewald_sfac: tangent structure factors of n_dir directions into
+// tk [n_dir][b.max_k][2] doubles, then the per-atom pass that ADDS the primal seeds (direction 0's blocks) and their tangents onto
+// qbar [nq][n_atoms] / tqbar [n_dir][nq][n_atoms] / xbar [n_atoms][3] / txbar [n_dir][n_atoms][3].  q [n_atoms]: total charges;
+// tq [n_dir][nq][n_atoms]: tangents of the charge channels; tv [n_dir][n_atoms][3]: the directions.  No atomics.
+// (hvp.hip raises STATUS_EWALD_LIST_SHORT with an atomicOr of that constant: a flag, not a result.)
+int launch_ewald_tangent(hipStream_t s, const float* q, const float* tq, int nq, const float* tv, const int* mol_idx,
+                         const int* mol_start, int n_atoms, int n_mol, int n_dir, const EwaldBuffers& b, double* tk, float factor,
+                         float* qbar, float* tqbar, float* xbar, float* txbar);
 
 struct CoulombParams {
   float factor;      // 1/2 Hartree Bohr
@@ -422,6 +432,9 @@ struct PairForceRider {
 // bit of status[6] that the kernels writing the energies and forces raise when a value is not finite: an MLP activation beyond
 // fp16's range with the fp16x2-split GEMM operands (gemm_h2_common.h) surfaces there (or a genuine blow-up of the input geometry)
 constexpr int STATUS_NONFINITE = 32;
+// bit of status[6] the tangent sweep raises with Ewald summation when options.dsf_rc (there: the cutoff of the real-space list) is
+// below a system's own real-space cutoff: the list misses pairs the sum needs
+constexpr int STATUS_EWALD_LIST_SHORT = 64;
 // the molecule energy sums as riders of the stress launches (partial sums beside the virial sums, the slice sums beside the stress
 // finish): they are only needed at the end, and two launch boundaries go.  part: its own [n_mol][S] partial sums.
 struct EnergyRider {

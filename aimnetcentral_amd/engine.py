@@ -55,6 +55,7 @@ class NeighborOverflowError(RuntimeError):
     exception of this name, neighbors.py:127-130)."""
 
 
+EWALD_LIST_SHORT_FLAG = 64  # status[6] bit 6 (csrc/kernels.h STATUS_EWALD_LIST_SHORT): aimnet_engine_hvp, list cutoff below an Ewald r_c
 NONFINITE_FLAG = 32  # status[6] bit 5 (csrc/kernels.h STATUS_NONFINITE): a non-finite energy or force was written - not an input flag
 
 
@@ -72,8 +73,11 @@ def describe_input_flags(flags: int, n_mol: int | None = None) -> str:
     if flags & 16:
         what.append("a caller-supplied neighbour matrix is not a full symmetric matrix (an entry i -> j without exactly one mirror j -> i, "
                     "or a duplicated entry)")
-    if flags & ~31:
-        what.append(f"unknown flag bits {flags & ~31:#x}")
+    if flags & EWALD_LIST_SHORT_FLAG:
+        what.append("Ewald summation in the tangent sweep: options.dsf_rc (the cutoff of the real-space list) is below a system's "
+                    "real-space cutoff")
+    if flags & ~(31 | EWALD_LIST_SHORT_FLAG):
+        what.append(f"unknown flag bits {flags & ~(31 | EWALD_LIST_SHORT_FLAG):#x}")
     return " and ".join(what) if what else "no flags"
 
 
@@ -145,6 +149,7 @@ class HipEngine:
         self._max_nb_lr: dict[float, int] = {}
         self.last_status: np.ndarray | None = None
         self.has_dftd3 = False
+        self._ewald_nb_lr = 0     # row capacity of the real-space list of Ewald summation in `hvp` (0: sized from r_c at first use)
         self._ewald_max_k = 8192  # capacity of the Ewald k arrays (entries; grows to what status[7] reports)
         self._pme_max_mesh = 8192  # capacity of one system's PME mesh (points; every system of a batch gets a slice: grows to what status[7] reports)
         self._status7_pme = False  # what status[7] of the pending deferred evaluations counts (mesh points or k entries)
@@ -553,11 +558,13 @@ class HipEngine:
 
     def hvp(self, coord, numbers, mol_idx, charge, vectors, cell=None, pbc=(True, True, True), coulomb: str = "simple",
             dsf_rc: float = 15.0, dsf_alpha: float = 0.2, want_forces: bool = False,
-            dftd3: dict[str, float] | None = None) -> dict[str, Any]:
+            dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6) -> dict[str, Any]:
         """Analytic Hessian-vector products (csrc/hvp.hip, aimnet_engine_hvp): vectors [K, N, 3] -> hv [K, N, 3] on the device
         (+ the forces of the same sweep with `want_forces`).  Inputs as `eval`; with `dftd3` the dispersion block is added as a
         central difference of the D3 gradient inside the same call.  The K directions are processed in as many sweeps as the
-        workspace budget asks for."""
+        workspace budget asks for.  `coulomb`: "none", "simple", "dsf" or "ewald" (the exact structure-factor sum at
+        `ewald_accuracy`, periodic cells only; `dsf_rc` / `dsf_alpha` are not read with it); "pme" raises - its tangent is not
+        carried, AIMNet2Calculator takes differences of forces there."""
         import torch
 
         dev = self.device
@@ -592,10 +599,26 @@ class HipEngine:
             n_cell = 1 if cell.ndim == 2 else cell.shape[0]
         if not isinstance(pbc, (tuple, list)):
             pbc = tuple(bool(x) for x in torch.as_tensor(pbc).reshape(-1).tolist())[:3]
-        if coulomb in ("ewald", "pme"):
-            raise ValueError("HipEngine.hvp: the analytic tangent sweep covers the pair-wise Coulomb methods only; with Ewald summation use "
-                             "differences of the forces (AIMNet2Calculator does: hvp_method 'fd' is taken automatically)")
-        method = {"none": _lib.COULOMB_NONE, "simple": _lib.COULOMB_SIMPLE, "dsf": _lib.COULOMB_DSF}[coulomb]
+        if coulomb == "pme":
+            raise ValueError("HipEngine.hvp: the analytic tangent sweep does not carry particle-mesh Ewald; use coulomb='ewald' (the exact "
+                             "sum) or differences of the forces (AIMNet2Calculator does: hvp_method 'fd' is taken automatically)")
+        method = {"none": _lib.COULOMB_NONE, "simple": _lib.COULOMB_SIMPLE, "dsf": _lib.COULOMB_DSF,
+                  "ewald": _lib.COULOMB_EWALD}[coulomb]
+        lr_rc = float(dsf_rc)  # cutoff of the long-range list
+        if method == _lib.COULOMB_EWALD:
+            if cell is None:
+                raise ValueError("HipEngine.hvp: coulomb='ewald' needs a periodic cell")
+            if not (0.0 < float(ewald_accuracy) < 1.0):
+                raise ValueError("HipEngine.hvp: ewald_accuracy must lie in (0, 1)")
+            # the real-space term runs on a list: its cutoff is the largest r_c of the batch (ewald_setup_kernel's formula on the
+            # host; the device verifies it, status[6] bit 6), widened by the rounding between the two
+            counts = torch.bincount(mol_idx.long().clamp(0, n_mol - 1), minlength=n_mol).cpu().numpy()
+            vols = np.abs(np.linalg.det(cell.detach().cpu().numpy().astype(np.float64).reshape(-1, 3, 3)))
+            vols = np.broadcast_to(vols, (n_mol,)) if vols.shape[0] == 1 else vols
+            if vols.shape[0] != n_mol:
+                raise ValueError("HipEngine.hvp: cell must be [3, 3] or [n_mol, 3, 3]")
+            eta = (vols * vols / np.maximum(counts, 1)) ** (1.0 / 6.0) / math.sqrt(2.0 * math.pi)
+            lr_rc = float(np.max(math.sqrt(-2.0 * math.log(float(ewald_accuracy))) * eta)) * (1.0 + 1e-5)
         hv = torch.empty_like(vectors)
         f_out = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_forces else None
         status = torch.empty(8, dtype=torch.int32, device=dev)
@@ -612,9 +635,16 @@ class HipEngine:
         while k0 < K:
             opt = _lib.EvalOptions()
             opt.coulomb = method
-            opt.dsf_rc, opt.dsf_alpha = float(dsf_rc), float(dsf_alpha)
+            opt.dsf_rc, opt.dsf_alpha = lr_rc, float(dsf_alpha)
             opt.max_nb = self.max_nb
-            opt.max_nb_lr = self._lr_capacity(float(dsf_rc)) if method == _lib.COULOMB_DSF else 0
+            opt.max_nb_lr = self._lr_capacity(lr_rc) if method == _lib.COULOMB_DSF else 0
+            if method == _lib.COULOMB_EWALD:
+                # r_c changes with every cell, atom count and accuracy: ONE capacity of its own (as _ewald_max_k for the k entries),
+                # not a key per cutoff in _max_nb_lr; it only grows (an overflow repeats the sweep)
+                self._ewald_nb_lr = max(self._ewald_nb_lr, _round16(int(0.2 * 4.0 / 3.0 * math.pi * lr_rc**3)))
+                opt.max_nb_lr = self._ewald_nb_lr
+                opt.ewald_accuracy = float(ewald_accuracy)
+                opt.ewald_max_k = self._ewald_max_k
             if dftd3 is not None:
                 if not self.has_dftd3:
                     raise RuntimeError("dftd3 requested but no DFT-D3 tables were uploaded (HipEngine.set_dftd3_tables)")
@@ -641,11 +671,16 @@ class HipEngine:
             self.last_status = st
             if st[6]:
                 raise ValueError("HipEngine.hvp: invalid input: " + describe_input_flags(int(st[6]), n_mol))
-            if st[2] or st[3] or st[5]:  # neighbour-row overflow: grow and repeat this sweep
+            k_short = method == _lib.COULOMB_EWALD and st[7] > opt.ewald_max_k
+            if k_short:  # the Ewald k boxes did not fit: their size is now known - grow as `eval` does and repeat this sweep
+                self._ewald_max_k = (int(st[7]) * 5 // 4 + 7) // 8 * 8
+            if st[2] or st[3] or st[5] or k_short:  # neighbour-row overflow: grow and repeat this sweep
                 if st[2]:
                     self.max_nb = _round16(int(max(self.max_nb * 1.5, st[0])))
-                if st[3]:
-                    self._max_nb_lr[float(dsf_rc)] = _round16(int(max(opt.max_nb_lr * 1.5, st[1])))
+                if st[3] and method == _lib.COULOMB_EWALD:
+                    self._ewald_nb_lr = _round16(int(max(opt.max_nb_lr * 1.5, st[1])))
+                elif st[3]:
+                    self._max_nb_lr[lr_rc] = _round16(int(max(opt.max_nb_lr * 1.5, st[1])))
                 if st[5]:
                     self._max_nb_lr[float(dftd3.get("cutoff", 15.0))] = _round16(int(max(opt.max_nb_d3 * 1.5, st[4])))
                 continue

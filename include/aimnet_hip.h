@@ -133,12 +133,14 @@ typedef struct aimnet_inputs {
 typedef struct aimnet_eval_options {
   uint32_t flags;          /* AIMNET_FORCES | AIMNET_STRESS */
   int32_t coulomb;         /* AIMNET_COULOMB_* */
-  float dsf_rc;            /* 15.0 */
+  float dsf_rc;            /* 15.0.  aimnet_engine_hvp with AIMNET_COULOMB_EWALD: the cutoff of the real-space LIST, at least every
+                            * system's own real-space cutoff (status[6] bit 6 otherwise); dsf_alpha is not read then */
   float dsf_alpha;         /* 0.2 */
   int32_t max_nb;          /* row capacity of the short-range (rc) neighbour matrix.  A row of EXACTLY max_nb entries is complete:
                             * the overflow flag (status[2]; [3], [5] for the other lists) is raised only when a row needs MORE
                             * than its capacity (status[0] > max_nb) - such rows were truncated and the results are invalid */
-  int32_t max_nb_lr;       /* row capacity of the DSF neighbour matrix (0 if unused) */
+  int32_t max_nb_lr;       /* row capacity of the DSF neighbour matrix (0 if unused); aimnet_engine_hvp with AIMNET_COULOMB_EWALD: of
+                            * the real-space list */
   /* external DFT-D3(BJ) two-body dispersion, DFTD3 of aimnet/modules/lr.py:1335-1820 as wired by
    * calculator.py:234-247,999-1032; needs aimnet_engine_set_dftd3 first.  0 = off. */
   int32_t dftd3;
@@ -179,6 +181,8 @@ typedef struct aimnet_outputs {
                                 With the fp16x2-split GEMM operands ("gemm_h2", the default above 256 rows) that is how an MLP
                                 activation or adjoint beyond fp16's range (|x| >= 65504) surfaces: set_option("gemm_h2", 0) and
                                 repeat the evaluation (the bf16x3 operands have fp32's range); still raised, the input is the cause.
+                                Bit 6 (64), aimnet_engine_hvp with AIMNET_COULOMB_EWALD only: options.dsf_rc, there the cutoff of the
+                                real-space list, is below a system's real-space cutoff - the list misses pairs, hv is meaningless.
                               7 Ewald: k-array entries the batch needs (compare with options.ewald_max_k); PME: mesh points the
                                 largest system needs (compare with options.pme_max_mesh); 0 for other methods */
   float* spin_charges; /* [n_atoms] alpha - beta of an NSE model (aimnet2.py:103), or NULL; must be NULL for 1-channel models */
@@ -243,8 +247,13 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
 /* Analytic Hessian-vector products H v = d/d eps [dE/dx (x + eps v)] for n_vec directions at once (csrc/hvp.hip: forward-mode
  * tangent sweep through the forward and the backward sweep of the model; specification oracle/aimnet2_analytic.py::evaluate_hvp).
  * `in` / `opt` as for aimnet_engine_eval (opt->flags is ignored; DSF - periodic or not - runs on the neighbour list and needs
- * max_nb_lr > 0; with opt->dftd3 the dispersion block is a 4-point central difference of the D3 gradient alone, h = 4e-3 A along
- * the normalised direction, all 4 n_vec displaced copies in one batch - as the reference treats its PME block, calculator.py:1777-1781).
+ * max_nb_lr > 0.  AIMNET_COULOMB_EWALD is carried analytically: the real-space term on a list of cutoff opt->dsf_rc (>= every
+ * system's r_c = sqrt(-2 ln accuracy) (V^2 / N)^(1/6) / sqrt(2 pi); checked on the device, status[6] bit 6) with row capacity
+ * max_nb_lr, the structure factors and their tangents in double (16 bytes of workspace per k entry and direction); status[7]
+ * reports the k entries needed as aimnet_engine_eval does; the cell must be periodic along all three axes.  AIMNET_COULOMB_PME is
+ * rejected: the mesh has no tangent here, take differences of forces.  With opt->dftd3 the dispersion block is a 4-point central
+ * difference of the D3 gradient alone, h = 4e-3 A along the normalised direction, all 4 n_vec displaced copies in one batch - as
+ * the reference treats its PME block, calculator.py:1777-1781).
  * vectors [n_vec, n_atoms, 3] and hv [n_vec, n_atoms, 3] are device fp32; forces [n_atoms, 3] (may be NULL) receives the forces
  * of the same sweep; status [8] as aimnet_outputs.status (a raised overflow flag invalidates hv: grow the rows and call again).
  * Any number of molecules / cells (the reference restricts itself to one structure; the host keeps that contract).  Memory:
