@@ -249,14 +249,11 @@ int mlp_gemm3(const aimnet_engine* e, hipStream_t s, int fmt, int epi, bool out3
               const int* brow, int ldbias) {
   const int ldw = fwd ? L.k_in : L.k_out;
   const int alt = ((k0 / 32) & 1) ? 2 : 1;
-  if (fmt == 2) {
-    const unsigned short* w2 = (fwd ? L.w2a : L.wt2a) + (size_t)n0 * 2 * ldw + (size_t)(k0 / 32) * 64;
-    return launch_gemm_h2_cfg(s, 0, epi, out3, A3 + (size_t)(k0 / 32) * 64, lda3, w2, 2 * ldw, M, N, K, bias, C, C3, ldc3, D, ldc, brow,
-                              ldbias, alt);
-  }
-  const unsigned short* w3 = (fwd ? L.w3a : L.wt3a) + (size_t)n0 * 3 * ldw + (size_t)(k0 / 32) * 96;
-  return launch_gemm_bf3a_cfg(s, 0, epi, out3, A3 + (size_t)(k0 / 32) * 96, lda3, w3, 3 * ldw, M, N, K, bias, C, C3, ldc3, D, ldc, brow,
-                              ldbias, alt);
+  const int pm = split_planes(fmt);
+  const size_t koff = (size_t)(k0 / 32) * 32 * pm;  // first k-block of the launch, in 16-bit elements of a split row
+  const unsigned short* w = fmt == SPLIT_H2 ? (fwd ? L.w2a : L.wt2a) : (fwd ? L.w3a : L.wt3a);
+  return launch_gemm_split_cfg(s, fmt, 0, epi, out3, SplitArgs{A3 + koff, lda3, w + (size_t)n0 * pm * ldw + koff, pm * ldw, M, N, K, bias, C,
+                                                              C3, ldc3, D, ldc, brow, ldbias, alt});
 }
 // the one-launch energy head of gemm_head.hip covers the shipped architecture (256 -> 128 -> 128 -> 1)
 bool head_fusable(const aimnet_engine* e) {
@@ -270,21 +267,21 @@ bool presplit_active(const aimnet_engine* e, int N) {
   return e->gemm_presplit != 0 && bf3 && !e->keep_intermediates;
 }
 int split_format(const aimnet_engine* e, int n_rows) {
-  if (!presplit_active(e, n_rows)) return 0;
-  return (e->gemm_h2 && e->h2_fits) ? 2 : 1;
+  if (!presplit_active(e, n_rows)) return SPLIT_NONE;
+  return (e->gemm_h2 && e->h2_fits) ? SPLIT_H2 : SPLIT_BF3;
 }
 
-// ---- one MLP sweep on split activations (fmt 1 = bf16x3, 2 = fp16x2): ONE launch of gemm_chain.hip where the pass has a plan
+// ---- one MLP sweep on split activations (sfmt SPLIT_BF3 = bf16x3, SPLIT_H2 = fp16x2): ONE launch of gemm_chain.hip where the pass has a plan
 // (fp16x2 form only), else one launch per layer.  x: the input rows in split form; H[l]: layer outputs (hidden ones in split form -
 // the chain does not write them -, the last in fp32, or in split form for the fused energy head: `split_last`); D[l]: GELU' (fp32).
 int mlp_sweep_fwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N, const int* numbers, const float* x, float* const* H,
                   float* const* D, bool split_last, bool chain) {
   const aimnet_arch& ar = e->arch;
   const std::vector<Layer>& Ls = e->mlp[p];
-  const int nl = (int)Ls.size(), pm = sfmt == 2 ? 2 : 3;
+  const int nl = (int)Ls.size(), pm = split_planes(sfmt);
   const bool emb0 = p == 0 && e->emb_bias && e->emb_bias0;
   const ChainPlan& cf = e->chain_fwd[p][emb0 ? 1 : 0];
-  if (sfmt == 2 && chain && cf.shape >= 0) {
+  if (sfmt == SPLIT_H2 && chain && cf.shape >= 0) {
     ChainArgs ca{};
     ca.x = reinterpret_cast<const unsigned short*>(x) + (emb0 ? (256 / 32) * 64 : 0);
     ca.ldx = 2 * Ls[0].k_in;
@@ -337,10 +334,10 @@ int mlp_sweep_fwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N,
 int mlp_sweep_bwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N, bool conv_only, float*& zcur, float*& znext,
                   float* const* D, bool chain) {
   const std::vector<Layer>& Ls = e->mlp[p];
-  const int nl = (int)Ls.size(), pm = sfmt == 2 ? 2 : 3;
+  const int nl = (int)Ls.size(), pm = split_planes(sfmt);
   int ld = Ls[nl - 1].k_out;
   const ChainPlan& cb = e->chain_bwd[p][(p == 0 && conv_only) ? 1 : 0];
-  if (sfmt == 2 && chain && cb.shape >= 0 && !(conv_only && p != 0)) {
+  if (sfmt == SPLIT_H2 && chain && cb.shape >= 0 && !(conv_only && p != 0)) {
     ChainArgs ca{};
     ca.x = reinterpret_cast<const unsigned short*>(zcur);
     ca.ldx = 2 * ld;
@@ -630,7 +627,6 @@ int aimnet_engine_create(const aimnet_arch* arch, const aimnet_weights* w, int d
     if ((rc = dev_upload(e, soz, (size_t)64, &e->slot_of_z))) goto fail;
     if ((rc = dev_upload(e, zos, (size_t)ns, &e->z_of_slot))) goto fail;
     apply_env_options(e);
-    (void)gemm_h2_set_attributes();  // AIMNET_H2_TILE / AIMNET_H2_DEEP (gemm_h2.hip)
   }
   if ((rc = dev_upload(e, w->agh_a, (size_t)16 * 16 * 12, &e->agh_a))) goto fail;
   if ((rc = dev_upload(e, w->agh_q, (size_t)e->nq * 16 * 12, &e->agh_q))) goto fail;
@@ -712,7 +708,7 @@ int aimnet_engine_create(const aimnet_arch* arch, const aimnet_weights* w, int d
   for (int g = 0; g < 16; ++g) e->bp.shifts[g] = arch->shifts[g];
   if ((rc = gemm_set_attributes())) goto fail;
   if ((rc = gemm_bf3_set_attributes())) goto fail;
-  if ((rc = gemm_bf3a_set_attributes())) goto fail;
+  if ((rc = gemm_split_set_attributes())) goto fail;  // AIMNET_BF3A_TILE / AIMNET_H2_TILE / AIMNET_H2_DEEP (gemm_h2.hip)
   if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) {
@@ -1102,9 +1098,9 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
   const int* order = (!ext && W.nl.binned && e->spatial_order) ? W.nl.sorted : nullptr;
   // a^0 = afv[Z] is never materialised: pass 0 gathers the embedding rows directly (conv_fwd / conv_bwd row_of, update_a)
   const bool p0m = e->p0_moments && (opt->flags & (AIMNET_FORCES | AIMNET_STRESS));
-  const int sfmt = split_format(e, N);  // GEMM activations in split form: 1 bf16x3 (gemm_bf3a.hip), 2 fp16x2 (gemm_h2.hip)
-  const bool ps = sfmt != 0;
-  const int pm = sfmt == 2 ? 2 : 3;  // 16-bit elements per fp32 value of a split row
+  const int sfmt = split_format(e, N);  // GEMM activations in split form: SPLIT_BF3 bf16x3 (gemm_bf3a.hip), SPLIT_H2 fp16x2 (gemm_h2.hip)
+  const bool ps = sfmt != SPLIT_NONE;
+  const int pm = split_planes(sfmt);  // 16-bit elements per fp32 value of a split row
   const bool hfused = ps && head_fusable(e);  // energy head forward + backward in one launch (gemm_head.hip)
   // reverse-pair map through per-atom hash tables of the rows (once per neighbour list)
   // (its only reader is launch_pair_force, the last kernel of the backward.  On one stream the two small kernels ride on later
@@ -1266,7 +1262,7 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
       ha.aim3 = reinterpret_cast<const unsigned short*>(hin);
       ha.lda3 = pm * ld_in;
       ha.fmt = sfmt;
-      if (sfmt == 2) { ha.w1 = e->head[0].w2a; ha.w2 = e->head[1].w2a; ha.w2t = e->head[1].wt2a; ha.w1t = e->head[0].wt2a; }
+      if (sfmt == SPLIT_H2) { ha.w1 = e->head[0].w2a; ha.w2 = e->head[1].w2a; ha.w2t = e->head[1].wt2a; ha.w1t = e->head[0].wt2a; }
       else { ha.w1 = e->head[0].w3a; ha.w2 = e->head[1].w3a; ha.w2t = e->head[1].wt3a; ha.w1t = e->head[0].wt3a; }
       ha.b1 = e->head[0].b; ha.b2 = e->head[1].b; ha.w3 = e->head_w_last; ha.b3 = e->head_b_last;
       ha.dlast = grad ? W.D[np - 1][nlp - 1] : nullptr;
@@ -1359,7 +1355,7 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
       ld = L.k_in;
     }
     if (ps) {  // (interim: the head still runs on fp32 operands; its adjoint is split for the MLP backward)
-      if (sfmt == 2) RC(launch_split_h2(s, zcur, ld, N, ld, reinterpret_cast<unsigned short*>(znext), 2 * ld, H2_ACT));
+      if (sfmt == SPLIT_H2) RC(launch_split_h2(s, zcur, ld, N, ld, reinterpret_cast<unsigned short*>(znext), 2 * ld, H2_ACT));
       else RC(launch_split_bf3(s, zcur, ld, N, ld, reinterpret_cast<unsigned short*>(znext), 3 * ld));
       std::swap(zcur, znext);
     }
@@ -1534,18 +1530,24 @@ int aimnet_debug_gemm_bf3(int cfg, int epi, const float* A, int lda, const void*
                              nullptr, 0, kneg < 0 ? BF3_NO_NEG : kneg);
 }
 
-int aimnet_debug_gemm_bf3a(int cfg, int epi, int out3, const void* A3, int lda3, const void* Bt3, int ldb, int M, int N, int K,
-                           const float* bias, float* C, void* C3, int ldc3, float* D, int ldc, int alt, void* hip_stream) {
+// the two split formats' debug entry points: one launcher (gemm_split.h)
+static int debug_gemm_split(int fmt, int cfg, int epi, int out, const void* A3, int lda3, const void* Bt, int ldb, int M, int N, int K,
+                            const float* bias, float* C, void* C3, int ldc3, float* D, int ldc, int alt, void* hip_stream) {
   using namespace aimnet;
   if (alt < 0 || alt > 2) return AIMNET_E_INVALID;
   static bool once = false;
   if (!once) {
-    int rc = gemm_bf3a_set_attributes();
+    int rc = gemm_split_set_attributes();
     if (rc) return rc;
     once = true;
   }
-  return launch_gemm_bf3a_cfg((hipStream_t)hip_stream, cfg, epi, out3 != 0, (const unsigned short*)A3, lda3, (const unsigned short*)Bt3,
-                              ldb, M, N, K, bias, C, (unsigned short*)C3, ldc3, D, ldc, nullptr, 0, alt);
+  return launch_gemm_split_cfg((hipStream_t)hip_stream, fmt, cfg, epi, out != 0,
+                               SplitArgs{(const unsigned short*)A3, lda3, (const unsigned short*)Bt, ldb, M, N, K, bias, C,
+                                         (unsigned short*)C3, ldc3, D, ldc, nullptr, 0, alt});
+}
+int aimnet_debug_gemm_bf3a(int cfg, int epi, int out3, const void* A3, int lda3, const void* Bt3, int ldb, int M, int N, int K,
+                           const float* bias, float* C, void* C3, int ldc3, float* D, int ldc, int alt, void* hip_stream) {
+  return debug_gemm_split(aimnet::SPLIT_BF3, cfg, epi, out3, A3, lda3, Bt3, ldb, M, N, K, bias, C, C3, ldc3, D, ldc, alt, hip_stream);
 }
 int aimnet_debug_split_h2(const float* src, int ld, int M, int K, void* dst, int ldd, int mode, void* hip_stream) {
   if (!src || !dst || M <= 0 || K <= 0 || ldd < 2 * pad32(K) || ldd % 64 || mode < 0 || mode > 2) return AIMNET_E_INVALID;
@@ -1554,16 +1556,7 @@ int aimnet_debug_split_h2(const float* src, int ld, int M, int K, void* dst, int
 
 int aimnet_debug_gemm_h2(int cfg, int epi, int out2, const void* A2, int lda2, const void* Bt2, int ldb, int M, int N, int K,
                          const float* bias, float* C, void* C2, int ldc2, float* D, int ldc, int alt, void* hip_stream) {
-  using namespace aimnet;
-  if (alt < 0 || alt > 2) return AIMNET_E_INVALID;
-  static bool once = false;
-  if (!once) {
-    int rc = gemm_h2_set_attributes();
-    if (rc) return rc;
-    once = true;
-  }
-  return launch_gemm_h2_cfg((hipStream_t)hip_stream, cfg, epi, out2 != 0, (const unsigned short*)A2, lda2, (const unsigned short*)Bt2,
-                            ldb, M, N, K, bias, C, (unsigned short*)C2, ldc2, D, ldc, nullptr, 0, alt);
+  return debug_gemm_split(aimnet::SPLIT_H2, cfg, epi, out2, A2, lda2, Bt2, ldb, M, N, K, bias, C, C2, ldc2, D, ldc, alt, hip_stream);
 }
 int aimnet_engine_debug_mlp_sweep(aimnet_engine* e, int pass, int backward, int chain, int flag, const void* x2, int M,
                                   const int32_t* numbers, float* const* H, float* const* D, float* const* zb, int* which,
@@ -1577,11 +1570,11 @@ int aimnet_engine_debug_mlp_sweep(aimnet_engine* e, int pass, int backward, int 
   hipStream_t s = (hipStream_t)hip_stream;
   if (!backward) {
     if (!x2 || !H) return AIMNET_E_INVALID;
-    return mlp_sweep_fwd(e, s, 2, pass, M, numbers, reinterpret_cast<const float*>(x2), H, D, flag != 0, chain != 0);
+    return mlp_sweep_fwd(e, s, SPLIT_H2, pass, M, numbers, reinterpret_cast<const float*>(x2), H, D, flag != 0, chain != 0);
   }
   if (!zb || !zb[0] || !zb[1] || !which) return AIMNET_E_INVALID;
   float *zcur = zb[0], *znext = zb[1];
-  const int rc = mlp_sweep_bwd(e, s, 2, pass, M, flag != 0, zcur, znext, D, chain != 0);
+  const int rc = mlp_sweep_bwd(e, s, SPLIT_H2, pass, M, flag != 0, zcur, znext, D, chain != 0);
   *which = zcur == zb[0] ? 0 : 1;
   return rc;
 }

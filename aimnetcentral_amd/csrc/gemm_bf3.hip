@@ -505,20 +505,20 @@ static int launch_bf3(hipStream_t stream, int epi, const float* A, int lda, cons
 
 static int g_bf3_force_tile = 0;  // AIMNET_BF3_TILE forces one configuration (A/B runs)
 
-struct Bf3Cand { int id, tm, tn; };
 // id = 100 * WN (waves across N; 8 / WN across M) + 10 * SM + SN; block tile (16 SM 8 / WN) x (16 SN WN)
-static const Bf3Cand kBf3Cands[] = {{452, 160, 128}, {224, 128, 128}, {432, 96, 128}, {422, 64, 128}, {223, 128, 96},
-                                    {851, 80, 128},  {234, 192, 128}, {871, 112, 128}, {861, 96, 128}, {891, 144, 128}};
+static const SplitTileCand kBf3Cands[] = {{452, 160, 128}, {224, 128, 128}, {432, 96, 128}, {422, 64, 128}, {223, 128, 96},
+                                     {851, 80, 128},  {234, 192, 128}, {871, 112, 128}, {861, 96, 128}, {891, 144, 128}};
 
 // Tile choice: the busiest CU runs ceil(tiles / CUs) tiles one after the other (all these tiles hold one block per CU); a tile
 // costs its MFMA work (tm x tn), the operand stream and split work per k-step (tm + tn) and a fixed prologue / epilogue part.
 // Fitted to tests/tools/bf3_bench.py on the fourteen MLP layer shapes at 10 080 rows: it reproduces the measured best tile of
 // every shape (profiles/r3_gemm_bf3.md).
-static int choose_bf3_tile(int M, int N) {
+int choose_tile_by_cost(const SplitTileCand* cands, int n, int M, int N) {
   const long n_cu = device_cus();
-  int best = kBf3Cands[0].id;
+  int best = cands[0].id;
   double best_cost = 1e300;
-  for (const Bf3Cand& c : kBf3Cands) {
+  for (int t = 0; t < n; ++t) {
+    const SplitTileCand& c = cands[t];
     const long tiles = (long)ceil_div(M, c.tm) * ceil_div(N, c.tn);
     const long per_cu = (tiles + n_cu - 1) / n_cu;
     const double cost = (double)per_cu * ((double)c.tm * c.tn + 60.0 * (c.tm + c.tn) + 3000.0);
@@ -536,7 +536,7 @@ int launch_gemm_bf3_cfg(hipStream_t stream, int cfg, int epi, const float* A, in
     return -1;
   }
   if (cfg == 0) cfg = g_bf3_force_tile;
-  if (cfg == 0) cfg = choose_bf3_tile(M, N);
+  if (cfg == 0) cfg = choose_tile_by_cost(kBf3Cands, (int)(sizeof(kBf3Cands) / sizeof(kBf3Cands[0])), M, N);
   switch (cfg) {
 #define AIMNET_BF3_CASE(ID, SM_, SN_, WN_)                                                                                        \
     case ID: return launch_bf3<SM_, SN_, WN_, 1>(stream, epi, A, lda, Bt, ldb, M, N, K, bias, C, D, ldc, brow, ldbias, kneg);      \

@@ -100,11 +100,16 @@ __device__ __forceinline__ void store_h2_tile_pair(unsigned short* __restrict__ 
   }
 }
 
-// format-generic store of four consecutive columns: FMT 1 = bf3 (gemm_bf3_common.h), 2 = h2 activation form
+// format-generic stores of four consecutive columns / of a tile pair: FMT 1 = bf3 (gemm_bf3_common.h), 2 = h2 activation form
 template <int FMT>
 __device__ __forceinline__ void store_split_x4(unsigned short* __restrict__ row, int col, f32x4 v) {
   if constexpr (FMT == 2) store_h2_x4(row, col, v);
   else store_bf3_x4(row, col, v);
+}
+template <int FMT>
+__device__ __forceinline__ void store_split_tile_pair(unsigned short* __restrict__ crow, int col0, int lc, f32x4 v0, f32x4 v1) {
+  if constexpr (FMT == 2) store_h2_tile_pair(crow, col0, lc, v0, v1);
+  else store_bf3_tile_pair(crow, col0, lc, v0, v1);
 }
 
 // ---- LDS tile of one k-step: blocks of 16 rows, [hi: 16 rows x 64 B][lo: 16 rows x 64 B] = 2 KiB; the 16-byte granule of

@@ -497,7 +497,7 @@ __global__ __launch_bounds__(512) void head_fused_h2_kernel(HeadFusedArgs a) {
 
 int launch_head_fused(hipStream_t s, const HeadFusedArgs& a) {
   if (a.M <= 0) return 0;
-  const int blk = a.fmt == 2 ? 64 : 96;  // 16-bit elements per 32-k block of a row
+  const int blk = 32 * split_planes(a.fmt);  // 16-bit elements per 32-k block of a row
   if ((a.lda3 % blk) || (a.ldz3 % blk) || (a.ldd & 3) ||
       (((size_t)a.aim3 | (size_t)a.w1 | (size_t)a.w2 | (size_t)a.w2t | (size_t)a.w1t | (size_t)a.b1 | (size_t)a.b2 | (size_t)a.w3 |
         (size_t)a.dlast | (size_t)a.zbar3) & 15)) {
@@ -509,7 +509,7 @@ int launch_head_fused(hipStream_t s, const HeadFusedArgs& a) {
     AIMNET_HIP_CHECK(hipFuncSetAttribute((const void*)head_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     AIMNET_HIP_CHECK(hipFuncSetAttribute((const void*)head_fused_h2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   }
-  if (a.fmt == 2) hipLaunchKernelGGL(head_fused_h2_kernel, dim3(ceil_div(a.M, HT)), dim3(512), H2_LDS, s, a);
+  if (a.fmt == SPLIT_H2) hipLaunchKernelGGL(head_fused_h2_kernel, dim3(ceil_div(a.M, HT)), dim3(512), H2_LDS, s, a);
   else hipLaunchKernelGGL(head_fused_kernel, dim3(ceil_div(a.M, HT)), dim3(512), H_LDS, s, a);
   AIMNET_LAUNCH_CHECK();
   return 0;

@@ -44,25 +44,39 @@ int launch_gemm_bf3_cfg(hipStream_t stream, int cfg, int epi, const float* A, in
                         int N, int K, const float* bias, float* C, float* D, int ldc, const int* brow = nullptr, int ldbias = 0,
                         int kneg = BF3_NO_NEG);
 int gemm_bf3_set_attributes();
+// tile choice of the split GEMMs (gemm_bf3.hip, gemm_split.h): the candidate whose busiest CU finishes first (gemm_bf3.hip)
+struct SplitTileCand { int id, tm, tn; };
+int choose_tile_by_cost(const SplitTileCand* cands, int n, int M, int N);
 
-// ---- gemm_bf3a.hip: the same product with the ACTIVATIONS pre-split as well (A3: bf3 layout, lda3 = bf16 elements per row, a
-// multiple of 96): both operands reach LDS by DMA, no vector work in the main loop.  out3: the GELU / chain-rule epilogues write
-// C in bf3 form (C3, ldc3 >= 3 * pad32(N)) for the next layer instead of fp32 (C, ldc); D is fp32 [M][ldc] either way.
-int launch_gemm_bf3a_cfg(hipStream_t stream, int cfg, int epi, bool out3, const unsigned short* A3, int lda3, const unsigned short* Bt,
-                         int ldb, int M, int N, int K, const float* bias, float* C, unsigned short* C3, int ldc3, float* D, int ldc,
-                         const int* brow = nullptr, int ldbias = 0, int alt = 0);
+// ---- gemm_bf3a.hip / gemm_h2.hip: the same product with the ACTIVATIONS pre-split as well - ONE kernel body, launcher and tile
+// choice (gemm_split.h) over two operand formats, the values split_format() (engine.h) returns:
+//   SPLIT_BF3: three bf16 planes (the "bf3" layout above, 192 B per row and k-block), six matrix instructions per tile and k-step
+//   SPLIT_H2 : fp16 hi + scaled fp16 lo ("h2", gemm_h2_common.h: fp32 == hi + lo / 4096 to 2^-24; [hi: 32 fp16][lo: 32 fp16]
+//              = 128 B per row and k-block), three matrix instructions
+// A3 / Bt: both operands in the format's layout, lda3 / ldb = 16-bit elements per row (a multiple of 32 * split_planes(fmt)); both
+// reach LDS by DMA, no vector work in the main loop.  out: the GELU / chain-rule epilogues write C in the same form (C3, ldc3 >=
+// split_planes(fmt) * pad32(N)) for the next layer instead of fp32 (C, ldc); D is fp32 [M][ldc] either way.
+enum { SPLIT_NONE = 0, SPLIT_BF3 = 1, SPLIT_H2 = 2 };
+constexpr int split_planes(int fmt) { return fmt == SPLIT_H2 ? 2 : 3; }  // 16-bit elements per fp32 value of a split row
+struct SplitArgs {  // the kernels' arguments, in their order (brow, ldbias: as launch_gemm_nt; alt: below)
+  const unsigned short* A3;
+  int lda3;
+  const unsigned short* Bt;
+  int ldb, M, N, K;
+  const float* bias;
+  float* C;
+  unsigned short* C3;
+  int ldc3;
+  float* D;
+  int ldc;
+  const int* brow;
+  int ldbias, alt;
+};
+int launch_gemm_split_cfg(hipStream_t stream, int fmt, int cfg, int epi, bool out, const SplitArgs& a);
 // alt: 0 = weights stored with their own sign (result = sum of the two accumulator sets), 1 = BF3_ALT weights and the launch starts
-// on an even k-block (result = even - odd), 2 = BF3_ALT weights, odd first k-block (result = odd - even)
-int gemm_bf3a_set_attributes();
-
-// ---- gemm_h2.hip: the same product on fp16x2-split operands ("h2", gemm_h2_common.h: fp32 == hi + lo / 4096 to 2^-24; per row,
-// K/32 blocks of [hi: 32 fp16][lo: 32 fp16] = 128 B; ld counts 16-bit elements = 2 x the padded K): three matrix instructions per
-// tile and k-step instead of six.  out2: the GELU / chain-rule epilogues write C in h2 form (C2, ldc2 >= 2 * pad32(N)).
-// alt as launch_gemm_bf3a_cfg (1 / 2: weights in the H2_WEIGHT form and activations in the H2_ACT form; 0: both plain).
-int launch_gemm_h2_cfg(hipStream_t stream, int cfg, int epi, bool out2, const unsigned short* A2, int lda2, const unsigned short* Bt,
-                       int ldb, int M, int N, int K, const float* bias, float* C, unsigned short* C2, int ldc2, float* D, int ldc,
-                       const int* brow = nullptr, int ldbias = 0, int alt = 0);
-int gemm_h2_set_attributes();
+// on an even k-block (result = even - odd), 2 = BF3_ALT weights, odd first k-block (result = odd - even); for SPLIT_H2, 1 / 2:
+// weights in the H2_WEIGHT form and activations in the H2_ACT form; 0: both plain
+int gemm_split_set_attributes();  // AIMNET_BF3A_TILE, AIMNET_H2_TILE, AIMNET_H2_DEEP
 // mode: 0 plain, 1 activation form (lo of the odd k-blocks negated), 2 weight form (hi of the odd k-blocks negated)
 enum { H2_PLAIN = 0, H2_ACT = 1, H2_WEIGHT = 2 };
 bool split_h2_host(const float* w, int rows, int K, unsigned short* out, int mode);  // false: an entry does not fit fp16's range
@@ -115,7 +129,7 @@ struct HeadFusedArgs {
   unsigned short* zbar3;                      // [M][ldz3] adjoint of that layer's pre-activation, bf3 form (grad only)
   int ldz3;
   int M, grad;
-  int fmt = 1;  // 1: operands in the bf16x3 form (BF3_ALT weights), 2: in the fp16x2 form (H2_WEIGHT weights, H2_ACT activations)
+  int fmt = SPLIT_BF3;  // SPLIT_BF3: operands in the bf16x3 form (BF3_ALT weights), SPLIT_H2: in the fp16x2 form (H2_WEIGHT weights, H2_ACT activations)
 };
 int launch_head_fused(hipStream_t s, const HeadFusedArgs& a);
 

@@ -21,7 +21,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 TILES = [0, 452, 432, 422, 223, 224, 234, 851]
-TILE_TM = {452: 160, 432: 96, 422: 64, 223: 128, 224: 128, 234: 192, 851: 80}  # block tile rows (gemm_h2.hip kH2Cands)
+TILE_TM = {452: 160, 432: 96, 422: 64, 223: 128, 224: 128, 234: 192, 851: 80}  # block tile rows (gemm_split.h kSplitCands)
 MAX_ERR, RMS_REL = 5e-5, 1e-6  # the gate of the exact-fp32 / bf16x3 siblings (test_gpu_ops.py); relative rms of mean |z|
 SENT16 = 0x7E5B  # sentinel of the guard bands (a NaN as fp16, an odd bit pattern in every other reading)
 SENT32 = 0x7FC0DEAD
