@@ -29,6 +29,8 @@ void set_last_error(const char* fmt, ...);
     }                                                                                     \
   } while (0)
 
+constexpr float BOHR_INV_F = 1.8897261258369282f;  // 1 / 0.5291772105638411: 1 A in Bohr (constants.py:8-9)
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

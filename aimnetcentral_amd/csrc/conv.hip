@@ -1039,31 +1039,8 @@ int launch_conv_bwd(hipStream_t s, int nq, bool need_abar, bool stress, const fl
 constexpr int REV_ROW_MAX = 128;  // row capacity: positions fit 8 bits and a 256-slot table stays at most half full
 bool pair_rev_supported(int n_atoms, int cap) { return cap <= REV_ROW_MAX && n_atoms < (1 << 25); }
 
-// (the hash build and the lookup live in pairmap.h as device functions: they also ride on other launches, kernels.h PairMapRider)
-__global__ __launch_bounds__(256) void pair_hash_kernel(const int* __restrict__ nb_idx, const int* __restrict__ nb_shift,
-                                                        const int* __restrict__ nb_cnt, int cap, int n_atoms,
-                                                        unsigned long long* __restrict__ tab, int* __restrict__ rev) {
-  __shared__ unsigned long long s_tab[4][RH_SLOTS];
-  pair_hash_block(nb_idx, nb_shift, nb_cnt, cap, n_atoms, tab, rev, blockIdx.x, s_tab);
-}
-
-__global__ __launch_bounds__(256) void pair_rev_hash_kernel(const int* __restrict__ nb_idx, const int* __restrict__ nb_shift,
-                                                            const int* __restrict__ nb_cnt, int cap, int n_atoms,
-                                                            const unsigned long long* __restrict__ tab, int* __restrict__ rev) {
-  pair_rev_hash_block(nb_idx, nb_shift, nb_cnt, cap, n_atoms, tab, rev, blockIdx.x);
-}
-
+// (the hash build and the lookup live in pairmap.h as device functions: they ride on other launches, kernels.h PairMapRider)
 size_t pair_hash_bytes(int n_atoms) { return (size_t)n_atoms * RH_SLOTS * sizeof(unsigned long long); }
-
-int launch_pair_rev_hash(hipStream_t s, const int* nb_idx, const int* nb_shift, const int* nb_cnt, int cap, int n_atoms,
-                         unsigned long long* tab, int* rev) {
-  hipLaunchKernelGGL(pair_hash_kernel, dim3(ceil_div(n_atoms, 4)), dim3(256), 0, s, nb_idx, nb_shift, nb_cnt, cap, n_atoms, tab, rev);
-  AIMNET_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pair_rev_hash_kernel, dim3(ceil_div(n_atoms, 4)), dim3(256), 0, s, nb_idx, nb_shift, nb_cnt, cap, n_atoms, tab,
-                     rev);
-  AIMNET_LAUNCH_CHECK();
-  return 0;
-}
 
 // forces_i = -(fgrad_i + sum_m F1(i -> j_m) - F1(j_m -> i))  (conv_bwd_kernel XE form; one wave per atom, lane = pair): the last
 // kernel of the backward, it writes the force output itself
@@ -1094,33 +1071,6 @@ int launch_pair_force(hipStream_t s, const int* nb_idx, const int* nb_cnt, const
 // i.e. 64 + 64 floats per pair instead of a 1 KiB feature row and a 4 KiB Sbar row, and 16x fewer FMAs.
 // Exact re-association of the reference sums (Warp backward_g, conv_sv_2d_sp_wp.py:139-164, with the AEV
 // backward of aev.py:94-110); no gradient with respect to a_j is needed because afv is a constant.
-__global__ void species_kernel(const int* __restrict__ numbers, const int* __restrict__ slot_of_z, int n_atoms,
-                               int* __restrict__ aslot, unsigned long long* __restrict__ present_part) {
-  __shared__ unsigned long long s_mask;
-  if (threadIdx.x == 0) s_mask = 0ull;
-  __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  unsigned long long m = 0ull;
-  if (i < n_atoms) {
-    const int sl = slot_of_z[min(63, max(0, numbers[i]))];
-    aslot[i] = sl;
-    m = 1ull << sl;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m |= __shfl_xor(m, off, 64);
-  if ((threadIdx.x & 63) == 0) atomicOr(&s_mask, m);
-  __syncthreads();
-  if (threadIdx.x == 0) present_part[blockIdx.x] = s_mask;
-}
-
-int launch_species(hipStream_t s, const int* numbers, const int* slot_of_z, int n_atoms, int* aslot,
-                   unsigned long long* present_part) {
-  hipLaunchKernelGGL(species_kernel, dim3(ceil_div(n_atoms, 256)), dim3(256), 0, s, numbers, slot_of_z, n_atoms, aslot,
-                     present_part);
-  AIMNET_LAUNCH_CHECK();
-  return 0;
-}
-
 constexpr int P0_AFV_LDS = 8;  // embedding rows of the species present that unconcat_p0_kernel keeps in LDS
 
 // xbar of pass 0 -> Sbar_i (registers/LDS only, never written to HBM) -> T_i[s] for the species present.

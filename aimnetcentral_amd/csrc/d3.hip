@@ -28,7 +28,6 @@
 
 namespace aimnet {
 
-constexpr float BOHR_INV_F = 1.8897261258369282f;   // 1 / 0.5291772105638411 (constants.py:8-9)
 constexpr float HALF_HARTREE_F = 13.605693012183622f;
 constexpr int D3W = 12;  // floats per atom in the weight table: s[5], w[5], cn, pad
 constexpr int D3_SLOTS = 4;  // list slots per loop trip in the two light passes (cn, cnforce)

@@ -46,6 +46,46 @@ struct View {
   int elem_size, row_stride;
 };
 
+// carves a workspace into 256-byte aligned buffers (base == NULL: size query, every pointer NULL); named buffers are recorded as
+// debug views when `views` is given
+struct Carver {
+  char* base;
+  size_t off = 0;
+  std::map<std::string, View>* views = nullptr;
+  template <typename T>
+  T* take(size_t n, const char* name = nullptr, int row_stride = 0) {
+    off = align_up(off, 256);
+    T* p = base ? (T*)(base + off) : nullptr;
+    if (name && views) (*views)[name] = View{off, n, (int)sizeof(T), row_stride};
+    off += n * sizeof(T);
+    return p;
+  }
+};
+
+#define RC(call)         \
+  do {                   \
+    int _rc = (call);    \
+    if (_rc) return _rc; \
+  } while (0)
+
+// large non-periodic molecules (>= 1500 atoms on average) get a bounding-box cell list instead of the O(n^2) scan
+static inline bool bbox_applies(int n_atoms, int n_mol) { return (long)n_atoms >= 1500L * n_mol; }
+
+static inline CoulombParams coulomb_params(const aimnet_arch& ar, const aimnet_eval_options* opt) {
+  const float half_hartree_bohr = (float)(0.5 * 27.211386024367243 * 0.5291772105638411);
+  return CoulombParams{half_hartree_bohr, ar.sr_rc, ar.sr_envelope, opt->dsf_rc, opt->dsf_alpha};
+}
+static inline D3Params d3_params(const aimnet_eval_options* opt) {  // (the S5 switch window is in Bohr)
+  return D3Params{opt->d3_s6, opt->d3_s8, opt->d3_a1, opt->d3_a2, opt->d3_smoothing_on * BOHR_INV_F, opt->d3_cutoff * BOHR_INV_F};
+}
+// Ewald / PME arguments of both entry points: 0 fine, 1 the cell is not periodic along all three axes, 2 the accuracy is outside
+// (0, 1) or the capacity (ewald_max_k, PME: pme_max_mesh) below its minimum
+static inline int ewald_args_check(const aimnet_inputs* in, const aimnet_eval_options* opt) {
+  if (!in->cell || in->pbc_sys || !(in->pbc[0] && in->pbc[1] && in->pbc[2])) return 1;
+  const bool cap_ok = opt->coulomb == AIMNET_COULOMB_PME ? opt->pme_max_mesh >= 512 : opt->ewald_max_k >= EWALD_KB;
+  return (opt->ewald_accuracy > 0.0f && opt->ewald_accuracy < 1.0f && cap_ok) ? 0 : 2;
+}
+
 }  // namespace aimnet
 
 using aimnet::BasisParams;
@@ -153,12 +193,6 @@ struct aimnet_engine {
   int conv_xe = 1;
   // atoms up to which the 4-waves-per-atom "split" conv kernels are used (AIMNET_SPLIT_MAX / set_option("split_max")); per engine
   int split_max = aimnet::conv_split_max_default();
-  // AIMNET_OVERLAP_COULOMB / set_option("overlap_coulomb"): the Coulomb / DFT-D3 pair kernels (VALU-bound, they need only the
-  // final charges) run on a second HIP stream next to the last pass' MLP, the energy head and the first backward GEMMs
-  // (MFMA-bound): forked after the last charge update, joined in front of the first conv backward
-  int overlap_coulomb = 0;  // measured (profiles/r2_summary.md): 2.135 vs 2.118 ms/step - concurrent kernels of one process slow each other down here too
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   std::vector<Layer> mlp[AIMNET_MAX_PASS];
   std::vector<Layer> head;
   float* head_w_last;  // [k] last head layer as a vector
@@ -188,4 +222,5 @@ int mlp_gemm3(const aimnet_engine* e, hipStream_t s, int fmt, int epi, bool out3
               bool fwd, int k0, int n0, int M, int N, int K, const float* bias, float* C, unsigned short* C3, int ldc3, float* D, int ldc,
               const int* brow = nullptr, int ldbias = 0);
 int split_format(const aimnet_engine* e, int n_rows);  // 0: fp32 activations, 1: bf3, 2: h2 (engine.hip)
+int max_width(const aimnet_engine* e);  // widest padded layer of the MLPs and the energy head (engine.hip)
 }  // namespace aimnet

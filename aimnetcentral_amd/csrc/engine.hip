@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "eval_plan.h"
 
 namespace aimnet {
 
@@ -142,10 +143,10 @@ const OptionRow OPTIONS[] = {
     {"dsf_np_walk", "AIMNET_DSF_NP_WALK", &aimnet_engine::dsf_np_walk, OPT_BOOL, 0, 1},
     {"split_max", "AIMNET_SPLIT_MAX", &aimnet_engine::split_max, OPT_RANGE, 0, INT32_MAX},
     {"p0_moments", "AIMNET_P0_MOMENTS", &aimnet_engine::p0_moments, OPT_BOOL, 0, 1},
-    {"overlap_coulomb", "AIMNET_OVERLAP_COULOMB", &aimnet_engine::overlap_coulomb, OPT_BOOL, 0, 1},
     {"spatial_order", "AIMNET_SPATIAL_ORDER", &aimnet_engine::spatial_order, OPT_BOOL, 0, 1},
     {nullptr, "AIMNET_KEEP_INTERMEDIATES", &aimnet_engine::keep_intermediates, OPT_BOOL, 0, 1},
     {"conv_mfma", "profiles/r2_conv_mfma.md", nullptr, OPT_RETIRED, 0, 0},
+    {"overlap_coulomb", "profiles/r6_overlap_coulomb_ab.txt", nullptr, OPT_RETIRED, 0, 0},
 };
 const OptionRow* find_option(const char* name) {
   for (const OptionRow& r : OPTIONS)
@@ -261,19 +262,17 @@ bool head_fusable(const aimnet_engine* e) {
          e->head[1].n_out == 128 && e->head[2].n_in == 128 && e->head[2].n_out == 1 && e->mlp[e->arch.n_pass - 1].back().k_out == 256 &&
          !e->arch.last_linear[e->arch.n_pass - 1] && e->head_fused != 0;
 }
-// activations in split form for this batch? (layout() and eval() must agree)
-bool presplit_active(const aimnet_engine* e, int N) {
-  const bool bf3 = e->gemm_bf3 == 2 || (e->gemm_bf3 == 1 && N > 256);  // the batches that take the split GEMMs at all (mlp_gemm)
-  return e->gemm_presplit != 0 && bf3 && !e->keep_intermediates;
-}
+// GEMM activations in split form for this batch?  SPLIT_NONE, or SPLIT_H2 (fp16x2, gemm_h2.hip) / SPLIT_BF3 (bf16x3, gemm_bf3a.hip)
 int split_format(const aimnet_engine* e, int n_rows) {
-  if (!presplit_active(e, n_rows)) return SPLIT_NONE;
+  const bool bf3 = e->gemm_bf3 == 2 || (e->gemm_bf3 == 1 && n_rows > 256);  // the batches that take the split GEMMs at all (mlp_gemm)
+  if (!(e->gemm_presplit != 0 && bf3 && !e->keep_intermediates)) return SPLIT_NONE;
   return (e->gemm_h2 && e->h2_fits) ? SPLIT_H2 : SPLIT_BF3;
 }
 
-// ---- one MLP sweep on split activations (sfmt SPLIT_BF3 = bf16x3, SPLIT_H2 = fp16x2): ONE launch of gemm_chain.hip where the pass has a plan
+// ---- one MLP sweep.  Split activations (sfmt SPLIT_BF3 = bf16x3, SPLIT_H2 = fp16x2): ONE launch of gemm_chain.hip where the pass has a plan
 // (fp16x2 form only), else one launch per layer.  x: the input rows in split form; H[l]: layer outputs (hidden ones in split form -
 // the chain does not write them -, the last in fp32, or in split form for the fused energy head: `split_last`); D[l]: GELU' (fp32).
+// SPLIT_NONE: fp32 rows throughout, one mlp_gemm per layer.
 int mlp_sweep_fwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N, const int* numbers, const float* x, float* const* H,
                   float* const* D, bool split_last, bool chain) {
   const aimnet_arch& ar = e->arch;
@@ -308,29 +307,30 @@ int mlp_sweep_fwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N,
     }
     return launch_gemm_chain(s, cf.shape, ca);
   }
-  const unsigned short* a3 = reinterpret_cast<const unsigned short*>(x);
-  int lda3 = pm * Ls[0].k_in;
+  const float* hin = x;  // fp32 rows, or split rows behind the same pointer
+  int ld_in = Ls[0].k_in;
   for (int l = 0; l < nl; ++l) {
     const bool last = l == nl - 1, linear = last && ar.last_linear[p];
-    const bool f32out = last && !split_last;  // the last layer's output is read by pointwise kernels - or by the fused head
+    // the last layer's output is read by pointwise kernels (fp32) - or, in split form, by the fused head
+    const bool f32out = sfmt == SPLIT_NONE || (last && !split_last);
     const int epi = linear ? EPI_BIAS : EPI_BIAS_GELU, ko = Ls[l].k_out;
-    float* Cf = f32out ? H[l] : nullptr;
-    unsigned short* C3 = f32out ? nullptr : reinterpret_cast<unsigned short*>(H[l]);
+    const int k0 = (l == 0 && emb0) ? 256 : 0;  // embedding columns folded into the per-element bias table
+    const float* bias = k0 ? e->emb_bias0 : Ls[l].b;
+    const int* brow = k0 ? numbers : nullptr;
     float* Dl = linear ? nullptr : D[l];
-    int rc;
-    if (l == 0 && emb0)
-      rc = mlp_gemm3(e, s, sfmt, epi, !f32out, a3, lda3, Ls[l], true, 256, 0, N, ko, Ls[l].k_in - 256, e->emb_bias0, Cf, C3, pm * ko, Dl, ko,
-                     numbers, ko);
+    if (sfmt == SPLIT_NONE)
+      RC(mlp_gemm(e, s, epi, hin + k0, ld_in, Ls[l], true, k0, 0, N, ko, Ls[l].k_in - k0, bias, H[l], Dl, ko, brow, k0 ? ko : 0));
     else
-      rc = mlp_gemm3(e, s, sfmt, epi, !f32out, a3, lda3, Ls[l], true, 0, 0, N, ko, Ls[l].k_in, Ls[l].b, Cf, C3, pm * ko, Dl, ko);
-    if (rc) return rc;
-    a3 = C3;
-    lda3 = pm * ko;
+      RC(mlp_gemm3(e, s, sfmt, epi, !f32out, reinterpret_cast<const unsigned short*>(hin), pm * ld_in, Ls[l], true, k0, 0, N, ko,
+                   Ls[l].k_in - k0, bias, f32out ? H[l] : nullptr, f32out ? nullptr : reinterpret_cast<unsigned short*>(H[l]), pm * ko, Dl,
+                   ko, brow, k0 ? ko : 0));
+    hin = H[l];
+    ld_in = ko;
   }
   return 0;
 }
-// adjoint sweep: zcur = adjoint of the last layer's pre-activation (split form, GELU' applied) -> zcur = xbar (fp32, row stride
-// k_in of the first layer; conv_only: only its columns 256.. are formed).  zcur / znext are the ping-pong buffers.
+// adjoint sweep: zcur = adjoint of the last layer's pre-activation (split form - SPLIT_NONE: fp32 -, GELU' applied) -> zcur = xbar
+// (fp32, row stride k_in of the first layer; conv_only: only its columns 256.. are formed).  zcur / znext are the ping-pong buffers.
 int mlp_sweep_bwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N, bool conv_only, float*& zcur, float*& znext,
                   float* const* D, bool chain) {
   const std::vector<Layer>& Ls = e->mlp[p];
@@ -364,42 +364,32 @@ int mlp_sweep_bwd(const aimnet_engine* e, hipStream_t s, int sfmt, int p, int N,
   }
   for (int l = nl - 1; l >= 0; --l) {
     const Layer& L = Ls[l];
-    const unsigned short* z3 = reinterpret_cast<const unsigned short*>(zcur);
-    int rc;
-    if (l > 0)
-      rc = mlp_gemm3(e, s, sfmt, EPI_MUL, true, z3, pm * ld, L, false, 0, 0, N, L.k_in, L.k_out, nullptr, nullptr,
-                     reinterpret_cast<unsigned short*>(znext), pm * L.k_in, D[l - 1], L.k_in);
-    else if (conv_only)
-      rc = mlp_gemm3(e, s, sfmt, EPI_NONE, false, z3, pm * ld, L, false, 0, 256, N, L.k_in - 256, L.k_out, nullptr, znext + 256, nullptr, 0,
-                     nullptr, L.k_in);
-    else
-      rc = mlp_gemm3(e, s, sfmt, EPI_NONE, false, z3, pm * ld, L, false, 0, 0, N, L.k_in, L.k_out, nullptr, znext, nullptr, 0, nullptr,
-                     L.k_in);
-    if (rc) return rc;
+    const int n0 = (l == 0 && conv_only) ? 256 : 0;  // first column of xbar that is formed
+    const int epi = l > 0 ? EPI_MUL : EPI_NONE;
+    float* Dl = l > 0 ? D[l - 1] : nullptr;
+    if (sfmt == SPLIT_NONE)
+      RC(mlp_gemm(e, s, epi, zcur, ld, L, false, 0, n0, N, L.k_in - n0, L.k_out, nullptr, znext + n0, Dl, L.k_in));
+    else  // the adjoints of hidden activations stay in split form, xbar is fp32
+      RC(mlp_gemm3(e, s, sfmt, epi, l > 0, reinterpret_cast<const unsigned short*>(zcur), pm * ld, L, false, 0, n0, N, L.k_in - n0, L.k_out,
+                   nullptr, l > 0 ? nullptr : znext + n0, l > 0 ? reinterpret_cast<unsigned short*>(znext) : nullptr,
+                   l > 0 ? pm * L.k_in : 0, Dl, L.k_in));
     std::swap(zcur, znext);
     ld = L.k_in;
   }
   return 0;
+}
+int max_width(const aimnet_engine* e) {
+  int w = 32;
+  for (int p = 0; p < e->arch.n_pass; ++p)
+    for (const Layer& L : e->mlp[p]) w = std::max(w, std::max(L.k_in, L.k_out));
+  for (const Layer& L : e->head) w = std::max(w, std::max(L.k_in, L.k_out));
+  return w;
 }
 }  // namespace aimnet
 
 namespace {
 
 // ---- workspace layout ---------------------------------------------------------------------------
-struct Carver {
-  char* base;
-  size_t off = 0;
-  std::map<std::string, View>* views = nullptr;
-  template <typename T>
-  T* take(size_t n, const char* name = nullptr, int row_stride = 0) {
-    off = align_up(off, 256);
-    T* p = base ? (T*)(base + off) : nullptr;
-    if (name && views) (*views)[name] = View{off, n, (int)sizeof(T), row_stride};
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 struct Workspace {
   NlistBuffers nl;
   int *nb_idx, *nb_shift, *nb_cnt;
@@ -423,8 +413,7 @@ struct Workspace {
   double* part;  // per-(system, slice) partial sums of the molecule reductions
   double* part_e;  // [n_mol][S] energy partial sums when the energy reduction rides on the stress launches
   int S;         // slices per molecule
-  bool xe = false;   // reverse-pair conv backward: pair buffer + reverse map
-  float4* pairbuf;
+  float4* pairbuf;   // reverse-pair conv backward (LayoutPlan::xe): pair buffer + reverse map
   int* rev;
   unsigned long long* rev_tab;  // per-atom hash tables of the rows (hash form of the reverse-pair map)
   float *zb0, *zb1;  // ping-pong adjoint buffers (N x max padded width)
@@ -440,30 +429,14 @@ struct Workspace {
   size_t total;
 };
 
-int max_width(const aimnet_engine* e) {
-  int w = 32;
-  for (int p = 0; p < e->arch.n_pass; ++p)
-    for (const Layer& L : e->mlp[p]) w = std::max(w, std::max(L.k_in, L.k_out));
-  for (const Layer& L : e->head) w = std::max(w, std::max(L.k_in, L.k_out));
-  return w;
-}
-
-// The D3 list and the list-based (non-periodic) DSF list are the same neighbour matrix when their cutoffs agree
-// (both default to 15 A): build and store it once.  The workspace layout does not know about periodicity, so the
-// test is on the capacities the caller passed: max_nb_lr > 0 means "a DSF list will be built".
-bool d3_shares_lr_list(const aimnet_eval_options* opt, int cap_lr) {
-  return opt->coulomb == AIMNET_COULOMB_DSF && cap_lr > 0 && opt->d3_cutoff == opt->dsf_rc;
-}
-
-void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options* opt, char* base, Workspace& W,
+// P: what the layout has to know beyond the sizes (eval_plan.h) - taken as decided, nothing is re-derived here
+void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options* opt, const LayoutPlan& P, char* base, Workspace& W,
             std::map<std::string, View>* views) {
   Carver c{base, 0, views};
   const int np = e->arch.n_pass;
-  const bool grad = (opt->flags & (AIMNET_FORCES | AIMNET_STRESS)) != 0;
+  const bool grad = P.grad;
   const size_t n = (size_t)N;
-  const int cap = std::max(1, opt->max_nb), cap_lr = std::max(0, opt->max_nb_lr);
-  W.xe = e->conv_xe != 0 && grad && np > 1 && N > e->split_max &&
-         pair_rev_supported(N, cap) && n * (size_t)cap < (size_t)INT32_MAX;
+  const int cap = P.cap, cap_lr = P.cap_lr;
   char* nl_base = c.take<char>(nlist_scratch_bytes(N, n_mol));
   if (base) nlist_carve(W.nl, nl_base, N, n_mol);
   if (views)  // the wrapped coordinates sit at a fixed position inside the nlist scratch
@@ -476,8 +449,8 @@ void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options*
   W.lr_cnt = c.take<int>(n, "lr_cnt", 1);
   {
     const bool d3 = opt->dftd3 != 0;
-    const bool share = d3 && d3_shares_lr_list(opt, cap_lr);
-    const int cap_d3 = d3 && !share ? std::max(1, opt->max_nb_d3) : 0;
+    const bool share = P.d3_in_lr;  // one matrix for the D3 list and the DSF list
+    const int cap_d3 = P.cap_d3;
     W.d3_idx = share ? W.lr_idx : c.take<int>(n * cap_d3, "d3_idx", cap_d3);
     W.d3_shift = share ? W.lr_shift : c.take<int>(n * cap_d3, "d3_shift", cap_d3);
     W.d3_cnt = share ? W.lr_cnt : c.take<int>(d3 ? n : 0, "d3_cnt", 1);
@@ -488,12 +461,12 @@ void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options*
   {
     const bool pme = opt->coulomb == AIMNET_COULOMB_PME;
     const bool ew = opt->coulomb == AIMNET_COULOMB_EWALD;
-    W.ew.max_k = ew ? std::max(EWALD_KB, opt->ewald_max_k / EWALD_KB * EWALD_KB) : 0;
+    W.ew.max_k = P.ewald_max_k;
     W.ew.sys = c.take<EwaldSystem>(ew || pme ? (size_t)n_mol : 0);
     W.ew.frac = c.take<double>(ew ? n * 3 : 0);
     W.ew.k = c.take<EwaldK>(ew ? (size_t)W.ew.max_k : 0);
-    W.ew.max_mesh = pme ? std::max(512, opt->pme_max_mesh) : 0;
-    W.ew.max_parts = pme ? ceil_div(W.ew.max_mesh, PME_PART) : 0;
+    W.ew.max_mesh = P.pme_max_mesh;
+    W.ew.max_parts = P.pme_max_parts;
     const size_t mesh_all = (size_t)W.ew.max_mesh * (pme ? (size_t)n_mol : 0);
     W.ew.meshq = c.take<long long>(mesh_all);
     W.ew.ma = c.take<double>(2 * mesh_all);
@@ -507,7 +480,7 @@ void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options*
   float* h_shared[2] = {nullptr, nullptr};
   const bool share = !e->keep_intermediates;  // (not the pointers: in the size-query pass every pointer is NULL)
   // pre-split activations (gemm_bf3a.hip): the shared operand buffers hold 6 instead of 4 bytes per element
-  const size_t ps_num = presplit_active(e, N) ? 3 : 2;
+  const size_t ps_num = P.split_format != SPLIT_NONE ? 3 : 2;
   if (share) {
     int ldx_max = 32, h_max = 32;
     for (int p = 0; p < np; ++p) {
@@ -554,7 +527,7 @@ void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options*
   W.qtot = c.take<float>(e->nq > 1 ? n : 0, "qtot", 1);
   W.fgrad = c.take<float>(n * 3, "fgrad", 3);
   W.virial_atom = c.take<float>(n * 9);
-  W.S = std::min(128, std::max(1, (N / std::max(1, n_mol) + 511) / 512));
+  W.S = P.S;
   W.part = c.take<double>((size_t)n_mol * W.S * 9);
   W.part_e = c.take<double>((size_t)n_mol * W.S);
   if (grad) {
@@ -568,14 +541,427 @@ void layout(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options*
   } else {
     W.abar = W.zb0 = W.zb1 = W.Sbar = W.Sqbar = nullptr;
   }
-  W.pairbuf = c.take<float4>(W.xe ? n * cap : 0);
-  W.rev = c.take<int>(W.xe ? n * cap : 0);
-  W.rev_tab = c.take<unsigned long long>(W.xe ? pair_hash_bytes(N) / sizeof(unsigned long long) : 0);
+  W.pairbuf = c.take<float4>(P.xe ? n * cap : 0);
+  W.rev = c.take<int>(P.xe ? n * cap : 0);
+  W.rev_tab = c.take<unsigned long long>(P.xe ? pair_hash_bytes(N) / sizeof(unsigned long long) : 0);
   W.n_part = (N + 255) / 256;
   W.aslot = c.take<int>(n);
   W.bad_part = c.take<int>((n + 63) / 64);
   W.present_part = c.take<unsigned long long>((size_t)W.n_part);
   W.total = align_up(c.off, 256);
+}
+
+// ---- one evaluation in stages -------------------------------------------------------------------
+// eval_plan.h decides, once, who does which job; every stage below (a member of this context) reads from the plan whether a job is
+// its own.
+struct Eval {
+  aimnet_engine* e;
+  hipStream_t s;
+  const aimnet_inputs* in;
+  const aimnet_eval_options* opt;
+  const aimnet_outputs* out;
+  Workspace& W;
+  const EvalPlan& P;
+  int N, n_mol, n_cell, np, nq;
+  bool pbc;
+  const aimnet::DdLink* dd;  // spatial domain decomposition (aimnet_engine_set_dd) or NULL
+  const int* mol_c;          // mol_idx clamped to [0, n_mol): memory-safe whatever the caller passed (status[6] reports it)
+  const int* order;          // binned systems: centre atoms are processed in the bin-sorted order of the cell list (kernels.h, `order`)
+  const float* q_fin;        // final charges (NSE: alpha + beta is the charge everything downstream sees)
+  // reverse-pair map through per-atom hash tables of the rows (once per neighbour list).  Its only reader is launch_pair_force, the
+  // last kernel of the backward, so the two small kernels ride on later launches: the hash build on the SR-Coulomb launch, the lookup
+  // on the DSF walk (VALU-bound, the lookup is latency-bound) or else on the energy reduction - kernels.h PairMapRider
+  PairMapRider pair_map() const {
+    if (!P.rev_hash) return PairMapRider{};
+    return PairMapRider{W.nb_idx, n_cell > 0 ? W.nb_shift : nullptr, W.nb_cnt, P.layout.cap, N, W.rev_tab, W.rev, ceil_div(N, 4)};
+  }
+  int prepare(), lists_built(), lists_imported(), forward(), head(SrRiders& rider), coulomb(const SrRiders& head_rider), join();
+  int head_bwd(float*& zcur, float*& znext), nse_bwd(int p, float* znext), backward(), finalize();
+};
+
+// status words, molecule offsets / sanity flags / species slots (and, small periodic batches, the whole cell-list preparation)
+int Eval::prepare() {
+  const int* slot_of_z = P.want_species ? e->slot_of_z : nullptr;
+  if (P.prep == Prep::FusedSmall)
+    return launch_prep_small(s, in->coord, in->mol_idx, in->numbers, N, n_mol, pbc ? in->cell : nullptr, n_cell, in->pbc,
+                             in->pbc_sys, e->arch.rc, out->status, slot_of_z, W.aslot, W.present_part, W.nl);
+  const bool owned = P.status == StatusZero::RiderOwned;
+  if (!owned) AIMNET_HIP_CHECK(hipMemsetAsync(out->status, 0, 8 * sizeof(int), s));
+  // periodic fast path: the cell + bin-grid setup block rides on this launch (it needs none of its output)
+  CellSetupRider csr{};
+  const bool setup_rides = P.prep == Prep::SeparateSetupRider;
+  if (setup_rides) csr = cell_setup_rider(in->cell, n_cell, in->pbc, in->pbc_sys, e->arch.rc, N, n_mol, W.nl);
+  return launch_mol_start(s, in->mol_idx, N, n_mol, W.nl.mol_start, W.nl.mol_c, in->numbers, out->status + 6, slot_of_z,
+                          W.aslot, W.present_part,  // + aslot / present species
+                          setup_rides ? &csr : nullptr, owned ? W.bad_part : nullptr);
+}
+
+// the engine's own lists (the pair geometry (u, d) of the short-range list is written by the list builder itself)
+int Eval::lists_built() {
+  const float rc = e->arch.rc;
+  int* status = out->status;
+  if (P.prep != Prep::FusedSmall)
+    RC(launch_wrap(s, in->coord, mol_c, N, n_mol, in->cell, n_cell, in->pbc, W.nl, in->pbc_sys, pbc ? rc : 0.0f,
+                   P.prep == Prep::SeparateSetupRider));
+  if (P.bbox) RC(launch_bbox(s, n_mol, W.nl));
+  RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, rc, rc, P.layout.cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
+                  status + 0, status + 2, W.pg, P.sr_status_rides));
+  if (P.lr == ListFrom::Built)  // (periodic DSF and large non-periodic systems need no list: they walk the short-range cell grid)
+    RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->dsf_rc, -1.0f, P.layout.cap_lr, N, 0, W.nl, W.lr_idx,
+                    W.lr_shift, W.lr_cnt, status + 1, status + 3));
+  if (P.d3 == ListFrom::Built) {
+    D3CnRider cnr;  // the coordination numbers ride on the (cell-grid) build of the D3 matrix
+    if (P.d3_cn_rides) {
+      cnr.aslot = W.aslot; cnr.rcov = e->d3.rcov; cnr.nref = e->d3.nref; cnr.cnref = e->d3.cnref; cnr.d3w = W.d3w;
+    }
+    RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->d3_cutoff, -1.0f, P.cap_d3, N, 0, W.nl, W.d3_idx,
+                    W.d3_shift, W.d3_cnt, status + 4, status + 5, nullptr, false, P.d3_cn_rides ? &cnr : nullptr));
+  }
+  return 0;
+}
+
+// caller-supplied matrices: the reference hands them to the model as they are (calculator.py:1069-1071) - import them into the row
+// format of the kernels; coordinates as given (the shifts refer to them), no bins, centres processed in input order
+int Eval::lists_imported() {
+  const int cap = P.layout.cap, cap_lr = P.layout.cap_lr;
+  int* status = out->status;
+  RC(launch_wrap(s, in->coord, mol_c, N, n_mol, nullptr, 0, in->pbc, W.nl));
+  RC(launch_import_list(s, in->nbmat, pbc ? in->shifts : nullptr, in->nbmat_width, N, mol_c, in->cell, n_cell, cap, W.nl, W.nb_idx,
+                        W.nb_shift, W.nb_cnt, status + 0, status + 2, W.pg, status + 6));
+  RC(launch_list_symmetry_check(s, W.nb_idx, pbc ? W.nb_shift : nullptr, W.nb_cnt, cap, N, status + 6));
+  if (P.lr == ListFrom::Imported) {
+    RC(launch_import_list(s, in->nbmat_lr, pbc ? in->shifts_lr : nullptr, in->nbmat_lr_width, N, mol_c, in->cell, n_cell, cap_lr,
+                          W.nl, W.lr_idx, W.lr_shift, W.lr_cnt, status + 1, status + 3, nullptr, status + 6));
+    // (the bin-ordered coordinate stream of the list builder is unused with caller-supplied matrices: 16 bytes per atom of scratch)
+    RC(launch_list_symmetry_check(s, W.lr_idx, pbc ? W.lr_shift : nullptr, W.lr_cnt, cap_lr, N, status + 6, 64,
+                                  (unsigned long long*)W.nl.xs));
+  }
+  if (P.d3 == ListFrom::Imported) {
+    const int* src = in->nbmat_d3 ? in->nbmat_d3 : in->nbmat_lr;
+    const int* src_sh = in->nbmat_d3 ? in->shifts_d3 : in->shifts_lr;
+    const int src_w = in->nbmat_d3 ? in->nbmat_d3_width : in->nbmat_lr_width;
+    RC(launch_import_list(s, src, pbc ? src_sh : nullptr, src_w, N, mol_c, in->cell, n_cell, P.cap_d3, W.nl, W.d3_idx, W.d3_shift,
+                          W.d3_cnt, status + 4, status + 5, nullptr, status + 6));
+    RC(launch_list_symmetry_check(s, W.d3_idx, pbc ? W.d3_shift : nullptr, W.d3_cnt, P.cap_d3, N, status + 6, 64,
+                                  (unsigned long long*)W.nl.xs));
+  }
+  return 0;
+}
+
+// a^0 = afv[Z] is never materialised: pass 0 gathers the embedding rows directly (conv_fwd / conv_bwd row_of, update_a)
+int Eval::forward() {
+  const int sfmt = P.layout.split_format;
+  for (int p = 0; p < np; ++p) {
+    const std::vector<Layer>& Ls = e->mlp[p];
+    const int nl = (int)Ls.size();
+    RC(prof_mark(e, s, FAM_CONV_FWD));
+    RC(launch_conv_fwd(s, p > 0 ? nq : 0, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr, p > 0 ? W.q[p - 1] : nullptr,
+                       W.nb_idx, W.nb_cnt, W.pg, P.layout.cap, e->agh_a, e->agh_q, e->bp, W.x[p], Ls[0].k_in, W.V[p], W.Vq[p], N,
+                       order, p == 0 && e->p0_moments, e->split_max, sfmt));
+    RC(prof_mark(e, s, FAM_GEMM));
+    RC(mlp_sweep_fwd(e, s, sfmt, p, N, in->numbers, W.x[p], W.H[p], W.D[p], P.head_fused && p == np - 1, e->gemm_chain != 0));
+    if (p == np - 1) break;
+    RC(prof_mark(e, s, FAM_POINTWISE));
+    // (the feature update a^{p+1} = a^p + delta_a rides on the NSE launch: independent work, one kernel boundary less)
+    RC(launch_nse_fwd(s, W.H[p][nl - 1], Ls[nl - 1].k_out, nq, p > 0 ? W.q[p - 1] : nullptr, W.nl.mol_start, in->charge, n_mol, N,
+                      W.S, (float*)W.part, W.q[p], W.Fm[p], W.Dm[p], p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr,
+                      W.a[p + 1], dd));
+    // domain decomposition: the final charges of halo copies are exact only within one cutoff of the owned region, the Coulomb
+    // sums reach further - the owners' values come in through the exchange function
+    if (dd && p == np - 2 && dd->fn(dd->ctx, AIMNET_DD_CHARGES, W.q[p], (int64_t)nq * N, (void*)s) != 0) {
+      set_last_error("eval: the domain-decomposition exchange function failed (charges)");
+      return AIMNET_E_INVALID;
+    }
+  }
+  return 0;
+}
+
+// energy head: forward + backward in one launch (gemm_head.hip), or its GEMMs here and the last layer as `rider` of the SR-Coulomb
+// launch (independent of the Coulomb block, so it shares that block's first launch - kernels.h, SrRiders)
+int Eval::head(SrRiders& rider) {
+  const int sfmt = P.layout.split_format, pm = P.layout.split_planes;
+  const bool grad = P.grad;
+  const int nlp = (int)e->mlp[np - 1].size();
+  const float* hin = W.H[np - 1][nlp - 1];
+  int ld_in = e->mlp[np - 1][nlp - 1].k_out;
+  const int nh = (int)e->head.size();
+  RC(prof_mark(e, s, FAM_GEMM));
+  if (P.head_fused) {
+    HeadFusedArgs ha{};
+    ha.aim3 = reinterpret_cast<const unsigned short*>(hin);
+    ha.lda3 = pm * ld_in;
+    ha.fmt = sfmt;
+    if (sfmt == SPLIT_H2) { ha.w1 = e->head[0].w2a; ha.w2 = e->head[1].w2a; ha.w2t = e->head[1].wt2a; ha.w1t = e->head[0].wt2a; }
+    else { ha.w1 = e->head[0].w3a; ha.w2 = e->head[1].w3a; ha.w2t = e->head[1].wt3a; ha.w1t = e->head[0].wt3a; }
+    ha.b1 = e->head[0].b; ha.b2 = e->head[1].b; ha.w3 = e->head_w_last; ha.b3 = e->head_b_last;
+    ha.dlast = grad ? W.D[np - 1][nlp - 1] : nullptr;
+    ha.ldd = ld_in;
+    ha.e_atom = W.e_atom;
+    ha.zbar3 = grad ? reinterpret_cast<unsigned short*>(W.zb0) : nullptr;
+    ha.ldz3 = pm * ld_in;
+    ha.M = N;
+    ha.grad = grad ? 1 : 0;
+    return launch_head_fused(s, ha);
+  }
+  for (int l = 0; l + 1 < nh; ++l) {
+    const Layer& L = e->head[l];
+    RC(mlp_gemm(e, s, EPI_BIAS_GELU, hin, ld_in, L, true, 0, 0, N, L.k_out, L.k_in, L.b, W.hH[l], W.hD[l], L.k_out));
+    hin = W.hH[l];
+    ld_in = L.k_out;
+  }
+  RC(prof_mark(e, s, FAM_POINTWISE));
+  // with gradients: the rider also writes the backward seed d e / d z_{nh-2} = w_last * GELU'(z) into zb0
+  rider.h = hin; rider.ldh = ld_in; rider.w = e->head_w_last; rider.b = e->head_b_last;
+  rider.k = e->head[nh - 1].n_in; rider.e_atom = W.e_atom;
+  rider.d = grad ? W.hD[nh - 2] : nullptr; rider.zbar = grad ? W.zb0 : nullptr;
+  rider.n_head_blocks = ceil_div(N, 4);
+  return 0;
+}
+
+// ---- Coulomb + DFT-D3: energies, and the seeds of qbar / dE/dx / virial ----
+int Eval::coulomb(const SrRiders& head_rider) {
+  const aimnet_arch& ar = e->arch;
+  const int cap = P.layout.cap, cap_lr = P.layout.cap_lr;
+  const bool grad = P.grad, want_s = P.want_s;
+  if (nq == 2) RC(launch_charge_sum(s, W.q[np - 2], N, W.qtot, out->spin_charges));  // (aimnet2.py:102-106)
+  CoulombParams cp = coulomb_params(ar, opt);
+  const bool pme = P.lr_term == LongRange::PmeWalk;
+  const bool ewald = P.lr_term == LongRange::EwaldWalk || pme;  // (the real-space walk and the self term are the same)
+  if (pme) {  // per-system (alpha, rc, mesh) from the cell, fractional coordinates in double (pme.hip)
+    RC(launch_pme_setup(s, in->cell, n_cell, W.nl.mol_start, in->charge, nq, n_mol, opt->ewald_accuracy, W.ew, out->status + 7));
+    cp.ewald = W.ew.sys;
+  } else if (ewald) {  // per-system (alpha, rc, kc) and k boxes from the cell, fractional coordinates in double (ewald.hip)
+    RC(launch_ewald_setup(s, in->cell, n_cell, W.nl.mol_start, mol_c, W.nl.xw, in->charge, nq, N, n_mol, opt->ewald_accuracy, W.ew,
+                          out->status + 7));
+    cp.ewald = W.ew.sys;
+  }
+  const PairMapRider pmap = pair_map();
+  SrRiders rd = head_rider;
+  if (P.stream_rides) {  // the list-free walk runs below: its charge stream rides here
+    rd.xs = W.nl.xs;
+    rd.xq = (float4*)W.nl.sorted_tmp_xq;
+    rd.charges_out = out->charges;
+    rd.n_stream_blocks = ceil_div(N, 256);
+  }
+  if (P.lr_term == LongRange::SimpleInSr) {  // all pairs of the molecule: same waves
+    rd.simple_xw = W.nl.xw;
+    rd.simple_mol_idx = mol_c;
+    rd.simple_mol_start = W.nl.mol_start;
+  }
+  rd.hash = pmap;  // hash build of the reverse-pair map (n_blocks = 0: none)
+  if (P.sr_status_rides) {
+    rd.cnt_true = W.nl.sorted_tmp;  // the row counts launch_nlist left (status_later)
+    rd.status_cap = cap;
+    rd.status_max = out->status + 0;
+    rd.status_ovf = out->status + 2;
+    rd.n_status_blocks = ceil_div(N, 1024);
+    if (P.status == StatusZero::RiderOwned) {
+      rd.n_status_blocks = 1;
+      rd.status_all = out->status;
+      rd.bad_part = W.bad_part;
+      rd.keep7 = ewald ? 1 : 0;
+    }
+  }
+  RC(launch_coulomb_sr(s, grad, want_s, ar.sr_coulomb != 0, q_fin, W.nb_idx, W.nb_cnt, W.pg, cap, cp, N, W.ecoul, W.qbar, W.fgrad,
+                       W.virial_atom, &rd));
+  switch (P.lr_term) {
+    case LongRange::None:
+    case LongRange::SimpleInSr:  // ran inside the SR-Coulomb launch above (SrRiders::simple_xw)
+    case LongRange::DsfInD3:     // rides on the D3 pair pass below (one list, one geometry evaluation)
+      break;
+    case LongRange::SimpleMatrix:  // coul_simple over the caller's matrix (lr.py:311-331)
+      RC(launch_coulomb_dsf(s, grad, false, q_fin, W.nl.xw, mol_c, in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, cp, N,
+                            W.ecoul, W.qbar, W.fgrad, W.virial_atom, true));
+      break;
+    case LongRange::DsfMatrix:
+      RC(launch_coulomb_dsf(s, grad, want_s, q_fin, W.nl.xw, mol_c, in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, cp, N,
+                            W.ecoul, W.qbar, W.fgrad, W.virial_atom));
+      break;
+    case LongRange::DsfWalk:
+    case LongRange::EwaldWalk:
+    case LongRange::PmeWalk:  // the walk copies q to the `charges` output on its way
+      RC(launch_coulomb_dsf_walk(s, grad, want_s, q_fin, mol_c, W.nl, cp, N, W.ecoul, W.qbar, W.fgrad, W.virial_atom, out->charges,
+                                 true, P.rev_lookup == RevLookup::OnWalk ? &pmap : nullptr));
+      if (pme)  // reciprocal space on the mesh + neutralising background (pme.hip)
+        RC(launch_pme_recip(s, grad, want_s, W.nl.xw, q_fin, mol_c, W.nl.mol_start, order, N, n_mol, W.ew, cp.factor, W.ecoul,
+                            W.qbar, W.fgrad, W.virial_atom));
+      else if (ewald)  // reciprocal space + neutralising background, accumulated onto what the pair kernels have stored
+        RC(launch_ewald_recip(s, grad, want_s, q_fin, mol_c, W.nl.mol_start, N, n_mol, W.ew, cp.factor, W.ecoul, W.qbar, W.fgrad,
+                              W.virial_atom));
+      break;
+  }
+  if (P.d3 != ListFrom::None)  // external DFT-D3: adds to the per-atom pair energies, dE/dx and the virial seeded by the Coulomb kernels
+    RC(launch_dftd3(s, grad, want_s, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, P.cap_d3, e->d3,
+                    d3_params(opt), opt->d3_cutoff, N, W.d3xs, W.d3w, W.dEdcn, W.ecoul, W.fgrad, W.virial_atom,
+                    P.lr_term == LongRange::DsfInD3, cp, q_fin, W.qbar, P.d3_cn_rides, dd));
+  if (grad && nq == 2) RC(launch_copy_f32(s, W.qbar, W.qbar + N, (size_t)N));  // dE/dq_alpha = dE/dq_beta = dE/dq at this point
+  if (dd) {  // halo copies: no energy, no Coulomb adjoint / direct force, no backward seed (model.hip, dd_mask_kernel)
+    const int nlp = (int)e->mlp[np - 1].size();
+    const int seed_bytes = P.head_fused ? P.layout.split_planes * e->mlp[np - 1][nlp - 1].k_out * 2 : e->head[e->head.size() - 2].k_out * 4;
+    RC(launch_dd_mask(s, dd->owned, in->numbers, e->sae, W.e_atom, W.ecoul, grad ? W.qbar : nullptr, nq, grad ? W.fgrad : nullptr,
+                      want_s ? W.virial_atom : nullptr, grad ? W.zb0 : nullptr, seed_bytes, N));
+  }
+  return 0;
+}
+
+// The results of the Coulomb block (ecoul, qbar / fgrad / virial seeds, qtot) are first needed here (energy only) or in front of
+// the first conv backward.  The molecule energies are outputs only: where the plan lets their sums (and the copy of the charges)
+// ride on the launches of finalize, nothing is launched here.
+int Eval::join() {
+  RC(prof_mark(e, s, FAM_POINTWISE));
+  if (P.energy != EnergySum::OwnLaunch) return 0;
+  const PairMapRider pmap = pair_map();
+  return launch_energy_reduce(s, W.e_atom, W.ecoul, in->numbers, e->sae, W.nl.mol_start, n_mol, W.S, W.part, out->energy,
+                              q_fin, P.charges == ChargesBy::EnergyLaunch ? out->charges : nullptr, N,  // + the charges output
+                              P.rev_lookup == RevLookup::OnEnergyLaunch ? &pmap : nullptr,  // + the lookup of the reverse-pair map
+                              out->status + 6);
+}
+
+// backward of the unfused energy head: zb0 holds the seed written by the head rider; leaves the adjoint of the last MLP's output in
+// zcur, in the split form the MLP sweeps read (the fused head has left it in zb0 already)
+int Eval::head_bwd(float*& zcur, float*& znext) {
+  const int sfmt = P.layout.split_format;
+  const int nh = (int)e->head.size();
+  int ld = e->head[nh - 2].k_out;
+  RC(prof_mark(e, s, FAM_GEMM));
+  for (int l = nh - 2; l >= 0; --l) {
+    const Layer& L = e->head[l];
+    float* dprev = l > 0 ? W.hD[l - 1] : W.D[np - 1][e->mlp[np - 1].size() - 1];  // aim = GELU(z_last) of the last MLP
+    RC(mlp_gemm(e, s, dprev ? EPI_MUL : EPI_NONE, zcur, ld, L, false, 0, 0, N, L.k_in, L.k_out, nullptr, znext, dprev, L.k_in));
+    std::swap(zcur, znext);
+    ld = L.k_in;
+  }
+  if (sfmt == SPLIT_NONE) return 0;
+  // (the head runs on fp32 operands; its adjoint is split for the MLP backward)
+  if (sfmt == SPLIT_H2) RC(launch_split_h2(s, zcur, ld, N, ld, reinterpret_cast<unsigned short*>(znext), 2 * ld, H2_ACT));
+  else RC(launch_split_bf3(s, zcur, ld, N, ld, reinterpret_cast<unsigned short*>(znext), 3 * ld));
+  std::swap(zcur, znext);
+  return 0;
+}
+
+// NSE adjoint of pass p (the molecule sums of qbar . y, then the adjoint zbar of its MLP output into znext)
+int Eval::nse_bwd(int p, float* znext) {
+  const int sfmt = P.layout.split_format;
+  const std::vector<Layer>& Lq = e->mlp[p];
+  const int nlq = (int)Lq.size();
+  const float* y = W.H[p][nlq - 1];
+  const int ldy = Lq[nlq - 1].k_out;
+  const float* dlast = e->arch.last_linear[p] ? nullptr : W.D[p][nlq - 1];
+  RC(prof_mark(e, s, FAM_POINTWISE));
+  switch (P.nse) {
+    case NseAdjoint::Decomposed:  // domain decomposition: the adjoint sums run over every local atom and are all-reduced over the ranks
+      RC(launch_nse_bwd_reduce(s, W.qbar, y, ldy, nq, W.nl.mol_start, n_mol, N, 1, (float*)W.part));
+      if (dd->fn(dd->ctx, AIMNET_DD_SUM, W.part, (int64_t)nq * n_mol, (void*)s) != 0) {
+        set_last_error("eval: the domain-decomposition exchange function failed (NSE adjoint sums)");
+        return AIMNET_E_INVALID;
+      }
+      return launch_build_zbar(s, W.qbar, W.abar, y, ldy, dlast, W.Fm[p], W.Dm[p], (const float*)W.part, 1, mol_c, N, n_mol, 256, nq,
+                               p > 0, znext, W.qbar, sfmt, nullptr, dd->owned);
+    case NseAdjoint::Merged:  // small systems: the molecule sums inside build_zbar, one launch instead of two
+      RC(launch_build_zbar(s, W.qbar, W.abar, y, ldy, dlast, W.Fm[p], W.Dm[p], nullptr, 1, mol_c, N, n_mol, 256, nq, p > 0, znext,
+                           W.qbar2, sfmt, W.nl.mol_start));
+      std::swap(W.qbar, W.qbar2);
+      return 0;
+    case NseAdjoint::Sliced:
+      RC(launch_nse_bwd_reduce(s, W.qbar, y, ldy, nq, W.nl.mol_start, n_mol, N, W.S, (float*)W.part));
+      return launch_build_zbar(s, W.qbar, W.abar, y, ldy, dlast, W.Fm[p], W.Dm[p], (const float*)W.part, W.S, mol_c, N, n_mol, 256,
+                               nq, p > 0, znext, W.qbar, sfmt);
+  }
+  return 0;
+}
+
+int Eval::backward() {
+  const int cap = P.layout.cap, sfmt = P.layout.split_format;
+  const bool want_s = P.want_s, xe = P.layout.xe;
+  float* zcur = W.zb0;
+  float* znext = W.zb1;
+  if (!P.head_fused) RC(head_bwd(zcur, znext));
+  for (int p = np - 1; p >= 0; --p) {
+    const bool p0m = p == 0 && P.p0_moments;
+    const int ld = e->mlp[p][0].k_in;
+    // zcur = adjoint of the last layer's pre-activation (GELU' already applied) -> zcur = xbar_p (N x k_in of the first layer;
+    // pass-0 moments: only its conv columns 256.. are consumed - the embedding is a constant)
+    RC(prof_mark(e, s, FAM_GEMM));
+    RC(mlp_sweep_bwd(e, s, sfmt, p, N, p0m, zcur, znext, W.D[p], e->gemm_chain != 0));
+    // the conv backward below is the first consumer of the Coulomb block's qbar / dE/dx / virial seeds
+    if (p == np - 1) RC(join());
+    RC(prof_mark(e, s, FAM_UNCONCAT));
+    if (p0m) {
+      RC(launch_unconcat_p0(s, zcur, ld, W.V[0], e->agh_a, e->afv, e->z_of_slot, e->nslots, W.present_part, W.n_part, W.Sbar, N));
+      RC(prof_mark(e, s, FAM_CONV_BWD));
+      RC(launch_conv_bwd_p0(s, want_s, W.Sbar, e->nslots, W.aslot, W.nb_idx, W.nb_cnt, W.pg, cap, e->bp, W.fgrad, W.virial_atom, N,
+                            order, P.rev_hash ? W.pairbuf : nullptr));
+      break;
+    }
+    RC(launch_unconcat(s, p > 0 ? nq : 0, zcur, ld, W.V[p], W.Vq[p], e->agh_a, e->agh_q, W.Sbar, W.Sqbar, N));
+    RC(prof_mark(e, s, FAM_CONV_BWD));
+    RC(launch_conv_bwd(s, p > 0 ? nq : 0, p > 0, want_s, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr,
+                       p > 0 ? W.q[p - 1] : nullptr, W.Sbar, W.Sqbar, W.nb_idx, W.nb_cnt, W.pg, cap, e->bp, zcur, ld,
+                       (p < np - 1) ? W.abar : nullptr, W.abar, W.qbar, W.qbar, W.fgrad, W.virial_atom, N, order,
+                       (xe && p > 0) ? W.pairbuf : nullptr, p < np - 1, e->split_max));
+    if (p == 0) break;
+    RC(nse_bwd(p - 1, znext));
+    std::swap(zcur, znext);
+  }
+  return 0;
+}
+
+// forces, stress and whatever the plan deferred to these launches
+int Eval::finalize() {
+  const int cap = P.layout.cap;
+  RC(prof_mark(e, s, FAM_POINTWISE));
+  // reverse-pair form: the pair buffer holds F1 of both passes; its gather is the last contribution to dE/dx and writes the forces
+  // (with a stress request the force gather rides on the launch of the virial sums: independent work, one kernel boundary less)
+  const PairForceRider pfr{W.nb_idx, W.nb_cnt, W.rev, W.pairbuf, cap, out->forces, ceil_div(N, 4)};
+  const EnergyRider erd{W.e_atom, W.ecoul, in->numbers, e->sae, W.part_e, out->energy, n_mol,
+                        q_fin, P.charges == ChargesBy::ForceRider ? out->charges : nullptr, N};
+  if (P.rev_hash && !P.pair_force_rides)
+    RC(launch_pair_force(s, W.nb_idx, W.nb_cnt, W.rev, W.pairbuf, cap, N, W.fgrad, out->forces, out->status + 6));
+  // (domain decomposition: no cell - the virial sums are divided by the volume of a unit cube, i.e. the `stress` output takes the
+  // rank's share of dE/d(strain) itself; the caller adds the ranks' shares and divides by the cell volume)
+  return launch_finalize(s, W.fgrad, W.virial_atom, W.nl.mol_start, dd ? e->unit_cell : in->cell, dd ? 1 : n_cell, n_mol, N,
+                         W.S, W.part, (P.want_f && !P.layout.xe) ? out->forces : nullptr, P.want_s ? out->stress : nullptr,
+                         P.pair_force_rides ? &pfr : nullptr, P.energy != EnergySum::OwnLaunch ? &erd : nullptr, e->sums_whole != 0,
+                         out->status + 6);
+}
+
+// the plain values eval_plan.h works on
+LayoutRequest layout_request(const aimnet_engine* e, int N, int n_mol, const aimnet_eval_options* opt) {
+  LayoutRequest r{};
+  r.N = N; r.n_mol = n_mol; r.n_pass = e->arch.n_pass;
+  r.flags = opt->flags; r.coulomb = opt->coulomb; r.dftd3 = opt->dftd3;
+  r.d3_same_cutoff = opt->d3_cutoff == opt->dsf_rc;
+  r.max_nb = opt->max_nb; r.max_nb_lr = opt->max_nb_lr; r.max_nb_d3 = opt->max_nb_d3;
+  r.ewald_max_k = opt->ewald_max_k; r.pme_max_mesh = opt->pme_max_mesh;
+  r.ewald_kb = EWALD_KB; r.pme_part = PME_PART;
+  r.conv_xe = e->conv_xe; r.split_max = e->split_max;
+  r.pair_rev_ok = pair_rev_supported(N, std::max(1, opt->max_nb));
+  r.split_format = split_format(e, N);
+  r.split_planes = split_planes(r.split_format);
+  return r;
+}
+EvalRequest eval_request(const aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const aimnet_outputs* out) {
+  EvalRequest r{};
+  const int N = in->n_atoms, n_mol = in->n_mol;
+  r.L = layout_request(e, N, n_mol, opt);
+  r.pbc = in->cell != nullptr;
+  r.n_cell = in->n_cell; r.nq = e->nq;
+  r.has_stress_out = out->stress != nullptr; r.has_forces_out = out->forces != nullptr; r.has_spin_out = out->spin_charges != nullptr;
+  r.ewald_args = (opt->coulomb == AIMNET_COULOMB_EWALD || opt->coulomb == AIMNET_COULOMB_PME) ? ewald_args_check(in, opt) : 0;
+  r.nbmat = in->nbmat != nullptr; r.shifts = in->shifts != nullptr;
+  r.nbmat_lr = in->nbmat_lr != nullptr; r.shifts_lr = in->shifts_lr != nullptr;
+  r.nbmat_d3 = in->nbmat_d3 != nullptr; r.shifts_d3 = in->shifts_d3 != nullptr;
+  r.nbmat_width = in->nbmat_width; r.nbmat_lr_width = in->nbmat_lr_width; r.nbmat_d3_width = in->nbmat_d3_width;
+  r.dd = e->dd.owned != nullptr;
+  r.d3_tables = e->d3.ns != 0;
+  r.prep_fused = e->prep_fused; r.energy_rides = e->energy_rides; r.status_rides = e->status_rides; r.setup_rides = e->setup_rides;
+  r.status_owned = e->status_owned; r.nse_merged = e->nse_merged; r.d3_cn_rides = e->d3_cn_rides; r.dsf_np_walk = e->dsf_np_walk;
+  r.p0_moments = e->p0_moments; r.spatial_order = e->spatial_order;
+  r.prep_small_ok = prep_small_applies(N, n_mol, r.pbc);
+  r.cell_setup_ok = cell_setup_rides(N, n_mol);
+  r.bbox_ok = bbox_applies(N, n_mol);
+  r.head_fusable = head_fusable(e);
+  return r;
 }
 
 }  // namespace
@@ -709,13 +1095,6 @@ int aimnet_engine_create(const aimnet_arch* arch, const aimnet_weights* w, int d
   if ((rc = gemm_set_attributes())) goto fail;
   if ((rc = gemm_bf3_set_attributes())) goto fail;
   if ((rc = gemm_split_set_attributes())) goto fail;  // AIMNET_BF3A_TILE / AIMNET_H2_TILE / AIMNET_H2_DEEP (gemm_h2.hip)
-  if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) {
-    set_last_error("engine_create: cannot create the side stream / events");
-    rc = AIMNET_E_HIP;
-    goto fail;
-  }
   *out = e;
   return AIMNET_OK;
 fail:
@@ -727,9 +1106,6 @@ void aimnet_engine_destroy(aimnet_engine* e) {
   if (!e) return;
   for (void* p : e->allocs) (void)hipFree(p);
   for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-  if (e->side) (void)hipStreamDestroy(e->side);
   delete e;
 }
 
@@ -857,7 +1233,7 @@ size_t aimnet_engine_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, in
   (void)n_cell;
   if (!e || !opt || n_atoms <= 0 || n_mol <= 0) return 0;
   Workspace W;
-  layout(e, n_atoms, n_mol, opt, nullptr, W, nullptr);
+  layout(e, n_atoms, n_mol, opt, layout_plan(layout_request(e, n_atoms, n_mol, opt)), nullptr, W, nullptr);
   return W.total;
 }
 
@@ -873,12 +1249,6 @@ int aimnet_engine_debug_view(const aimnet_engine* e, const char* name, size_t* b
   return AIMNET_OK;
 }
 
-#define RC(call)            \
-  do {                      \
-    int _rc = (call);       \
-    if (_rc) return _rc;    \
-  } while (0)
-
 int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt,
                        const aimnet_outputs* out, void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!e || !in || !opt || !out || !workspace) return AIMNET_E_INVALID;
@@ -888,557 +1258,41 @@ int aimnet_engine_eval(aimnet_engine* e, const aimnet_inputs* in, const aimnet_e
     set_last_error("eval: null or empty input/output");
     return AIMNET_E_INVALID;
   }
-  const bool want_f = (opt->flags & AIMNET_FORCES) != 0, want_s = (opt->flags & AIMNET_STRESS) != 0;
-  const bool grad = want_f || want_s;
-  const bool pbc = in->cell != nullptr;
-  if (want_s && ((!pbc && !e->dd.owned) || !out->stress)) {  // (domain decomposition: the rank's virial, see aimnet_engine_set_dd)
-    set_last_error("eval: stress requires a cell and a stress buffer");
-    return AIMNET_E_INVALID;
-  }
-  if (want_f && !out->forces) {
-    set_last_error("eval: forces requested without a forces buffer");
-    return AIMNET_E_INVALID;
-  }
-  const int nq = e->nq;
-  if (nq == 1 && out->spin_charges) {
-    set_last_error("eval: spin_charges requested from a 1-channel (closed-shell) model");
-    return AIMNET_E_INVALID;
-  }
-  if (pbc && !(in->n_cell == 1 || in->n_cell == n_mol)) {
-    set_last_error("eval: n_cell must be 1 or n_mol");
-    return AIMNET_E_INVALID;
-  }
-  int coulomb = opt->coulomb;
-  // large non-periodic systems get a bounding-box cell grid (launch_bbox below): DSF walks it like a periodic cell's grid, no matrix
-  const bool np_walk = e->dsf_np_walk && !pbc && in->nbmat == nullptr && coulomb == AIMNET_COULOMB_DSF && (long)N >= 1500L * n_mol &&
-                       !(opt->dftd3 != 0 && opt->d3_cutoff == opt->dsf_rc);
-  if (coulomb == AIMNET_COULOMB_DSF && !pbc && opt->max_nb_lr <= 0 && !np_walk) {
-    set_last_error("eval: non-periodic DSF Coulomb needs max_nb_lr > 0 (periodic DSF walks the cell grid, no list)");
-    return AIMNET_E_INVALID;
-  }
-  if (coulomb == AIMNET_COULOMB_SIMPLE && pbc) {
-    set_last_error("eval: 'simple' Coulomb is undefined for periodic input (host must switch to DSF, calculator.py:1044)");
-    return AIMNET_E_INVALID;
-  }
-  if (coulomb == AIMNET_COULOMB_EWALD || coulomb == AIMNET_COULOMB_PME) {
-    if (!pbc || in->pbc_sys || !(in->pbc[0] && in->pbc[1] && in->pbc[2])) {
-      set_last_error("eval: Ewald summation needs a cell that is periodic along all three axes (lr.py:655-657)");
-      return AIMNET_E_INVALID;
-    }
-    if (in->nbmat) {
-      set_last_error("eval: Ewald summation walks the engine's own cell grid: caller-supplied neighbour matrices are not taken with it "
-                     "(the reference builds its own per-call list for this method too, calculator.py:1560-1603)");
-      return AIMNET_E_INVALID;
-    }
-    if (!(opt->ewald_accuracy > 0.0f && opt->ewald_accuracy < 1.0f) ||
-        (coulomb == AIMNET_COULOMB_EWALD ? opt->ewald_max_k < EWALD_KB : opt->pme_max_mesh < 512)) {
-      set_last_error("eval: Ewald summation needs 0 < ewald_accuracy < 1 and ewald_max_k >= %d (PME: pme_max_mesh >= 512)", EWALD_KB);
-      return AIMNET_E_INVALID;
-    }
-  }
-  // caller-supplied neighbour matrices (aimnet_inputs.nbmat ...): no list is built, the coordinates are taken as given
-  const bool ext = in->nbmat != nullptr;
-  if (ext) {
-    if (in->nbmat_width <= 0 || opt->max_nb < in->nbmat_width) {
-      set_last_error("eval: caller-supplied nbmat needs 0 < nbmat_width <= options.max_nb (got %d, %d)", in->nbmat_width, opt->max_nb);
-      return AIMNET_E_INVALID;
-    }
-    if (pbc && !in->shifts) {
-      set_last_error("eval: a caller-supplied nbmat of a periodic system needs its shifts");
-      return AIMNET_E_INVALID;
-    }
-    if (in->nbmat_lr && (in->nbmat_lr_width <= 0 || opt->max_nb_lr < in->nbmat_lr_width || (pbc && !in->shifts_lr))) {
-      set_last_error("eval: caller-supplied nbmat_lr needs 0 < nbmat_lr_width <= options.max_nb_lr, and shifts_lr when periodic");
-      return AIMNET_E_INVALID;
-    }
-    if (coulomb == AIMNET_COULOMB_DSF && !in->nbmat_lr) {
-      set_last_error("eval: DSF Coulomb with a caller-supplied nbmat needs nbmat_lr as well (no list is built in this mode)");
-      return AIMNET_E_INVALID;
-    }
-    if (opt->dftd3 != 0) {
-      const bool own = in->nbmat_d3 != nullptr;
-      if (!own && !in->nbmat_lr) {
-        set_last_error("eval: DFT-D3 with a caller-supplied nbmat needs nbmat_d3 or nbmat_lr");
-        return AIMNET_E_INVALID;
-      }
-      if (own && (in->nbmat_d3_width <= 0 || (pbc && !in->shifts_d3))) {
-        set_last_error("eval: caller-supplied nbmat_d3 needs a width, and shifts_d3 when periodic");
-        return AIMNET_E_INVALID;
-      }
-    }
-  } else if (in->nbmat_lr || in->nbmat_d3) {
-    set_last_error("eval: nbmat_lr / nbmat_d3 are only read together with nbmat");
-    return AIMNET_E_INVALID;
-  }
-  // spatial domain decomposition (aimnet_engine_set_dd): the local cluster of owned + halo atoms is a non-periodic system
-  const aimnet::DdLink* dd = e->dd.owned ? &e->dd : nullptr;
-  if (dd && (pbc || ext || !(coulomb == AIMNET_COULOMB_NONE || coulomb == AIMNET_COULOMB_DSF))) {
-    set_last_error("eval: a domain-decomposed evaluation takes a non-periodic cluster (no cell, no caller-supplied lists), Coulomb "
-                   "'none' or 'dsf'");
-    return AIMNET_E_INVALID;
-  }
+  // validate, plan, lay out
+  const EvalRequest rq = eval_request(e, in, opt, out);
+  RC(eval_validate(rq, g_err, sizeof(g_err)));
+  const EvalPlan P = eval_plan(rq);
   hipStream_t s = (hipStream_t)hip_stream;
   AIMNET_HIP_CHECK(hipSetDevice(e->device));
   Workspace W;
   e->views.clear();
-  layout(e, N, n_mol, opt, (char*)workspace, W, &e->views);
+  layout(e, N, n_mol, opt, P.layout, (char*)workspace, W, &e->views);
   if (W.total > workspace_bytes) {
     set_last_error("eval: workspace too small (%zu < %zu)", workspace_bytes, W.total);
     return AIMNET_E_WORKSPACE;
   }
-  const aimnet_arch& ar = e->arch;
-  const int np = ar.n_pass;
-  const int cap = std::max(1, opt->max_nb), cap_lr = std::max(0, opt->max_nb_lr);
-  const int n_cell = pbc ? in->n_cell : 0;
+  RC(eval_validate_lists(rq, P.layout, g_err, sizeof(g_err)));
+  const int np = e->arch.n_pass;
+  Eval ev{e, s, in, opt, out, W, P, N, n_mol, rq.pbc ? in->n_cell : 0, np, e->nq, rq.pbc, rq.dd ? &e->dd : nullptr,
+          W.nl.mol_c, P.bin_order ? W.nl.sorted : nullptr, e->nq == 2 ? W.qtot : W.q[np - 2]};
 
-  // ---- neighbour lists + pair geometry ------------------------------------------------------
   e->prof_on = e->prof_level > 0 && (e->prof_evals++ % e->prof_every) == 0;
   if (e->prof_on) e->prof_sampled++;
   RC(prof_mark(e, s, FAM_NLIST));
-  const bool want_species = (e->p0_moments && (opt->flags & (AIMNET_FORCES | AIMNET_STRESS))) || opt->dftd3 != 0;
-  // small periodic batches: status zeroing, molecule offsets / sanity / species, cell + bin setup, wrapping and binning in one launch
-  const bool prep1 = e->prep_fused && !ext && prep_small_applies(N, n_mol, pbc);
-  bool setup_rides = false, status_owned = false;
-  if (prep1) {
-    RC(launch_prep_small(s, in->coord, in->mol_idx, in->numbers, N, n_mol, pbc ? in->cell : nullptr, n_cell, in->pbc, in->pbc_sys, ar.rc,
-                         out->status,
-                         want_species ? e->slot_of_z : nullptr, W.aslot, W.present_part, W.nl));
-  } else {
-    // One list, its status words reduced by a rider of the SR-Coulomb launch: that rider can just as well STORE all eight status
-    // words (with the sanity flags of the launch below collected per wave), and nothing has to be zeroed in front of the evaluation.
-    const bool one_list = !ext && !(coulomb == AIMNET_COULOMB_DSF && !pbc) && opt->dftd3 == 0;
-    status_owned = e->status_rides && e->status_owned && one_list && N <= 32768;
-    if (!status_owned) AIMNET_HIP_CHECK(hipMemsetAsync(out->status, 0, 8 * sizeof(int), s));
-    // periodic fast path: the cell + bin-grid setup block rides on this launch (it needs none of its output)
-    setup_rides = e->setup_rides && !ext && pbc && cell_setup_rides(N, n_mol);
-    CellSetupRider csr{};
-    if (setup_rides) csr = cell_setup_rider(in->cell, n_cell, in->pbc, in->pbc_sys, ar.rc, N, n_mol, W.nl);
-    RC(launch_mol_start(s, in->mol_idx, N, n_mol, W.nl.mol_start, W.nl.mol_c, in->numbers, out->status + 6,
-                        want_species ? e->slot_of_z : nullptr, W.aslot, W.present_part,  // + aslot / present species
-                        setup_rides ? &csr : nullptr, status_owned ? W.bad_part : nullptr));
-  }
-  const int* mol_c = W.nl.mol_c;  // clamped to [0, n_mol): memory-safe whatever the caller passed (status[6] reports it)
-  const bool d3 = opt->dftd3 != 0;
-  if (d3 && e->d3.ns == 0) {
-    set_last_error("eval: DFT-D3 requested but aimnet_engine_set_dftd3 was never called");
-    return AIMNET_E_INVALID;
-  }
-  int cap_d3 = cap_lr;
-  bool d3_shared = false, d3_cn_done = false;
-  const int* sr_cnt_true = nullptr;  // != NULL: the short-range list's status words are still to be reduced (SrRiders)
-  if (ext) {
-    // the reference hands a caller's matrices to the model as they are (calculator.py:1069-1071): import them into the row format
-    // of the kernels; coordinates as given (the shifts refer to them), no bins, centres processed in input order
-    RC(launch_wrap(s, in->coord, mol_c, N, n_mol, nullptr, 0, in->pbc, W.nl));
-    RC(launch_import_list(s, in->nbmat, pbc ? in->shifts : nullptr, in->nbmat_width, N, mol_c, in->cell, n_cell, cap, W.nl, W.nb_idx,
-                          W.nb_shift, W.nb_cnt, out->status + 0, out->status + 2, W.pg, out->status + 6));
-    RC(launch_list_symmetry_check(s, W.nb_idx, pbc ? W.nb_shift : nullptr, W.nb_cnt, cap, N, out->status + 6));
-    if (in->nbmat_lr && coulomb != AIMNET_COULOMB_NONE) {
-      RC(launch_import_list(s, in->nbmat_lr, pbc ? in->shifts_lr : nullptr, in->nbmat_lr_width, N, mol_c, in->cell, n_cell, cap_lr, W.nl,
-                            W.lr_idx, W.lr_shift, W.lr_cnt, out->status + 1, out->status + 3, nullptr, out->status + 6));
-      // (the bin-ordered coordinate stream of the list builder is unused with caller-supplied matrices: 16 bytes per atom of scratch)
-      RC(launch_list_symmetry_check(s, W.lr_idx, pbc ? W.lr_shift : nullptr, W.lr_cnt, cap_lr, N, out->status + 6, 64,
-                                    (unsigned long long*)W.nl.xs));
-    }
-    if (d3) {
-      d3_shared = d3_shares_lr_list(opt, cap_lr);  // one cutoff for both: the layout stores ONE matrix
-      const int* src = in->nbmat_d3 ? in->nbmat_d3 : in->nbmat_lr;
-      const int* src_sh = in->nbmat_d3 ? in->shifts_d3 : in->shifts_lr;
-      const int src_w = in->nbmat_d3 ? in->nbmat_d3_width : in->nbmat_lr_width;
-      if (d3_shared) {
-        if (src != in->nbmat_lr) {
-          set_last_error("eval: with d3_cutoff == dsf_rc one caller-supplied matrix serves both terms: pass it as nbmat_lr only");
-          return AIMNET_E_INVALID;
-        }
-      } else {
-        cap_d3 = std::max(1, opt->max_nb_d3);
-        if (cap_d3 < src_w) {
-          set_last_error("eval: options.max_nb_d3 (%d) is smaller than the caller-supplied D3 matrix (%d)", cap_d3, src_w);
-          return AIMNET_E_INVALID;
-        }
-        RC(launch_import_list(s, src, pbc ? src_sh : nullptr, src_w, N, mol_c, in->cell, n_cell, cap_d3, W.nl, W.d3_idx, W.d3_shift,
-                              W.d3_cnt, out->status + 4, out->status + 5, nullptr, out->status + 6));
-        RC(launch_list_symmetry_check(s, W.d3_idx, pbc ? W.d3_shift : nullptr, W.d3_cnt, cap_d3, N, out->status + 6, 64,
-                                      (unsigned long long*)W.nl.xs));
-      }
-    }
-  } else {
-  if (!prep1) RC(launch_wrap(s, in->coord, mol_c, N, n_mol, in->cell, n_cell, in->pbc, W.nl, in->pbc_sys, pbc ? ar.rc : 0.0f, setup_rides));
-  // large non-periodic molecules (>= 1500 atoms on average) get a bounding-box cell list instead of the O(n^2) scan
-  if (!pbc && (long)N >= 1500L * n_mol) RC(launch_bbox(s, n_mol, W.nl));
-  // no second list build follows (periodic DSF walks the grid, "simple" sums all pairs, no D3 list): the status words of this list
-  // are reduced by rider blocks of the SR-Coulomb launch instead of a launch of their own
-  const bool status_rides = e->status_rides && !(coulomb == AIMNET_COULOMB_DSF && !pbc) && !d3;
-  RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, ar.rc, ar.rc, cap, N, 0, W.nl, W.nb_idx, W.nb_shift,
-                  W.nb_cnt, out->status + 0, out->status + 2, W.pg, status_rides ? &sr_cnt_true : nullptr));
-  if (coulomb == AIMNET_COULOMB_DSF && !pbc && !np_walk)  // periodic DSF (and large non-periodic systems) need no list: they walk the short-range cell grid
-    RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->dsf_rc, -1.0f, cap_lr, N, 0, W.nl, W.lr_idx,
-                    W.lr_shift, W.lr_cnt, out->status + 1, out->status + 3));
-  d3_shared = d3 && d3_shares_lr_list(opt, cap_lr) && !pbc;
-  if (d3 && !d3_shared) {
-    D3CnRider cnr;  // the coordination numbers ride on the (cell-grid) build of the D3 matrix
-    if (e->d3_cn_rides) {
-      cnr.aslot = W.aslot; cnr.rcov = e->d3.rcov; cnr.nref = e->d3.nref; cnr.cnref = e->d3.cnref; cnr.d3w = W.d3w;
-    }
-    if (d3_shares_lr_list(opt, cap_lr)) {  // periodic DSF walks the grid: the shared buffers are free for the D3 list
-      RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->d3_cutoff, -1.0f, cap_lr, N, 0, W.nl, W.d3_idx,
-                      W.d3_shift, W.d3_cnt, out->status + 4, out->status + 5, nullptr, nullptr, &cnr, &d3_cn_done));
-    } else {
-      cap_d3 = std::max(1, opt->max_nb_d3);
-      RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->d3_cutoff, -1.0f, cap_d3, N, 0, W.nl, W.d3_idx,
-                      W.d3_shift, W.d3_cnt, out->status + 4, out->status + 5, nullptr, nullptr, &cnr, &d3_cn_done));
-    }
-  }
-  }
+  RC(ev.prepare());
+  RC(P.ext ? ev.lists_imported() : ev.lists_built());
   RC(prof_mark(e, s, FAM_GEOM));
-  // (the pair geometry (u, d) of the short-range list was written by the list builder itself)
-
-  // ---- forward --------------------------------------------------------------------------------
-  // binned systems: process centre atoms in the bin-sorted order of the cell list (kernels.h, `order`)
-  const int* order = (!ext && W.nl.binned && e->spatial_order) ? W.nl.sorted : nullptr;
-  // a^0 = afv[Z] is never materialised: pass 0 gathers the embedding rows directly (conv_fwd / conv_bwd row_of, update_a)
-  const bool p0m = e->p0_moments && (opt->flags & (AIMNET_FORCES | AIMNET_STRESS));
-  const int sfmt = split_format(e, N);  // GEMM activations in split form: SPLIT_BF3 bf16x3 (gemm_bf3a.hip), SPLIT_H2 fp16x2 (gemm_h2.hip)
-  const bool ps = sfmt != SPLIT_NONE;
-  const int pm = split_planes(sfmt);  // 16-bit elements per fp32 value of a split row
-  const bool hfused = ps && head_fusable(e);  // energy head forward + backward in one launch (gemm_head.hip)
-  // reverse-pair map through per-atom hash tables of the rows (once per neighbour list)
-  // (its only reader is launch_pair_force, the last kernel of the backward.  On one stream the two small kernels ride on later
-  // launches instead of standing in front of the forward pass: the hash build on the SR-Coulomb launch, the lookup on the DSF walk
-  // (VALU-bound, the lookup is latency-bound) or else on the energy reduction - kernels.h PairMapRider)
-  PairMapRider pmap{};
-  const bool overlap_early = e->overlap_coulomb && e->prof_level < 2 && !dd;
-  if (W.xe && want_f) {
-    if (overlap_early) {
-      RC(launch_pair_rev_hash(s, W.nb_idx, n_cell > 0 ? W.nb_shift : nullptr, W.nb_cnt, cap, N, W.rev_tab, W.rev));
-    } else {
-      pmap = PairMapRider{W.nb_idx, n_cell > 0 ? W.nb_shift : nullptr, W.nb_cnt, cap, N, W.rev_tab, W.rev, ceil_div(N, 4)};
-    }
+  RC(ev.forward());
+  SrRiders head_rider{};  // the last energy-head layer, unless the head is fused
+  RC(ev.head(head_rider));
+  RC(prof_mark(e, s, FAM_COULOMB));
+  RC(ev.coulomb(head_rider));
+  if (P.grad) {
+    RC(ev.backward());  // (runs join() in front of its first conv backward)
+    RC(ev.finalize());
+  } else {
+    RC(ev.join());
   }
-  bool rev_done = pmap.n_blocks == 0;
-  // ---- Coulomb: energies, and the seeds of qbar / dE/dx / virial (a closure: it runs on the eval stream or on the side one) ----
-  const float* q_fin = nq == 2 ? W.qtot : W.q[np - 2];
-  const bool overlap = e->overlap_coulomb && e->prof_level < 2 && !dd;  // per-family profiling wants one stream
-  bool charges_written = false;  // the DSF walk's charge stream kernel copies q to the `charges` output on its way
-  SrRiders head_rider{};  // the last energy-head layer rides on the SR-Coulomb launch (filled in below when both run on one stream)
-  auto coulomb_block = [&](hipStream_t cs) -> int {
-    if (nq == 2)  // NSE: alpha + beta is the charge everything downstream sees (aimnet2.py:102-106)
-      RC(launch_charge_sum(cs, W.q[np - 2], N, W.qtot, out->spin_charges));
-    CoulombParams cp;
-    cp.factor = (float)(0.5 * 27.211386024367243 * 0.5291772105638411);
-    cp.sr_rc = ar.sr_rc;
-    cp.sr_envelope = ar.sr_envelope;
-    cp.dsf_rc = opt->dsf_rc;
-    cp.dsf_alpha = opt->dsf_alpha;
-    const bool pme = coulomb == AIMNET_COULOMB_PME;
-    const bool ewald = coulomb == AIMNET_COULOMB_EWALD || pme;  // (the real-space walk and the self term are the same)
-    if (pme) {  // per-system (alpha, rc, mesh) from the cell, fractional coordinates in double (pme.hip)
-      RC(launch_pme_setup(cs, in->cell, n_cell, W.nl.mol_start, in->charge, nq, n_mol, opt->ewald_accuracy, W.ew, out->status + 7));
-      cp.ewald = W.ew.sys;
-    } else if (ewald) {  // per-system (alpha, rc, kc) and k boxes from the cell, fractional coordinates in double (ewald.hip)
-      RC(launch_ewald_setup(cs, in->cell, n_cell, W.nl.mol_start, mol_c, W.nl.xw, in->charge, nq, N, n_mol, opt->ewald_accuracy, W.ew,
-                            out->status + 7));
-      cp.ewald = W.ew.sys;
-    }
-    const bool walk = ewald || np_walk || (coulomb == AIMNET_COULOMB_DSF && pbc && !ext &&
-                                           !(d3 && opt->d3_cutoff == opt->dsf_rc));  // the list-free walk runs below: its charge stream rides here
-    SrRiders rd = head_rider;
-    if (walk) {
-      rd.xs = W.nl.xs;
-      rd.xq = (float4*)W.nl.sorted_tmp_xq;
-      rd.charges_out = out->charges;
-      rd.n_stream_blocks = ceil_div(N, 256);
-    }
-    const bool simple_all = coulomb == AIMNET_COULOMB_SIMPLE && !(ext && in->nbmat_lr);  // all pairs of the molecule: same waves
-    if (simple_all) {
-      rd.simple_xw = W.nl.xw;
-      rd.simple_mol_idx = mol_c;
-      rd.simple_mol_start = W.nl.mol_start;
-    }
-    rd.hash = pmap;  // hash build of the reverse-pair map (n_blocks = 0: none)
-    if (sr_cnt_true) {
-      rd.cnt_true = sr_cnt_true;
-      rd.status_cap = cap;
-      rd.status_max = out->status + 0;
-      rd.status_ovf = out->status + 2;
-      rd.n_status_blocks = ceil_div(N, 1024);
-      if (status_owned) {
-        rd.n_status_blocks = 1;
-        rd.status_all = out->status;
-        rd.bad_part = W.bad_part;
-        rd.keep7 = ewald ? 1 : 0;
-      }
-    }
-    RC(launch_coulomb_sr(cs, grad, want_s, ar.sr_coulomb != 0, q_fin, W.nb_idx, W.nb_cnt, W.pg, cap, cp, N, W.ecoul, W.qbar,
-                         W.fgrad, W.virial_atom, &rd));
-    // DSF and DFT-D3 with one cutoff: the Coulomb pair terms ride on the D3 pair pass (one list, one geometry evaluation)
-    const bool dsf_in_d3 = !ext && d3 && coulomb == AIMNET_COULOMB_DSF && opt->d3_cutoff == opt->dsf_rc;
-    if (coulomb == AIMNET_COULOMB_SIMPLE && ext && in->nbmat_lr)  // coul_simple over the caller's matrix (lr.py:311-331)
-      RC(launch_coulomb_dsf(cs, grad, false, q_fin, W.nl.xw, mol_c, in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, cp, N,
-                            W.ecoul, W.qbar, W.fgrad, W.virial_atom, true));
-    else if (coulomb == AIMNET_COULOMB_SIMPLE)
-      ;  // ran inside the SR-Coulomb launch above (SrRiders::simple_xw)
-    else if (dsf_in_d3)
-      ;  // see launch_dftd3 below
-    else if (ewald || np_walk || (coulomb == AIMNET_COULOMB_DSF && pbc && !ext)) {
-      RC(launch_coulomb_dsf_walk(cs, grad, want_s, q_fin, mol_c, W.nl, cp, N, W.ecoul, W.qbar, W.fgrad, W.virial_atom,
-                                 out->charges, true, rev_done ? nullptr : &pmap));
-      rev_done = true;
-      charges_written = true;
-      if (pme)  // reciprocal space on the mesh + neutralising background (pme.hip)
-        RC(launch_pme_recip(cs, grad, want_s, W.nl.xw, q_fin, mol_c, W.nl.mol_start, order, N, n_mol, W.ew, cp.factor, W.ecoul, W.qbar, W.fgrad,
-                            W.virial_atom));
-      else if (ewald)  // reciprocal space + neutralising background, accumulated onto what the pair kernels have stored
-        RC(launch_ewald_recip(cs, grad, want_s, q_fin, mol_c, W.nl.mol_start, N, n_mol, W.ew, cp.factor, W.ecoul, W.qbar, W.fgrad,
-                              W.virial_atom));
-    } else if (coulomb == AIMNET_COULOMB_DSF)
-      RC(launch_coulomb_dsf(cs, grad, want_s, q_fin, W.nl.xw, mol_c, in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt,
-                            cap_lr, cp, N, W.ecoul, W.qbar, W.fgrad, W.virial_atom));
-    if (d3) {  // external DFT-D3: adds to the per-atom pair energies, dE/dx and the virial seeded by the Coulomb kernels
-      D3Params dp;
-      dp.s6 = opt->d3_s6; dp.s8 = opt->d3_s8; dp.a1 = opt->d3_a1; dp.a2 = opt->d3_a2;
-      dp.r_on = opt->d3_smoothing_on * 1.8897261258369282f;
-      dp.r_off = opt->d3_cutoff * 1.8897261258369282f;
-      RC(launch_dftd3(cs, grad, want_s, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3,
-                      e->d3, dp, opt->d3_cutoff, N, W.d3xs, W.d3w, W.dEdcn, W.ecoul, W.fgrad, W.virial_atom, dsf_in_d3, cp, q_fin,
-                      W.qbar, d3_cn_done, dd));
-    }
-    if (grad && nq == 2) RC(launch_copy_f32(cs, W.qbar, W.qbar + N, (size_t)N));  // dE/dq_alpha = dE/dq_beta = dE/dq at this point
-    return 0;
-  };
-
-  for (int p = 0; p < np; ++p) {
-    const std::vector<Layer>& Ls = e->mlp[p];
-    const int nl = (int)Ls.size();
-    RC(prof_mark(e, s, FAM_CONV_FWD));
-    RC(launch_conv_fwd(s, p > 0 ? nq : 0, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr, p > 0 ? W.q[p - 1] : nullptr,
-                       W.nb_idx, W.nb_cnt, W.pg, cap, e->agh_a, e->agh_q, e->bp, W.x[p], Ls[0].k_in, W.V[p], W.Vq[p], N, order,
-                       p == 0 && e->p0_moments, e->split_max, sfmt));
-    const float* hin = W.x[p];
-    int ld_in = Ls[0].k_in;
-    RC(prof_mark(e, s, FAM_GEMM));
-    if (ps) {  // activations in split form: one launch per MLP (gemm_chain.hip) or one per layer
-      RC(mlp_sweep_fwd(e, s, sfmt, p, N, in->numbers, W.x[p], W.H[p], W.D[p], hfused && p == np - 1, e->gemm_chain != 0));
-    } else
-    for (int l = 0; l < nl; ++l) {
-      const bool linear = (l == nl - 1) && ar.last_linear[p];
-      if (p == 0 && l == 0 && e->emb_bias && e->emb_bias0)  // embedding columns folded into the per-element bias table
-        RC(mlp_gemm(e, s, linear ? EPI_BIAS : EPI_BIAS_GELU, hin + 256, ld_in, Ls[l], true, 256, 0, N, Ls[l].k_out, Ls[l].k_in - 256,
-                    e->emb_bias0, W.H[p][l], linear ? nullptr : W.D[p][l], Ls[l].k_out, in->numbers, Ls[l].k_out));
-      else
-        RC(mlp_gemm(e, s, linear ? EPI_BIAS : EPI_BIAS_GELU, hin, ld_in, Ls[l], true, 0, 0, N, Ls[l].k_out, Ls[l].k_in, Ls[l].b,
-                    W.H[p][l], linear ? nullptr : W.D[p][l], Ls[l].k_out));
-      hin = W.H[p][l];
-      ld_in = Ls[l].k_out;
-    }
-    if (p < np - 1) {
-      RC(prof_mark(e, s, FAM_POINTWISE));
-      // (the feature update a^{p+1} = a^p + delta_a rides on the NSE launch: independent work, one kernel boundary less)
-      RC(launch_nse_fwd(s, W.H[p][nl - 1], Ls[nl - 1].k_out, nq, p > 0 ? W.q[p - 1] : nullptr, W.nl.mol_start, in->charge,
-                        n_mol, N, W.S, (float*)W.part, W.q[p], W.Fm[p], W.Dm[p], p == 0 ? e->afv : W.a[p],
-                        p == 0 ? in->numbers : nullptr, W.a[p + 1], dd));
-      // domain decomposition: the final charges of halo copies are exact only within one cutoff of the owned region, the Coulomb
-      // sums reach further - the owners' values come in through the exchange function
-      if (dd && p == np - 2 && dd->fn(dd->ctx, AIMNET_DD_CHARGES, W.q[p], (int64_t)nq * N, (void*)s) != 0) {
-        set_last_error("eval: the domain-decomposition exchange function failed (charges)");
-        return AIMNET_E_INVALID;
-      }
-      if (p == np - 2 && overlap) {  // the final charges exist: the Coulomb block starts on the side stream
-        AIMNET_HIP_CHECK(hipEventRecord(e->ev_fork, s));
-        AIMNET_HIP_CHECK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-        RC(coulomb_block(e->side));
-        AIMNET_HIP_CHECK(hipEventRecord(e->ev_join, e->side));
-      }
-    }
-  }
-  {
-    const int nlp = (int)e->mlp[np - 1].size();
-    const float* hin = W.H[np - 1][nlp - 1];
-    int ld_in = e->mlp[np - 1][nlp - 1].k_out;
-    const int nh = (int)e->head.size();
-    RC(prof_mark(e, s, FAM_GEMM));
-    if (hfused) {
-      HeadFusedArgs ha{};
-      ha.aim3 = reinterpret_cast<const unsigned short*>(hin);
-      ha.lda3 = pm * ld_in;
-      ha.fmt = sfmt;
-      if (sfmt == SPLIT_H2) { ha.w1 = e->head[0].w2a; ha.w2 = e->head[1].w2a; ha.w2t = e->head[1].wt2a; ha.w1t = e->head[0].wt2a; }
-      else { ha.w1 = e->head[0].w3a; ha.w2 = e->head[1].w3a; ha.w2t = e->head[1].wt3a; ha.w1t = e->head[0].wt3a; }
-      ha.b1 = e->head[0].b; ha.b2 = e->head[1].b; ha.w3 = e->head_w_last; ha.b3 = e->head_b_last;
-      ha.dlast = grad ? W.D[np - 1][nlp - 1] : nullptr;
-      ha.ldd = ld_in;
-      ha.e_atom = W.e_atom;
-      ha.zbar3 = grad ? reinterpret_cast<unsigned short*>(W.zb0) : nullptr;
-      ha.ldz3 = pm * ld_in;
-      ha.M = N;
-      ha.grad = grad ? 1 : 0;
-      RC(launch_head_fused(s, ha));
-    } else {
-    for (int l = 0; l + 1 < nh; ++l) {
-      const Layer& L = e->head[l];
-      RC(mlp_gemm(e, s, EPI_BIAS_GELU, hin, ld_in, L, true, 0, 0, N, L.k_out, L.k_in, L.b, W.hH[l], W.hD[l], L.k_out));
-      hin = W.hH[l];
-      ld_in = L.k_out;
-    }
-    RC(prof_mark(e, s, FAM_POINTWISE));
-    // with gradients: the same kernel writes the backward seed d e / d z_{nh-2} = w_last * GELU'(z) into zb0
-    if (overlap) {
-      RC(launch_head_last(s, hin, ld_in, e->head_w_last, e->head_b_last, e->head[nh - 1].n_in, N, W.e_atom,
-                          grad ? W.hD[nh - 2] : nullptr, grad ? W.zb0 : nullptr));
-    } else {  // same stream: independent of the Coulomb block, so it shares that block's first launch (kernels.h, SrRiders)
-      head_rider.h = hin; head_rider.ldh = ld_in; head_rider.w = e->head_w_last; head_rider.b = e->head_b_last;
-      head_rider.k = e->head[nh - 1].n_in; head_rider.e_atom = W.e_atom;
-      head_rider.d = grad ? W.hD[nh - 2] : nullptr; head_rider.zbar = grad ? W.zb0 : nullptr;
-      head_rider.n_head_blocks = ceil_div(N, 4);
-    }
-    }
-  }
-
-  if (!overlap) {
-    RC(prof_mark(e, s, FAM_COULOMB));
-    RC(coulomb_block(s));
-  }
-  if (dd) {  // halo copies: no energy, no Coulomb adjoint / direct force, no backward seed (model.hip, dd_mask_kernel)
-    const int nlp = (int)e->mlp[np - 1].size();
-    const int seed_bytes = hfused ? pm * e->mlp[np - 1][nlp - 1].k_out * 2 : e->head[e->head.size() - 2].k_out * 4;
-    RC(launch_dd_mask(s, dd->owned, in->numbers, e->sae, W.e_atom, W.ecoul, grad ? W.qbar : nullptr, nq, grad ? W.fgrad : nullptr,
-                      want_s ? W.virial_atom : nullptr, grad ? W.zb0 : nullptr, seed_bytes, N));
-  }
-  // results of the Coulomb block (ecoul, qbar / fgrad / virial seeds, qtot) are first needed here (energy only) or in front of
-  // the first conv backward (see `join` below)
-  // The molecule energies are outputs only: with a stress request (and nothing else riding on the energy launch) their sums ride
-  // on the two stress launches at the end of the evaluation instead of standing as two launches of their own here.
-  bool energy_deferred = false, copy_deferred = false;
-  auto join = [&]() -> int {
-    if (overlap) AIMNET_HIP_CHECK(hipStreamWaitEvent(s, e->ev_join, 0));
-    RC(prof_mark(e, s, FAM_POINTWISE));
-    if (e->energy_rides && grad && want_s && pbc && charges_written && rev_done) {
-      energy_deferred = true;
-      return 0;
-    }
-    // forces only, one slice per molecule, the force-negation launch at the end (not the reverse-pair gather): the sums and the
-    // copy of the charges ride there
-    if (e->energy_rides && grad && want_f && !(want_s && pbc) && !W.xe && W.S == 1 && rev_done) {
-      energy_deferred = true;
-      copy_deferred = !charges_written;
-      return 0;
-    }
-    RC(launch_energy_reduce(s, W.e_atom, W.ecoul, in->numbers, e->sae, W.nl.mol_start, n_mol, W.S, W.part, out->energy,
-                            q_fin, charges_written ? nullptr : out->charges, N,  // + the charges output, unless the DSF walk wrote it
-                            rev_done ? nullptr : &pmap,                          // + the lookup of the reverse-pair map, unless the walk ran it
-                            out->status + 6));
-    rev_done = true;
-    return 0;
-  };
-  if (!grad) {
-    RC(join());
-    RC(prof_mark(e, s, -1));
-    return AIMNET_OK;
-  }
-  bool joined = false;
-
-  // ---- backward -------------------------------------------------------------------------------
-  float* zcur = W.zb0;
-  float* znext = W.zb1;
-  if (!hfused) {  // (the fused head left the split adjoint of the last MLP's output in zb0)
-    const int nh = (int)e->head.size();
-    const Layer& Lp = e->head[nh - 2];  // zcur = zb0 holds the seed written by launch_head_last
-    int ld = Lp.k_out;
-    RC(prof_mark(e, s, FAM_GEMM));
-    for (int l = nh - 2; l >= 0; --l) {
-      const Layer& L = e->head[l];
-      float* dprev;
-      if (l > 0) dprev = W.hD[l - 1];
-      else dprev = W.D[np - 1][e->mlp[np - 1].size() - 1];  // aim = GELU(z_last) of the last MLP
-      RC(mlp_gemm(e, s, dprev ? EPI_MUL : EPI_NONE, zcur, ld, L, false, 0, 0, N, L.k_in, L.k_out, nullptr, znext, dprev, L.k_in));
-      std::swap(zcur, znext);
-      ld = L.k_in;
-    }
-    if (ps) {  // (interim: the head still runs on fp32 operands; its adjoint is split for the MLP backward)
-      if (sfmt == SPLIT_H2) RC(launch_split_h2(s, zcur, ld, N, ld, reinterpret_cast<unsigned short*>(znext), 2 * ld, H2_ACT));
-      else RC(launch_split_bf3(s, zcur, ld, N, ld, reinterpret_cast<unsigned short*>(znext), 3 * ld));
-      std::swap(zcur, znext);
-    }
-  }
-  for (int p = np - 1; p >= 0; --p) {
-    const std::vector<Layer>& Ls = e->mlp[p];
-    const int nl = (int)Ls.size();
-    int ld = Ls[nl - 1].k_out;  // zcur = adjoint of the last layer's pre-activation (GELU' already applied)
-    RC(prof_mark(e, s, FAM_GEMM));
-    if (ps) {  // zcur holds the adjoint in split form; the sweep leaves xbar (fp32) in zcur
-      RC(mlp_sweep_bwd(e, s, sfmt, p, N, p == 0 && p0m, zcur, znext, W.D[p], e->gemm_chain != 0));
-      ld = Ls[0].k_in;
-    } else
-    for (int l = nl - 1; l >= 0; --l) {
-      const Layer& L = Ls[l];
-      if (l > 0)
-        RC(mlp_gemm(e, s, EPI_MUL, zcur, ld, L, false, 0, 0, N, L.k_in, L.k_out, nullptr, znext, W.D[p][l - 1], L.k_in));
-      else if (p == 0 && p0m)  // only the conv columns 256.. of xbar_0 are consumed (the embedding is a constant)
-        RC(mlp_gemm(e, s, EPI_NONE, zcur, ld, L, false, 0, 256, N, L.k_in - 256, L.k_out, nullptr, znext + 256, nullptr, L.k_in));
-      else
-        RC(mlp_gemm(e, s, EPI_NONE, zcur, ld, L, false, 0, 0, N, L.k_in, L.k_out, nullptr, znext, nullptr, L.k_in));
-      std::swap(zcur, znext);
-      ld = L.k_in;
-    }
-    // zcur = xbar_p  (N x k_in of the first layer)
-    if (!joined) {  // the conv backward below is the first consumer of the Coulomb block's qbar / dE/dx / virial seeds
-      RC(join());
-      joined = true;
-    }
-    RC(prof_mark(e, s, FAM_UNCONCAT));
-    if (p == 0 && p0m) {
-      RC(launch_unconcat_p0(s, zcur, ld, W.V[0], e->agh_a, e->afv, e->z_of_slot, e->nslots, W.present_part, W.n_part, W.Sbar, N));
-      RC(prof_mark(e, s, FAM_CONV_BWD));
-      RC(launch_conv_bwd_p0(s, want_s, W.Sbar, e->nslots, W.aslot, W.nb_idx, W.nb_cnt, W.pg, cap, e->bp, W.fgrad, W.virial_atom, N,
-                            order, (W.xe && want_f) ? W.pairbuf : nullptr));
-      break;
-    }
-    RC(launch_unconcat(s, p > 0 ? nq : 0, zcur, ld, W.V[p], W.Vq[p], e->agh_a, e->agh_q, W.Sbar, W.Sqbar, N));
-    RC(prof_mark(e, s, FAM_CONV_BWD));
-    RC(launch_conv_bwd(s, p > 0 ? nq : 0, p > 0, want_s, p == 0 ? e->afv : W.a[p], p == 0 ? in->numbers : nullptr,
-                       p > 0 ? W.q[p - 1] : nullptr, W.Sbar, W.Sqbar, W.nb_idx, W.nb_cnt, W.pg, cap, e->bp, zcur, ld,
-                       (p < np - 1) ? W.abar : nullptr, W.abar, W.qbar, W.qbar, W.fgrad, W.virial_atom, N, order,
-                       (W.xe && p > 0) ? W.pairbuf : nullptr, p < np - 1, e->split_max));
-    if (p == 0) break;
-    // NSE adjoint of pass p-1, then the adjoint of its MLP output
-    const std::vector<Layer>& Lq = e->mlp[p - 1];
-    const int nlq = (int)Lq.size();
-    const float* y = W.H[p - 1][nlq - 1];
-    const int ldy = Lq[nlq - 1].k_out;
-    RC(prof_mark(e, s, FAM_POINTWISE));
-    if (dd) {  // domain decomposition: the adjoint sums run over every local atom and are all-reduced over the ranks
-      RC(launch_nse_bwd_reduce(s, W.qbar, y, ldy, nq, W.nl.mol_start, n_mol, N, 1, (float*)W.part));
-      if (dd->fn(dd->ctx, AIMNET_DD_SUM, W.part, (int64_t)nq * n_mol, (void*)s) != 0) {
-        set_last_error("eval: the domain-decomposition exchange function failed (NSE adjoint sums)");
-        return AIMNET_E_INVALID;
-      }
-      RC(launch_build_zbar(s, W.qbar, W.abar, y, ldy, ar.last_linear[p - 1] ? nullptr : W.D[p - 1][nlq - 1], W.Fm[p - 1],
-                           W.Dm[p - 1], (const float*)W.part, 1, mol_c, N, n_mol, 256, nq, p - 1 > 0, znext, W.qbar, sfmt, nullptr,
-                           dd->owned));
-    } else if (e->nse_merged && N <= 1024) {  // small systems: the molecule sums inside build_zbar, one launch instead of two
-      RC(launch_build_zbar(s, W.qbar, W.abar, y, ldy, ar.last_linear[p - 1] ? nullptr : W.D[p - 1][nlq - 1], W.Fm[p - 1],
-                           W.Dm[p - 1], nullptr, 1, mol_c, N, n_mol, 256, nq, p - 1 > 0, znext, W.qbar2, sfmt, W.nl.mol_start));
-      std::swap(W.qbar, W.qbar2);
-    } else {
-      RC(launch_nse_bwd_reduce(s, W.qbar, y, ldy, nq, W.nl.mol_start, n_mol, N, W.S, (float*)W.part));
-      RC(launch_build_zbar(s, W.qbar, W.abar, y, ldy, ar.last_linear[p - 1] ? nullptr : W.D[p - 1][nlq - 1], W.Fm[p - 1],
-                           W.Dm[p - 1], (const float*)W.part, W.S, mol_c, N, n_mol, 256, nq, p - 1 > 0, znext, W.qbar, sfmt));
-    }
-    std::swap(zcur, znext);
-  }
-  RC(prof_mark(e, s, FAM_POINTWISE));
-  // reverse-pair form: the pair buffer holds F1 of both passes; its gather is the last contribution to dE/dx and writes the forces
-  // (with a stress request the force gather rides on the launch of the virial sums: independent work, one kernel boundary less)
-  const bool pf_rides = W.xe && want_f && want_s && pbc;
-  const PairForceRider pfr{W.nb_idx, W.nb_cnt, W.rev, W.pairbuf, cap, out->forces, ceil_div(N, 4)};
-  const EnergyRider erd{W.e_atom, W.ecoul, in->numbers, e->sae, W.part_e, out->energy, n_mol,
-                        q_fin, copy_deferred ? out->charges : nullptr, N};
-  if (W.xe && want_f && !pf_rides) RC(launch_pair_force(s, W.nb_idx, W.nb_cnt, W.rev, W.pairbuf, cap, N, W.fgrad, out->forces, out->status + 6));
-  // (domain decomposition: no cell - the virial sums are divided by the volume of a unit cube, i.e. the `stress` output takes the
-  // rank's share of dE/d(strain) itself; the caller adds the ranks' shares and divides by the cell volume)
-  RC(launch_finalize(s, W.fgrad, W.virial_atom, W.nl.mol_start, dd ? e->unit_cell : in->cell, dd ? 1 : n_cell, n_mol, N, W.S, W.part,
-                     (want_f && !W.xe) ? out->forces : nullptr, want_s ? out->stress : nullptr, pf_rides ? &pfr : nullptr,
-                     energy_deferred ? &erd : nullptr, e->sums_whole != 0, out->status + 6));
   RC(prof_mark(e, s, -1));
   return AIMNET_OK;
 }
@@ -1488,7 +1342,7 @@ int aimnet_neighbor_list(const float* coord, const int32_t* mol_idx, int32_t n_a
   RC(launch_mol_start(s, mol_idx, n_atoms, n_mol, nl.mol_start, nl.mol_c));
   mol_idx = nl.mol_c;  // clamped to [0, n_mol)
   RC(launch_wrap(s, coord, mol_idx, n_atoms, n_mol, cell, cell ? n_cell : 0, pb, nl));
-  if (!cell && (long)n_atoms >= 1500L * n_mol) RC(launch_bbox(s, n_mol, nl));
+  if (!cell && bbox_applies(n_atoms, n_mol)) RC(launch_bbox(s, n_mol, nl));
   RC(launch_nlist(s, n_atoms, n_mol, mol_idx, cell, cell ? n_cell : 0, pb, cutoff, cutoff, max_nb, fill_value, 1, nl, nbmat,
                   codes, num_nb, status + 0, status + 1));
   if (cell) {

@@ -856,18 +856,6 @@ __global__ void hvp_out_kernel(const float* __restrict__ xbar, size_t n, float* 
 }
 
 // ---- workspace --------------------------------------------------------------------------------------------------------
-struct Carve {
-  char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t n) {
-    off = align_up(off, 256);
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 struct HvpWs {
   NlistBuffers nl;
   int *nb_idx, *nb_shift, *nb_cnt, *lr_idx, *lr_shift, *lr_cnt;
@@ -896,16 +884,8 @@ struct HvpWs {
   size_t total;
 };
 
-int hvp_max_width(const aimnet_engine* e) {
-  int w = 32;
-  for (int p = 0; p < e->arch.n_pass; ++p)
-    for (const Layer& L : e->mlp[p]) w = std::max(w, std::max(L.k_in, L.k_out));
-  for (const Layer& L : e->head) w = std::max(w, std::max(L.k_in, L.k_out));
-  return w;
-}
-
 void hvp_layout(const aimnet_engine* e, int N, int n_mol, int K, const aimnet_eval_options* opt, char* base, HvpWs& W) {
-  Carve c{base};
+  Carver c{base};
   const size_t n = (size_t)N, kn = (size_t)K * N;
   const int np = e->arch.n_pass, nq = e->nq;
   const int cap = std::max(1, opt->max_nb), cap_lr = std::max(0, opt->max_nb_lr);
@@ -918,7 +898,7 @@ void hvp_layout(const aimnet_engine* e, int N, int n_mol, int K, const aimnet_ev
   W.lr_shift = c.take<int>(n * cap_lr);
   W.lr_cnt = c.take<int>(n);
   W.pg = c.take<float4>(n * cap);
-  const int mw = hvp_max_width(e);
+  const int mw = max_width(e);
   for (int p = 0; p < np; ++p) {
     W.a[p] = p == 0 ? nullptr : c.take<float>(n * NF);
     W.ta[p] = p == 0 ? nullptr : c.take<float>(kn * NF);
@@ -1000,12 +980,6 @@ void hvp_layout(const aimnet_engine* e, int N, int n_mol, int K, const aimnet_ev
   }
   W.total = align_up(c.off, 256);
 }
-
-#define RC(call)         \
-  do {                   \
-    int _rc = (call);    \
-    if (_rc) return _rc; \
-  } while (0)
 
 inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
@@ -1124,11 +1098,12 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
   }
   const bool ewald = coulomb == AIMNET_COULOMB_EWALD;
   if (ewald) {
-    if (!pbc || in->pbc_sys || !(in->pbc[0] && in->pbc[1] && in->pbc[2])) {
+    const int bad = ewald_args_check(in, opt);
+    if (bad == 1) {
       set_last_error("hvp: Ewald summation needs a cell that is periodic along all three axes (lr.py:655-657)");
       return AIMNET_E_INVALID;
     }
-    if (!(opt->ewald_accuracy > 0.0f && opt->ewald_accuracy < 1.0f) || opt->ewald_max_k < EWALD_KB) {
+    if (bad) {
       set_last_error("hvp: Ewald summation needs 0 < ewald_accuracy < 1 and ewald_max_k >= %d", EWALD_KB);
       return AIMNET_E_INVALID;
     }
@@ -1146,7 +1121,7 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
     set_last_error("hvp: n_cell must be 1 or n_mol");
     return AIMNET_E_INVALID;
   }
-  if ((size_t)K * (size_t)N * (size_t)hvp_max_width(e) >= (size_t)INT32_MAX) {
+  if ((size_t)K * (size_t)N * (size_t)max_width(e) >= (size_t)INT32_MAX) {
     set_last_error("hvp: n_vec * n_atoms too large for one sweep (split the directions)");
     return AIMNET_E_INVALID;
   }
@@ -1170,7 +1145,7 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
                       d3 ? W.aslot : nullptr, d3 ? W.present_part : nullptr));
   const int* mol_c = W.nl.mol_c;
   RC(launch_wrap(s, in->coord, mol_c, N, n_mol, in->cell, n_cell, in->pbc, W.nl, in->pbc_sys, pbc ? ar.rc : 0.0f));
-  if (!pbc && (long)N >= 1500L * n_mol) RC(launch_bbox(s, n_mol, W.nl));
+  if (!pbc && bbox_applies(N, n_mol)) RC(launch_bbox(s, n_mol, W.nl));
   RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, ar.rc, ar.rc, cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
                   status + 0, status + 2, W.pg));
   if (coulomb == AIMNET_COULOMB_DSF || ewald)
@@ -1215,12 +1190,7 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
   }
 
   // ---- Coulomb seeds (+ tangents) of qbar / xbar ----
-  CoulombParams cp;
-  cp.factor = (float)(0.5 * 27.211386024367243 * 0.5291772105638411);
-  cp.sr_rc = ar.sr_rc;
-  cp.sr_envelope = ar.sr_envelope;
-  cp.dsf_rc = opt->dsf_rc;
-  cp.dsf_alpha = opt->dsf_alpha;
+  CoulombParams cp = coulomb_params(ar, opt);
   int qb = 0;  // index of the live qbar buffers
   const float *q_fin = W.q[np - 2], *tq_fin = W.tq[np - 2];
   hipLaunchKernelGGL(hvp_coulomb_sr_kernel, gwk, b256, 0, s, ar.sr_coulomb != 0, q_fin, tq_fin, nq, W.nb_idx, W.nb_cnt, W.pg, cap,
@@ -1316,10 +1286,7 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
     AIMNET_LAUNCH_CHECK();
     AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_g, 0, (size_t)NC * 3 * sizeof(float), s));
     AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_e, 0, (size_t)NC * sizeof(double), s));
-    D3Params dp;
-    dp.s6 = opt->d3_s6; dp.s8 = opt->d3_s8; dp.a1 = opt->d3_a1; dp.a2 = opt->d3_a2;
-    dp.r_on = opt->d3_smoothing_on * 1.8897261258369282f;
-    dp.r_off = opt->d3_cutoff * 1.8897261258369282f;
+    const D3Params dp = d3_params(opt);
     RC(launch_dftd3(s, true, false, W.d3c_x, W.d3c_mol, in->cell, n_cell, W.d3c_aslot, W.d3c_idx, W.d3c_shift, W.d3c_cnt, cap_d3,
                     e->d3, dp, opt->d3_cutoff, NC, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, W.d3c_g, nullptr, false, cp, nullptr,
                     nullptr));

@@ -155,7 +155,7 @@ size_t nlist_scratch_bytes(int n_atoms, int n_mol);
 size_t nlist_xw_offset(int n_mol);  // byte offset of NlistBuffers::xw inside the scratch
 void nlist_carve(NlistBuffers& b, char* base, int n_atoms, int n_mol);
 // bad: input sanity flags (bit 0 atomic number outside [0,63], bit 1 mol_idx outside [0,n_mol), bit 2 mol_idx not sorted);
-// mol_c [n_atoms]: the clamped copy of mol_idx; + the species pass (launch_species) when slot_of_z is given
+// mol_c [n_atoms]: the clamped copy of mol_idx; + the species pass (aslot, present_part) when slot_of_z is given
 // cell + bin-grid setup of the periodic fast path (launch_wrap with a bin width) as a rider block of launch_mol_start: it does not
 // need that launch's output (atom counts by binary search in the sorted mol_idx).  sys == NULL: none.
 struct CellSetupRider {
@@ -199,12 +199,12 @@ struct D3CnRider {
 int launch_nlist(hipStream_t s, int n_atoms, int n_mol, const int* mol_idx, const float* cell, int n_cell,
                  const int pbc[3], float cutoff, float bin_width, int cap, int fill_value, int fill_rows,
                  NlistBuffers& b, int* nb_idx, int* nb_shift, int* nb_cnt, int* status_max, int* status_ovf,
-                 float4* pg = nullptr,
-                 // != NULL: the status reduction is NOT launched; *status_later = the per-row counts for nlist_status_block
+                 float4* pg = nullptr,  // pg [n_atoms, cap] (may be NULL): also emit the pair geometry (u, d) of every entry
+                 // the status reduction is NOT launched: the per-row counts stay in b.sorted_tmp for nlist_status_block
                  // (cellwalk.h) as riders of a later launch - valid until the next list build
-                 const int** status_later = nullptr,  // pg [n_atoms, cap] (may be NULL): also emit the pair geometry (u, d) of every entry
-                 // cn != NULL and the batch is binned: the D3 coordination numbers ride (then *cn_done = true)
-                 const D3CnRider* cn = nullptr, bool* cn_done = nullptr);
+                 bool status_later = false,
+                 // != NULL (binned batches only, eval_plan.h decides): the D3 coordination numbers ride
+                 const D3CnRider* cn = nullptr);
 int launch_bins(hipStream_t s, int n_atoms, int n_mol, const int* mol_idx, float width, NlistBuffers& b);
 // caller-supplied neighbour matrix [n_atoms][width] (+ integer shifts [n_atoms][width][3] or NULL) -> the engine's row format
 // (valid entries compacted in order, shifts packed, optional pair geometry from the coordinates as given in b.xw); status as
@@ -245,16 +245,12 @@ bool pair_rev_supported(int n_atoms, int cap);  // row capacity / atom count the
 // reverse-pair map rev[i * cap + m] = position of (i, -shift) in the row of idx[i][m]: per-atom 256-slot hash tables `tab`
 // (pair_hash_bytes) built and probed on the device
 size_t pair_hash_bytes(int n_atoms);
-int launch_pair_rev_hash(hipStream_t s, const int* nb_idx, const int* nb_shift, const int* nb_cnt, int cap, int n_atoms,
-                         unsigned long long* tab, int* rev);
 int launch_pair_force(hipStream_t s, const int* nb_idx, const int* nb_cnt, const int* rev, const float4* pairbuf, int cap,
                       int n_atoms, const float* fgrad, float* forces, int* nf = nullptr);  // forces = -(fgrad + pair terms)
 // `order` (conv_fwd / conv_bwd / conv_bwd_p0): optional permutation of the atoms giving the PROCESSING order - the
 // bin-sorted order of the cell list for periodic systems - so that an XCD's centres and the rows they gather stay
 // spatially coherent (and L2-resident) whatever the order of the input file; NULL = input order.
 // pass-0 backward through species moments (conv.hip)
-int launch_species(hipStream_t s, const int* numbers, const int* slot_of_z, int n_atoms, int* aslot,
-                   unsigned long long* present_part);
 int launch_unconcat_p0(hipStream_t s, const float* xbar, int ldx, const float* Vsave, const float* agh_a, const float* afv,
                        const int* z_of_slot, int nslots, const unsigned long long* present_part, int n_part, float* T,
                        int n_atoms);
@@ -292,14 +288,10 @@ int launch_dd_mask(hipStream_t s, const float* owned, const int* numbers, const 
                    float* qbar, int nq, float* fgrad, float* virial_atom, void* seed, int seed_row_bytes, int n_atoms);
 int launch_nse_fwd(hipStream_t s, const float* y, int ldy, int nq, const float* q_prev, const int* mol_start,
                    const float* charge, int n_mol, int n_atoms, int S, float* part, float* q_new, float* Fm, float* Dm,
-                   // upd_a_new != NULL: a_new = a + delta_a (launch_update_a with these arguments) rides on the same launch
+                   // upd_a_new != NULL: a_new = a + delta_a (row_of: pass 0 adds to the embedding row afv[Z_i] directly) rides on the same launch
                    const float* upd_a = nullptr, const int* upd_row_of = nullptr, float* upd_a_new = nullptr,
                    const DdLink* dd = nullptr);  // != NULL: sums over owned atoms, all-reduced by dd->fn between the two launches
 int launch_charge_sum(hipStream_t s, const float* q2, int n_atoms, float* q_tot, float* q_spin);
-int launch_update_a(hipStream_t s, const float* a, const int* row_of, const float* y, int ldy, int nq, int n_atoms, float* a_new);
-// d / zbar (may be NULL): also writes the backward seed zbar = w * d (d = GELU' of the layer below, ldh wide)
-int launch_head_last(hipStream_t s, const float* h, int ldh, const float* w, const float* b, int k, int n_atoms,
-                     float* e_atom, const float* d, float* zbar);
 int launch_energy_reduce(hipStream_t s, const float* e_atom, const double* ecoul, const int* numbers,
                          const double* sae, const int* mol_start, int n_mol, int S, double* part, double* energy,
                          // copy_dst != NULL: copy_n floats copy_src -> copy_dst ride on the same launch (the charges output)
@@ -398,12 +390,12 @@ int launch_dftd3(hipStream_t s, bool grad, bool stress, const float* xw, const i
                  const DdLink* dd = nullptr);  // domain decomposition: halo rows of d3w / dE/dcn come from their owners (dd->fn, what = 2)  // cn_done: d3w was filled by the list build (D3CnRider): no d3_cn_kernel launch
 // with_dsf: the DSF Coulomb pair sum (cutoff == cp.dsf_rc) is evaluated in the same pair pass; adds to ecoul / qbar too
 // Independent work that rides on the SR-Coulomb launch (role-dispatched blocks behind the pair blocks; a kernel boundary costs
-// 4-5 us on the device): launch_head_last's arguments (n_head_blocks = ceil(n_atoms / 4), 0 = none) and the charge stream of the
+// 4-5 us on the device): the last energy-head layer k -> 1 with its adjoint seed zbar = w * d (n_head_blocks = ceil(n_atoms / 4), 0 = none) and the charge stream of the
 // list-free DSF walk (n_stream_blocks = ceil(n_atoms / 256), 0 = none; xs / xq = NlistBuffers::xs / sorted_tmp_xq)
 struct SrRiders {
   const float* h; int ldh; const float* w; const float* b; int k; float* e_atom; const float* d; float* zbar; int n_head_blocks;
   const float4* xs; float4* xq; float* charges_out; int n_stream_blocks;
-  // simple_xw != NULL: the "simple" LRCoulomb term (launch_coulomb_simple with these arguments) in the same waves
+  // simple_xw != NULL: the "simple" LRCoulomb term (all pairs inside a molecule) in the same waves
   const float* simple_xw; const int* simple_mol_idx; const int* simple_mol_start;
   PairMapRider hash;  // the hash build of the reverse-pair map (its lookup rides on a later launch)
   // the status words of the short-range list (nlist_status_block, cellwalk.h): n_status_blocks = ceil(n_atoms / 1024), 0 = none
@@ -416,9 +408,6 @@ struct SrRiders {
 int launch_coulomb_sr(hipStream_t s, bool grad, bool stress, bool enabled, const float* q, const int* nb_idx,
                       const int* nb_cnt, const float4* pg, int cap, CoulombParams cp, int n_atoms, double* ecoul,
                       float* qbar, float* fgrad, float* virial_atom, const SrRiders* riders = nullptr);
-int launch_coulomb_simple(hipStream_t s, bool grad, const float* q, const float* xw, const int* mol_idx,
-                          const int* mol_start, CoulombParams cp, int n_atoms, double* ecoul, float* qbar,
-                          float* fgrad);
 int launch_coulomb_dsf(hipStream_t s, bool grad, bool stress, const float* q, const float* xw, const int* mol_idx,
                        const float* cell, int n_cell, const int* nb_idx, const int* nb_shift, const int* nb_cnt,
                        int cap, CoulombParams cp, int n_atoms, double* ecoul, float* qbar, float* fgrad,

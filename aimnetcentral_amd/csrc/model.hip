@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void nse_fwd_apply_kernel(const float* __restr
 int launch_nse_fwd(hipStream_t s, const float* y, int ldy, int nq, const float* q_prev, const int* mol_start,
                    const float* charge, int n_mol, int n_atoms, int S, float* part, float* q_new, float* Fm, float* Dm,
                    const float* upd_a, const int* upd_row_of, float* upd_a_new, const DdLink* dd) {
-  // upd_a_new != NULL: the feature update a_new = a + delta_a (launch_update_a) rides on the launch of channel 0
+  // upd_a_new != NULL: the feature update a_new = a + delta_a (update_a_block) rides on the launch of channel 0
   const UpdateA none{nullptr, nullptr, nullptr, 0, 0, 0, nullptr};
   const UpdateA upd{upd_a, upd_row_of, y, ldy, 2 * nq, n_atoms, upd_a_new};
   const int n_upd = upd_a_new ? (int)(((size_t)n_atoms * 256 + 255) / 256) : 0;
@@ -214,18 +214,6 @@ int launch_charge_sum(hipStream_t s, const float* q2, int n_atoms, float* q_tot,
   return 0;
 }
 
-// row_of (may be NULL): feature row of atom i inside `a` - pass 0 adds delta_a to the embedding row afv[Z_i] directly, so
-// the initial features a^0 = afv[Z] (aimnet2.py:145-148) are never materialised
-__global__ void update_a_kernel(UpdateA u) { update_a_block(u, blockIdx.x); }
-
-int launch_update_a(hipStream_t s, const float* a, const int* row_of, const float* y, int ldy, int nq, int n_atoms, float* a_new) {
-  const size_t n = (size_t)n_atoms * 256;
-  const UpdateA u{a, row_of, y, ldy, 2 * nq, n_atoms, a_new};
-  hipLaunchKernelGGL(update_a_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, u);
-  AIMNET_LAUNCH_CHECK();
-  return 0;
-}
-
 // ---- energy head last layer (k -> 1) and its adjoint seed ---------------------------------------
 // d / zbar (may be NULL): the adjoint seed of the backward sweep, zbar = w * GELU'(z) of the layer below (ldh wide, zero
 // padding beyond k), is written by the same wave - dE/de_atom = 1, so it does not wait for anything
@@ -243,12 +231,6 @@ __device__ __forceinline__ void head_last_block(const float* __restrict__ h, int
     for (int c = lane; c < ldh; c += 64) zbar[(size_t)i * ldh + c] = (c < k) ? w[c] * d[(size_t)i * ldh + c] : 0.0f;
 }
 
-__global__ void head_last_kernel(const float* __restrict__ h, int ldh, const float* __restrict__ w,
-                                 const float* __restrict__ b, int k, int n_atoms, float* __restrict__ e_atom,
-                                 const float* __restrict__ d, float* __restrict__ zbar) {
-  head_last_block(h, ldh, w, b, k, n_atoms, e_atom, d, zbar, blockIdx.x);
-}
-
 // bin-ordered (x, y, z, q) stream of the list-free DSF walk (see charge_stream_kernel below), one 256-thread block of it
 __device__ __forceinline__ void charge_stream_block(const float4* __restrict__ xs, const float* __restrict__ q, int n_atoms,
                                                     float4* __restrict__ xq, float* __restrict__ charges_out, int block) {
@@ -259,13 +241,6 @@ __device__ __forceinline__ void charge_stream_block(const float4* __restrict__ x
   const float qv = q[id];
   xq[k] = make_float4(c.x, c.y, c.z, qv);
   if (charges_out) charges_out[id] = qv;
-}
-
-int launch_head_last(hipStream_t s, const float* h, int ldh, const float* w, const float* b, int k, int n_atoms,
-                     float* e_atom, const float* d, float* zbar) {
-  hipLaunchKernelGGL(head_last_kernel, dim3(ceil_div(n_atoms, 4)), dim3(256), 0, s, h, ldh, w, b, k, n_atoms, e_atom, d, zbar);
-  AIMNET_LAUNCH_CHECK();
-  return 0;
 }
 
 // partial sum number b = (molecule, slice) of E_m = sum_i e_i + SAE[Z_i] + pair energies (fp64)
@@ -493,7 +468,7 @@ __global__ __launch_bounds__(256) void coulomb_sr_kernel(bool enabled, const flo
     }
   }
   pair_store<GRAD, STRESS, false>(A, i, lane, -cp.factor, 0.0, 0.0f, ecoul, qbar, fgrad, virial_atom);
-  if (rd.simple_xw) {  // LRCoulomb "simple" (all pairs of the molecule, coulomb_simple_kernel below) in the same wave: it accumulates
+  if (rd.simple_xw) {  // LRCoulomb "simple" (every other atom of the same molecule, w = 1 / d) in the same wave: it accumulates
     // onto what this wave has just stored - the same sums in the same order as the separate launch, one kernel boundary less
     const float* __restrict__ xw = rd.simple_xw;
     const int mi = rd.simple_mol_idx[i];
@@ -530,47 +505,9 @@ int launch_coulomb_sr(hipStream_t s, bool grad, bool stress, bool enabled, const
   return 0;
 }
 
-// "simple": every other atom of the same molecule, w = 1/d
-template <bool GRAD>
-__global__ __launch_bounds__(256) void coulomb_simple_kernel(const float* __restrict__ q, const float* __restrict__ xw,
-                                                            const int* __restrict__ mol_idx,
-                                                            const int* __restrict__ mol_start, CoulombParams cp,
-                                                            int n_atoms, double* __restrict__ ecoul,
-                                                            float* __restrict__ qbar, float* __restrict__ fgrad) {
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n_atoms) return;
-  const int lane = threadIdx.x & 63;
-  const int m = mol_idx[i];
-  const int j0 = mol_start[m], j1 = mol_start[m + 1];
-  const float xi = xw[3 * i], yi = xw[3 * i + 1], zi = xw[3 * i + 2], qi = q[i];
-  PairAcc A;
-  for (int j = j0 + lane; j < j1; j += 64) {
-    if (j == i) continue;
-    const float rx = xw[3 * j] - xi, ry = xw[3 * j + 1] - yi, rz = xw[3 * j + 2] - zi;
-    const float d = sqrtf(rx * rx + ry * ry + rz * rz);
-    const float inv = 1.0f / d;
-    pair_add<GRAD, false>(A, inv, -inv * inv, qi, q[j], rx * inv, ry * inv, rz * inv, d);
-  }
-  pair_store<GRAD, false, true>(A, i, lane, cp.factor, 0.0, 0.0f, ecoul, qbar, fgrad, nullptr);
-}
-
-int launch_coulomb_simple(hipStream_t s, bool grad, const float* q, const float* xw, const int* mol_idx,
-                          const int* mol_start, CoulombParams cp, int n_atoms, double* ecoul, float* qbar,
-                          float* fgrad) {
-  dim3 grid(ceil_div(n_atoms, 4)), block(256);
-  if (grad)
-    hipLaunchKernelGGL(coulomb_simple_kernel<true>, grid, block, 0, s, q, xw, mol_idx, mol_start, cp, n_atoms, ecoul, qbar,
-                       fgrad);
-  else
-    hipLaunchKernelGGL(coulomb_simple_kernel<false>, grid, block, 0, s, q, xw, mol_idx, mol_start, cp, n_atoms, ecoul, qbar,
-                       fgrad);
-  AIMNET_LAUNCH_CHECK();
-  return 0;
-}
-
 // DSF over the long-range neighbour matrix, plus the self term -2k (erfc(a Rc)/(2 Rc) + a/sqrt(pi)) q_i^2
 // SIMPLE: w = 1 / d over every entry of the matrix, no cutoff, no self term - LRCoulomb.coul_simple over a CALLER-SUPPLIED
-// `nbmat_lr` (lr.py:311-331 sums over whatever list it is given; the engine's own lists use coulomb_simple_kernel above)
+// `nbmat_lr` (lr.py:311-331 sums over whatever list it is given; the engine's own lists sum all pairs inside the SR-Coulomb launch, SrRiders::simple_xw)
 template <bool GRAD, bool STRESS, bool SIMPLE = false>
 __global__ __launch_bounds__(256) void coulomb_dsf_kernel(const float* __restrict__ q, const float* __restrict__ xw,
                                                          const int* __restrict__ mol_idx, const float* __restrict__ cell,

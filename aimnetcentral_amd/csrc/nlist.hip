@@ -789,7 +789,7 @@ __global__ __launch_bounds__(256) void nlist_cell_kernel(const float* __restrict
                 const float d2 = fmaxf(rx * rx + ry * ry + rz * rz, 1e-24f);
                 const float d = d2 * __builtin_amdgcn_rsqf(d2);
                 const float rcj = cn.rcov[cn.aslot[__float_as_int(w)]];
-                const float arg = -16.0f * ((rci + rcj) * __builtin_amdgcn_rcpf(fmaxf(d * 1.8897261258369282f, 1e-12f)) - 1.0f);
+                const float arg = -16.0f * ((rci + rcj) * __builtin_amdgcn_rcpf(fmaxf(d * BOHR_INV_F, 1e-12f)) - 1.0f);
                 cnv += __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(arg * 1.4426950408889634f));
               }
               count += __popcll(mask);
@@ -927,8 +927,7 @@ __global__ __launch_bounds__(1024) void nlist_status_kernel(const int* __restric
 int launch_nlist(hipStream_t s, int n_atoms, int n_mol, const int* mol_idx, const float* cell, int n_cell,
                  const int pbc[3], float cutoff, float bin_width, int cap, int fill_value, int fill_rows,
                  NlistBuffers& b, int* nb_idx, int* nb_shift, int* nb_cnt, int* status_max, int* status_ovf, float4* pg,
-                 const int** status_later, const D3CnRider* cn, bool* cn_done) {
-  if (cn_done) *cn_done = false;
+                 bool status_later, const D3CnRider* cn) {
   (void)n_cell;
   (void)pbc;
   (void)cell;
@@ -946,12 +945,8 @@ int launch_nlist(hipStream_t s, int n_atoms, int n_mol, const int* mol_idx, cons
                        b.bin_start, b.xs, n_atoms, cutoff, cap, fill_value, fill_rows, nb_idx, nb_shift, nb_cnt, cnt_true, pg,
                        cn ? *cn : D3CnRider{});
     AIMNET_LAUNCH_CHECK();
-    if (cn && cn->d3w && cn_done) *cn_done = true;
   }
-  if (status_later) {  // the caller runs nlist_status_block over these counts as riders of a later launch (no list build in between)
-    *status_later = cnt_true;
-    return 0;
-  }
+  if (status_later) return 0;  // the caller runs nlist_status_block over cnt_true as riders of a later launch (no list build in between)
   hipLaunchKernelGGL(nlist_status_kernel, dim3(ceil_div(n_atoms, 1024)), dim3(1024), 0, s, cnt_true, n_atoms, cap, status_max,
                      status_ovf);
   AIMNET_LAUNCH_CHECK();

@@ -1,5 +1,5 @@
 """The engine's option table (csrc/engine.hip, OPTIONS): every switch that include/aimnet_hip.h lists reads back what was set, the
-environment and set_option normalise alike, unknown names are errors and the retired "conv_mfma" reads 0 and accepts only 0."""
+environment and set_option normalise alike, unknown names are errors and the retired "conv_mfma" and "overlap_coulomb" read 0 and accept only 0."""
 from __future__ import annotations
 
 import os
@@ -24,7 +24,7 @@ def test_option_table():
     from aimnetcentral_amd.engine import HipEngine
 
     names = _header_options()
-    assert "conv_mfma" in names and len(names) == len(set(names)) == 21
+    assert "conv_mfma" in names and "overlap_coulomb" in names and len(names) == len(set(names)) == 21
     spec = loader.synthetic_spec(0)
     eng = HipEngine(spec, "cuda:0")
     for name in names:
@@ -47,6 +47,10 @@ def test_option_table():
     eng.set_option("conv_mfma", 0)
     with pytest.raises(HipLibraryError, match="conv_mfma was removed"):
         eng.set_option("conv_mfma", 1)
+    assert eng.get_option("overlap_coulomb") == 0
+    eng.set_option("overlap_coulomb", 0)
+    with pytest.raises(HipLibraryError, match="overlap_coulomb was removed"):
+        eng.set_option("overlap_coulomb", 1)
     # the environment is read once, when an engine is created
     assert eng.get_option("gemm_chain") == 1
     old = os.environ.get("AIMNET_GEMM_CHAIN")
