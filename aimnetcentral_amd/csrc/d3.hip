@@ -62,7 +62,8 @@ __device__ __forceinline__ void d3_add(D3Acc& A, float t, float ux, float uy, fl
 template <bool GRAD, bool STRESS>
 __device__ __forceinline__ void d3_store(D3Acc& A, int i, int lane, float k, double* ecoul, float* fgrad, float* virial_atom,
                                          double kc = 0.0) {
-  const double e = wave_sum(A.e) + (kc != 0.0 ? kc / (double)k * wave_sum(A.ec) : 0.0);
+  // (fma written out: the energy must not depend on how the compiler contracts each <GRAD, STRESS> instantiation)
+  const double e = kc != 0.0 ? fma(kc / (double)k, wave_sum(A.ec), wave_sum(A.e)) : wave_sum(A.e);
   float f0 = 0.f, f1 = 0.f, f2 = 0.f;
   if (GRAD) {
     f0 = wave_sum(A.f0);
@@ -74,7 +75,7 @@ __device__ __forceinline__ void d3_store(D3Acc& A, int i, int lane, float k, dou
     }
   }
   if (lane == 0) {
-    ecoul[i] += (double)k * e;
+    ecoul[i] = fma((double)k, e, ecoul[i]);
     if (GRAD) {
       fgrad[3 * i + 0] += -2.0f * k * f0;
       fgrad[3 * i + 1] += -2.0f * k * f1;
@@ -246,7 +247,14 @@ __global__ __launch_bounds__(256) void d3_pair_kernel(const float4* __restrict__
   }
   const D3Cell C(c);
   const size_t row = (size_t)i * cap;
+  // ONE arithmetic form for every instantiation: the pair energy is the same number whether or not the gradient terms are formed
+  // beside it (an energy-only evaluation returns the bits of a force evaluation, tests/test_gpu_request_kinds.py).  With the
+  // multiply-adds left to the compiler's contraction the <GRAD = false> and <GRAD = true> energies differed by 3e-8 - 7e-8 eV per
+  // system (one rounding of the dispersion energy).  The likely cause - not pinned to one instruction - is that contraction and
+  // scheduling are decided per instantiation and the GRAD terms add uses to the shared subexpressions; what is established is
+  // that this form removes the difference: no contraction in this body, every fused multiply-add written out.
   auto body = [&](const D3Pair& P, const float4& sj0, const float4& sj1, const float2& sj2, float qj) {
+#pragma clang fp contract(off)
     const int sj = P.sj;
     const float s_j[5] = {sj0.x, sj0.y, sj0.z, sj0.w, sj1.x};
     const float w_j[5] = {sj1.y, sj1.z, sj1.w, sj2.x, sj2.y};
@@ -263,15 +271,15 @@ __global__ __launch_bounds__(256) void d3_pair_kernel(const float4* __restrict__
         for (int b = 0; b < 5; ++b) {
           const float c6r = cr[a * 5 + b];
           const float w = (s_i[a] + s_j[b] >= -12.0f && c6r != 0.0f) ? w_j[b] : 0.0f;
-          sb += c6r * w;
+          sb = fmaf(c6r, w, sb);
           tb += w;
         }
-        N += w_i[a] * sb;
-        D += w_i[a] * tb;
+        N = fmaf(w_i[a], sb, N);
+        D = fmaf(w_i[a], tb, D);
         if (GRAD) {
           const float wg = w_i[a] * g_i[a];
-          G += wg * sb;
-          H += wg * tb;
+          G = fmaf(wg, sb, G);
+          H = fmaf(wg, tb, H);
         }
       }
     }
@@ -280,18 +288,18 @@ __global__ __launch_bounds__(256) void d3_pair_kernel(const float4* __restrict__
     const float c6 = has ? N * invD : 0.0f;
     const float db = fmaxf(P.d * BOHR_INV_F, 1e-12f);
     const float qq = 3.0f * q_i * T.r4r2[sj];
-    const float r0 = P3.a1 * __builtin_amdgcn_sqrtf(qq) + P3.a2;
+    const float r0 = fmaf(P3.a1, __builtin_amdgcn_sqrtf(qq), P3.a2);
     const float d2 = db * db, d4 = d2 * d2, d6 = d4 * d2, d8 = d4 * d4;
     const float r2 = r0 * r0, r4 = r2 * r2, r6 = r4 * r2, r8 = r4 * r4;
     const float i6 = frcp(d6 + r6), i8 = frcp(d8 + r8);
-    const float damp = P3.s6 * i6 + P3.s8 * qq * i8;
+    const float damp = fmaf(P3.s6, i6, P3.s8 * qq * i8);
     float sw = 1.0f, dsw = 0.0f;
     if (P3.r_off > P3.r_on && db > P3.r_on) {
       const float iw = frcp(P3.r_off - P3.r_on);
       const float t = fminf(fmaxf((db - P3.r_on) * iw, 0.0f), 1.0f);
       const float t2 = t * t;
-      sw = 1.0f - t2 * t * (10.0f - 15.0f * t + 6.0f * t2);
-      dsw = -30.0f * t2 * (1.0f - 2.0f * t + t2) * iw;
+      sw = fmaf(-(t2 * t), fmaf(6.0f, t2, fmaf(-15.0f, t, 10.0f)), 1.0f);
+      dsw = -30.0f * t2 * (fmaf(-2.0f, t, 1.0f) + t2) * iw;
     }
     A.e += (double)(-c6 * damp * sw);
     float tc = 0.0f;
@@ -313,18 +321,18 @@ __global__ __launch_bounds__(256) void d3_pair_kernel(const float4* __restrict__
       pe = fmaf(pe, tt, 2.838921720e-01f);
       pe = fmaf(pe, tt, 2.820105286e-01f);
       const float ec = pe * tt * ex;
-      const float w = ec * inv - sv + (P.d - Rc) * slope;
+      const float w = fmaf(P.d - Rc, slope, fmaf(ec, inv, -sv));
       A.ec += (double)(w * qc_i * qj);
       if (GRAD) {
-        qb += w * qj;
-        tc = kratio * (-ec * inv * inv - two_a_sqrtpi * ex * inv + slope) * qc_i * qj;
+        qb = fmaf(w, qj, qb);
+        tc = kratio * fmaf(-ec * inv, inv, fmaf(-two_a_sqrtpi * ex, inv, slope)) * qc_i * qj;
       }
     }
     if (GRAD) {
-      const float ddamp = -6.0f * P3.s6 * d4 * db * i6 * i6 - 8.0f * P3.s8 * qq * d6 * db * i8 * i8;
-      const float de = -c6 * (ddamp * sw + damp * dsw) * BOHR_INV_F;  // d e_ij / d d_ij per Angstrom, C6 held fixed
+      const float ddamp = fmaf(-8.0f * P3.s8 * qq * d6 * db * i8, i8, -6.0f * P3.s6 * d4 * db * i6 * i6);
+      const float de = -c6 * fmaf(ddamp, sw, damp * dsw) * BOHR_INV_F;  // d e_ij / d d_ij per Angstrom, C6 held fixed
       d3_add<STRESS>(A, de + tc, P.ux, P.uy, P.uz, P.d);
-      if (has) dcn += -damp * sw * (G - c6 * H) * invD;
+      if (has) dcn = fmaf(-damp * sw * fmaf(-c6, H, G), invD, dcn);
     }
   };
   for (int m = lane; m < cnt; m += 128) {  // two list slots per trip, all of their loads issued before the arithmetic
@@ -354,7 +362,7 @@ __global__ __launch_bounds__(256) void d3_pair_kernel(const float4* __restrict__
     const float cs = -(sv * 0.5f + al * 0.56418958354775629f);
     if (GRAD) qb = wave_sum(qb);
     if (lane == 0) {
-      ecoul[i] += 2.0 * (double)cp.factor * (double)(cs * qc_i * qc_i);
+      ecoul[i] = fma(2.0 * (double)cp.factor, (double)(cs * qc_i * qc_i), ecoul[i]);
       if (GRAD) qbar[i] += 2.0f * cp.factor * qb + 4.0f * cp.factor * cs * qc_i;
     }
   }

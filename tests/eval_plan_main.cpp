@@ -2,11 +2,12 @@
 // It includes the header aimnet_engine_eval includes and calls the functions it calls - eval_validate, eval_validate_lists,
 // eval_plan, layout_plan - over the product of
 //   periodic or not  x  caller-supplied lists (none, nbmat, + nbmat_lr, + nbmat_d3, all three)  x  the five Coulomb methods
-//   x  D3 (off, same cutoff, another cutoff)  x  (energy, forces, forces + stress)  x  nq 1 / 2  x  domain decomposition on / off
+//   x  D3 (off, same cutoff, another cutoff)  x  (energy, forces, stress alone, forces + stress)  x  nq 1 / 2
+//   x  domain decomposition on / off
 //   x  max_nb_lr 0 / 600  x  N in {8, 300, 1025, 3000, 40000}  x  n_mol 1 / 2  x  the split format (none, bf16x3, fp16x2)
 // and, of the 11 engine switches and 5 size predicates the plan reads (16 binary knobs), every setting that differs from all-on in
 // at most two knobs and from all-off in at most one - a SAMPLE: the full 2^16 product over that shape list takes minutes under the
-// sanitizers, this one about ten seconds.  Requests that eval rejects are skipped by eval's own checks.
+// sanitizers, this one about a quarter of a minute.  Requests that eval rejects are skipped by eval's own checks.
 // What is asserted are the invariants that the stages of eval rely on - each job has exactly one owner, and whatever a stage reads
 // was produced before it - not a second copy of the plan's expressions.
 #include <cstdio>
@@ -123,6 +124,10 @@ static void check(const EvalRequest& rq) {
   if (P.rev_lookup == RevLookup::OnWalk) CHECK(walk, "lookup on the walk: the walk runs");
   if (P.rev_lookup == RevLookup::OnEnergyLaunch) CHECK(P.energy == EnergySum::OwnLaunch, "lookup on the energy launch: it is launched (before the gather)");
   if (P.pair_force_rides) CHECK(P.rev_hash && P.want_s, "the gather rides on a stress launch");
+  if (!P.want_f)  // energy only, stress alone (layout.xe may hold without the map): no force launch, so nothing is deferred to one
+    CHECK(!P.rev_hash && !P.pair_force_rides && P.energy != EnergySum::ForceRider && P.charges != ChargesBy::ForceRider,
+          "without a force request no job waits for the force gather or the force-negation launch");
+  if (P.energy == EnergySum::StressRider) CHECK(rq.pbc && walk, "the stress riders sum the energies after a walk has written the charges");
   // energies and charges: one owner each, and a deferred job has a launch to ride on
   if (!P.grad) CHECK(P.energy == EnergySum::OwnLaunch, "energy only: nothing to ride on");
   if (P.energy == EnergySum::StressRider) CHECK(P.want_s, "stress rider needs the stress launches");
@@ -145,7 +150,8 @@ static void check(const EvalRequest& rq) {
 
 int main() {
   const int Ns[] = {8, 300, 1025, 3000, 40000};
-  const unsigned flags[] = {0u, AIMNET_FORCES, AIMNET_FORCES | AIMNET_STRESS};
+  // stress alone: the request that has layout.xe (a gradient above split_max) without the reverse-pair map (no force gather)
+  const unsigned flags[] = {0u, AIMNET_FORCES, AIMNET_STRESS, AIMNET_FORCES | AIMNET_STRESS};
   const int coulombs[] = {AIMNET_COULOMB_NONE, AIMNET_COULOMB_SIMPLE, AIMNET_COULOMB_DSF, AIMNET_COULOMB_EWALD, AIMNET_COULOMB_PME};
   // knob settings: all-on with at most two knobs flipped, all-off with at most one
   static unsigned masks[2 + 2 * N_KNOBS + N_KNOBS * (N_KNOBS - 1) / 2];
