@@ -9,7 +9,8 @@
 //   ah bl and al bh into a third set that the epilogue scales by 1 / 4096.
 //
 // Kernel body, schedule (the ping-pong of two wave groups), launcher and tile choice are those of gemm_split.h, shared with
-// gemm_bf3a.hip; this file holds what the fp16x2 form decides (H2Fmt), its entry points and the format dispatch of both.
+// gemm_bf3a.hip, and so is what the fp16x2 form decides on the device (H2Operand, shared with gemm_head.hip); this file holds the
+// launcher's choices (H2Fmt), the entry points and the format dispatch of both.
 // LDS tiles: 16-row strips of [hi 1 KiB][lo 1 KiB] (gemm_h2_common.h), one DMA wave-instruction per plane of a strip.
 #include <math.h>
 #include <stdlib.h>
@@ -33,13 +34,8 @@ __global__ __launch_bounds__(512, 2) void gemm_h2_kernel(const unsigned short* _
   gemm_split_body<H2Fmt, EPI, SM, SN, WN, OUT3, NSA>(A3, lda3, Bt, ldb, M, N, K, bias, C, C3, ldc3, D, ldc, brow, ldbias, alt);
 }
 
-struct H2Fmt {
-  using frag = f16x8;
+struct H2Fmt : H2Operand {
   static constexpr const char* NAME = "gemm_h2";
-  static constexpr int FMT = SPLIT_H2, PLANES = split_planes(FMT);
-  static constexpr int NACC = 3;            // accumulator sets
-  static constexpr int ROW_BYTES = H2_ROWB;  // per row and 32-k step in memory
-  static constexpr int passes(int rows) { return (rows + 31) / 32; }  // DMA wave-instructions per wave of the issuing group (a pass = 4 KiB = 2 strips)
   // Ring depth.  NSA = activation ring depth (weights: nsb).  2: the activation tile is requested ONE step ahead (weights: two).
   // 3: two steps ahead as well; 4: both three steps ahead -
   // for launches that leave CUs idle (a few hundred to ~2 000 rows): there a step is as long as the request's latency whatever the
@@ -50,45 +46,6 @@ struct H2Fmt {
   static int ring_depth(int tiles) { return 2 * tiles <= device_cus() ? g_h2_deep : 2; }  // at most half of the CUs busy: longer request lead
   template <int EPI, int SM, int SN, int WN, bool OUT3, int NSA>
   static constexpr auto kernel() { return &gemm_h2_kernel<EPI, SM, SN, WN, OUT3, NSA>; }
-
-  // DMA of the issuing group: pass p, wave w4 -> KiB q = 4 p + w4 of the stage = plane q & 1 of the 16-row strip q >> 1; lane ->
-  // row (lane >> 2) of the strip, slot lane & 3 holding k-chunk slot ^ swz(row).  Strips beyond the tile (padding of the last
-  // pass) re-read the last row into the stage's padding; rows beyond the matrix re-read its last row.
-  static __device__ __forceinline__ unsigned goff(int p, int w4, int lane, int tile_rows, int r0, int rlim, unsigned ldbytes) {
-    const int q = p * 4 + w4;
-    const int row = min((q >> 1) * 16 + (lane >> 2), tile_rows - 1), pl = q & 1;
-    const int kcx = (lane & 3) ^ swz_h2(row);
-    return (unsigned)(min(r0 + row, rlim) - r0) * ldbytes + pl * 64 + kcx * 16;
-  }
-  // fragment addresses: row r, plane P, k-chunk c = lane >> 4 -> (r >> 4) * 2048 + P * 1024 + (r & 15) * 64 + (c ^ swz(r)) * 16
-  static __device__ __forceinline__ unsigned frag_addr(int row0, int l16, int lc) {
-    return (row0 >> 4) * H2_STRIP + l16 * 64 + ((lc ^ swz_h2(l16)) << 4);
-  }
-  template <int SM, int SN>
-  static __device__ __forceinline__ void load_frags(frag (&fa)[SM][2], frag (&fb)[SN][2], unsigned oa, unsigned ob) {
-    read_strips_h<0, SN, 1>(fb, ob);
-    read_strips_h<0, SM, 0>(fa, oa);
-    read_strips_h<0, SN, 0>(fb, ob);
-    read_strips_h<0, SM, 1>(fa, oa);
-  }
-
-  // Accumulation.  The matrix pipe TRUNCATES the aligned sum of its 32 products and the accumulator towards minus infinity
-  // (gemm_bf3a.hip, "Accumulation"; profiles/r4_bf3_bias.txt): one-signed, it does not average out over atoms.  As there, the hi
-  // planes of the weights' ODD k-blocks are stored negated and the hi x hi products of even / odd k-steps go to two accumulator
-  // sets whose difference the epilogue takes.  The cross terms are 2^-12 of that sum: their own truncation is irrelevant and
-  // they share one set (activations carry the lo planes of the odd k-blocks negated, so both cross products keep their sign).
-  // acc[0], [1]: ah bh of the even / odd k-steps; [2]: the cross terms ah bl + al bh (x 4096)
-  static __device__ __forceinline__ f32x4 mfma(frag b, frag a, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, c, 0, 0, 0); }
-  template <int PAR, int SM, int SN>  // PAR: parity of the k-step
-  static __device__ __forceinline__ void products(f32x4 (&acc)[3][SM][SN], const frag (&fa)[SM][2], const frag (&fb)[SN][2]) {
-    split_product<H2Fmt, 2, 0, 1>(acc, fa, fb);
-    split_product<H2Fmt, PAR, 0, 0>(acc, fa, fb);
-    split_product<H2Fmt, 2, 1, 0>(acc, fa, fb);
-  }
-  template <int SM, int SN>
-  static __device__ __forceinline__ f32x4 total(const f32x4 (&acc)[3][SM][SN], int i, int j, float s0, float s1) {
-    return acc[0][i][j] * s0 + acc[1][i][j] * s1 + acc[2][i][j] * H2_INV_SCALE;
-  }
 };
 
 // (A one-instruction-stream-per-wave schedule - fragments of step j+1 fetched into the registers step j's products release, one

@@ -35,7 +35,7 @@ int gemm_set_attributes();
 constexpr int BF3_NO_NEG = 1 << 30;
 // neg_from_block = BF3_ALT: every ODD k-block is stored negated - the operand form of gemm_bf3a.hip / gemm_head.hip, which keep two
 // accumulator sets (even / odd k-steps) and subtract them in the epilogue: the one-signed truncation of the bf16 MFMA accumulation
-// hits two interleaved half-sums of identical statistics and cancels without a tunable split point (gemm_bf3a.hip, "Accumulation")
+// hits two interleaved half-sums of identical statistics and cancels without a tunable split point (gemm_split.h, "Accumulation")
 constexpr int BF3_ALT = -2;
 void split_bf3_host(const float* w, int rows, int K, unsigned short* out, int neg_from_block);                 // host form (weights)
 int launch_split_bf3(hipStream_t s, const float* src, int ld, int M, int K, unsigned short* dst, int ldd,
@@ -116,17 +116,18 @@ int launch_gemm_chain(hipStream_t stream, int shape, const ChainArgs& a);
 // kb0 .. kb0 + nk - 1, in the order the kernel consumes them
 void chain_pack_weights(const unsigned short* w2, int n_rows, int ldk, int n0, int nw, int nt, int kb0, int nk, std::vector<unsigned short>& out);
 
-// ---- gemm_head.hip: the energy head 256 -> 128 -> 128 -> 1 forward and backward in one launch (operands of gemm_bf3a.hip)
+// ---- gemm_head.hip: the energy head 256 -> 128 -> 128 -> 1 forward and backward in one launch, on the split operands of
+// gemm_split.h; P = split_planes(fmt) planes of 16-bit elements per value (3 in the bf16x3 form, 2 in the fp16x2 form)
 struct HeadFusedArgs {
-  const unsigned short* aim3;  // [M][lda3] head input in bf3 form (written by the last MLP layer's epilogue)
+  const unsigned short* aim3;  // [M][lda3] head input in split form (written by the last MLP layer's epilogue)
   int lda3;
-  const unsigned short *w1, *w2, *w2t, *w1t;  // bf3 weights (BF3_ALT): W1 [128][3*256], W2 [128][3*128], W2^T [128][3*128], W1^T [256][3*128]
+  const unsigned short *w1, *w2, *w2t, *w1t;  // split weights: W1 [128][P*256], W2 [128][P*128], W2^T [128][P*128], W1^T [256][P*128],
+                                              // odd k-blocks negated as the format's GEMM wants them (BF3_ALT / H2_WEIGHT)
   const float *b1, *b2, *w3, *b3;             // biases [128], last layer [128] and its bias [1]
-  // (the four weight operands are in the BF3_ALT form: odd k-blocks negated)
   const float* dlast;                         // GELU' of the layer that produced the head input, fp32 [M][ldd] (grad only)
   int ldd;
   float* e_atom;                              // [M]
-  unsigned short* zbar3;                      // [M][ldz3] adjoint of that layer's pre-activation, bf3 form (grad only)
+  unsigned short* zbar3;                      // [M][ldz3] adjoint of that layer's pre-activation, split form (grad only)
   int ldz3;
   int M, grad;
   int fmt = SPLIT_BF3;  // SPLIT_BF3: operands in the bf16x3 form (BF3_ALT weights), SPLIT_H2: in the fp16x2 form (H2_WEIGHT weights, H2_ACT activations)
