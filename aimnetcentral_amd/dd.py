@@ -26,14 +26,13 @@ evaluates the whole system in 1.2 ms; decomposition is for systems beyond one GP
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Any
 
 import numpy as np
 
 from . import _lib
-from .engine import NONFINITE_FLAG, _round16, describe_input_flags
+from .engine import NONFINITE_FLAG, describe_input_flags
 
 DD_SUM, DD_CHARGES, DD_ROWS = 0, 1, 2  # AIMNET_DD_* of include/aimnet_hip.h
 EXCHANGE_FN = _lib.DD_EXCHANGE_FN
@@ -290,6 +289,7 @@ class DomainDecomposedEngine:
              dsf_rc: float = 15.0, dsf_alpha: float = 0.2, dftd3: dict[str, float] | None = None, halo: float | None = None,
              axis: int | None = None, grid=None) -> dict[str, Any]:
         import torch
+        import torch.distributed as dist
 
         eng = self.engine
         if coulomb not in ("none", "dsf"):
@@ -338,25 +338,11 @@ class DomainDecomposedEngine:
                         raise ex.error
                     raise
                 # the row capacities must grow on EVERY rank together (a rank that repeated its evaluation alone would leave the
-                # others waiting in a collective): status words max-reduced over the group, then the engine's own growth rule
-                import torch.distributed as dist
-
+                # others waiting in a collective): status words max-reduced over the group, then the engine's own growth rule (capacity.py)
                 st = self.all_reduce_(res["status"].clone(), op=dist.ReduceOp.MAX).cpu().numpy()
-                flags = int(st[6]) & ~NONFINITE_FLAG
-                if flags:
-                    raise ValueError("DomainDecomposedEngine: invalid input: " + describe_input_flags(flags, 1))
-                retry = False
-                if st[2]:
-                    eng.max_nb = _round16(int(max(eng.max_nb * 1.5, st[0])))
-                    retry = True
-                if st[3]:
-                    eng._max_nb_lr[float(dsf_rc)] = _round16(int(max(eng._max_nb_lr[float(dsf_rc)] * 1.5, st[1])))
-                    retry = True
-                if st[5]:  # DFT-D3 matrix (it may live in the long-range buffers: grow both, as HipEngine.eval does)
-                    d3_rc = float(dftd3.get("cutoff", 15.0))
-                    eng._max_nb_lr[d3_rc] = _round16(int(max(eng._lr_capacity(d3_rc) * 1.5, st[4], st[1])))
-                    retry = True
-                if not retry:
+                if int(st[6]) & ~NONFINITE_FLAG:
+                    raise ValueError("DomainDecomposedEngine: invalid input: " + describe_input_flags(int(st[6]) & ~NONFINITE_FLAG, 1))
+                if not eng.grow(st, *eng._last_request):  # (the options and the request of the evaluation just made)
                     break
         finally:
             _lib.check(eng.lib.aimnet_engine_set_dd(eng._h, None, EXCHANGE_FN(), None), "aimnet_engine_set_dd")

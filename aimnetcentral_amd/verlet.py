@@ -22,7 +22,8 @@ from __future__ import annotations
 
 from typing import Any
 
-from .engine import HipEngine, NeighborOverflowError, _round16, neighbor_list, same_cutoff
+from .capacity import grown, round16, same_cutoff, start_capacity
+from .engine import HipEngine, NeighborOverflowError, neighbor_list
 
 
 class VerletSkinLists:
@@ -55,16 +56,14 @@ class VerletSkinLists:
         self._key = None
 
     def _build_one(self, coord, cutoff: float, mol_idx, cell, pbc):
-        import math
-
-        cap = self._cap.get(cutoff) or _round16(int(0.2 * 4.0 / 3.0 * math.pi * cutoff**3))
+        cap = self._cap.get(cutoff) or start_capacity(cutoff)
         while True:
             nbmat, _num, shifts, xw, (longest, overflow) = neighbor_list(coord, cutoff, mol_idx, cell, pbc, max_nb=cap)
             if not overflow:
                 break
-            cap = _round16(int(max(cap * 1.5, longest)))  # AdaptiveNeighborList growth rule, neighbors.py:127-130
+            cap = grown(cap, longest)
         self._cap[cutoff] = cap
-        width = max(16, _round16(longest))
+        width = max(16, round16(longest))
         return nbmat[:, :width].contiguous(), (shifts[:, :width].contiguous() if shifts is not None else None), xw
 
     def _build(self, coord, mol_idx, cell, pbc, need_lr: float | None, need_d3: float | None) -> None:
@@ -100,7 +99,7 @@ class VerletSkinLists:
         # with caller-supplied matrices DSF runs over a matrix (no grid walk); 'simple' sums all pairs of a molecule and needs none
         need_lr = float(dsf_rc) if coulomb == "dsf" else None
         # one cutoff for DSF and D3: ONE matrix serves both terms (include/aimnet_hip.h: pass it as nbmat_lr only)
-        # (equal as the engine compares them: on the float32 values of its options, engine.same_cutoff)
+        # (equal as the engine compares them: on the float32 values of its options, capacity.same_cutoff)
         need_d3 = d3_rc if (d3_rc is not None and not (need_lr is not None and same_cutoff(d3_rc, need_lr))) else None
         # what the matrices depend on, as far as the host knows it without a read: shapes, periodicity, cutoffs; the CONTENTS of
         # mol_idx and of the cell are compared on the device below (`numbers` does not enter a neighbour matrix at all)
