@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_eval",
     "aimnet_engine_hvp_workspace_bytes",
     "aimnet_engine_hvp",
+    "aimnet_engine_charge_response_workspace_bytes",
+    "aimnet_engine_charge_response",
     "aimnet_engine_debug_view",
     "aimnet_engine_set_profiling",
     "aimnet_engine_set_profile_sampling",
@@ -200,6 +202,10 @@ def load() -> C.CDLL:
     lib.aimnet_engine_hvp_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(EvalOptions)]
     lib.aimnet_engine_hvp.restype = C.c_int
     lib.aimnet_engine_hvp.argtypes = [vp, C.POINTER(Inputs), C.POINTER(EvalOptions), vp, i32, vp, vp, vp, vp, sz, vp]
+    lib.aimnet_engine_charge_response_workspace_bytes.restype = sz
+    lib.aimnet_engine_charge_response_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(EvalOptions)]
+    lib.aimnet_engine_charge_response.restype = C.c_int
+    lib.aimnet_engine_charge_response.argtypes = [vp, C.POINTER(Inputs), C.POINTER(EvalOptions), vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.aimnet_engine_debug_view.restype = C.c_int
     lib.aimnet_engine_debug_view.argtypes = [vp, C.c_char_p, C.POINTER(sz), C.POINTER(sz), C.POINTER(i32), C.POINTER(i32)]
     lib.aimnet_engine_set_profiling.restype = C.c_int

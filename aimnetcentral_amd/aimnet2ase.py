@@ -157,6 +157,20 @@ class AIMNet2ASE(Calculator):
         n = H.shape[0]
         return H.reshape(n * 3, n * 3).cpu().numpy()
 
+    def get_dipole_derivatives(self, atoms=None):
+        """d mu / d x as a (3N, 3) array (row 3 i + a: atom i, Cartesian component a), the companion of get_hessian() for IR
+        intensities (vibrations.ir_intensities); analytic, from the forward tangent sweep."""
+        atoms = getattr(self, "atoms", None) if atoms is None else atoms
+        if atoms is None:
+            raise PropertyNotImplementedError("get_dipole_derivatives() requires an attached Atoms object or an explicit argument.")
+        if np.asarray(atoms.pbc).any():
+            raise PropertyNotImplementedError("The dipole moment of a periodic system is not defined: no dipole derivatives.")
+        self._charge_from_info(atoms)
+        P = self.base_calc.dipole_derivatives({"coord": np.asarray(atoms.positions, dtype=np.float32), "numbers": np.asarray(atoms.numbers),
+                                               "charge": float(self.charge), "mult": float(self.mult)},
+                                              validate_species=self.validate_species)
+        return P.detach().reshape(-1, 3).cpu().numpy()
+
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
         if properties is None:
             properties = ["energy"]

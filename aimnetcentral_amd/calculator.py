@@ -22,7 +22,9 @@ Deliberate deviations, all loud:
     at fp32 round-off (the external DFT-D3 block: a central difference of the D3 gradient alone, inside the same call), for
     every Coulomb method but "pme" - the exact Ewald sum is carried by the sweep, the mesh takes differences of forces.  The
     finite-difference operator over the analytic forces (`_fd_hvp`, `hvp_method = "fd"`) is kept as the cross-check;
-    create_graph=True raises (there is no autograd graph).
+    create_graph=True raises (there is no autograd graph);
+  * `charge_response` and `dipole_derivatives` (d q / d x and d mu / d x from the forward half of that sweep) have no reference
+    counterpart; they are methods, not keys of `eval`, and refuse periodic dipoles.
 """
 from __future__ import annotations
 
@@ -785,6 +787,46 @@ class AIMNet2Calculator:
             raise ValueError(f"vectors must have shape ({n}, 3) or (K, {n}, 3), got {tuple(v.shape)}")
         hv = self._hvp(d, v.reshape(-1, n, 3), eps)
         return hv.view_as(v)
+
+    def charge_response(self, data: dict[str, Any], vectors, *, validate_species: bool = True) -> dict[str, Any]:
+        """The charges of one structure and their derivatives along `vectors` (N,3) or (K,N,3), from the forward tangent sweep
+        (HipEngine.charge_response): `charges` (N,), `dq` (N,) or (K,N), for NSE models `dspin` (tangent of the spin charges), and
+        without a cell `dipole_derivative` (3,) or (K,3), the tangent of sum q x.  No reference counterpart.  The charges see
+        neither the Coulomb method nor a dispersion term, so neither is consulted."""
+        import torch
+
+        if validate_species:
+            self._validate_species_and_charge(data)
+        self._maybe_warn_mult_ignored(data)
+        d = self._single_structure(data, "charge_response")
+        v = torch.as_tensor(vectors, dtype=torch.float32, device=self.device)
+        n = d["coord"].shape[0]
+        if v.shape[-2:] != (n, 3) or v.ndim not in (2, 3):
+            raise ValueError(f"vectors must have shape ({n}, 3) or (K, {n}, 3), got {tuple(v.shape)}")
+        pbc3 = (True, True, True)
+        if d.get("pbc") is not None:
+            pbc3 = tuple(bool(x) for x in d["pbc"].detach().cpu().numpy().astype(bool).reshape(-1)[:3])
+        res = self.engine.charge_response(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
+                                          self._engine_charge(d["charge"], d.get("mult")), v.reshape(-1, n, 3), cell=d.get("cell"),
+                                          pbc=pbc3)
+        lead = v.shape[:-2]
+        out = {"charges": res["charges"], "dq": res["dq"].view(*lead, n)}
+        if "dspin" in res:
+            out["dspin"] = res["dspin"].view(*lead, n)
+        if "dmu" in res:
+            out["dipole_derivative"] = res["dmu"].view(*lead, 3)
+        return out
+
+    def dipole_derivatives(self, data: dict[str, Any], *, validate_species: bool = True):
+        """The polar tensor P[i,a,b] = d mu_b / d x_ia of one non-periodic structure, (N,3,3), from the 3N unit directions in one
+        charge_response call (what a vibrational analysis contracts with the normal modes: vibrations.ir_intensities)."""
+        import torch
+
+        if data.get("cell") is not None:
+            raise ValueError("dipole_derivatives: the dipole moment of a periodic cell is not defined")
+        n = int(torch.as_tensor(data["coord"]).shape[-2])
+        eye = torch.eye(3 * n, device=self.device, dtype=torch.float32).view(3 * n, n, 3)
+        return self.charge_response(data, eye, validate_species=validate_species)["dipole_derivative"].view(n, 3, 3)
 
 
 class _ExternalDftD3State:

@@ -875,6 +875,7 @@ struct HvpWs {
   EwaldBuffers ew;  // Ewald summation: per-system parameters, fractional coordinates, k entries (ewald.hip)
   double* ew_tk;    // [K][max_k][2] tangent structure factors (t_P, t_Q)
   float* ew_qtot;   // [N] alpha + beta of a two-channel model
+  float* qsum;      // [N] (aimnet_engine_charge_response) alpha + beta of every atom, read by crs_dipole_kernel
   // external DFT-D3 block (4 K displaced copies as one batch)
   int *d3_idx, *d3_shift, *d3_cnt, *aslot, *d3c_idx, *d3c_shift, *d3c_cnt, *d3c_mol, *d3c_aslot;
   unsigned long long* present_part;
@@ -1043,6 +1044,147 @@ int mlp_backward(const aimnet_engine* e, hipStream_t s, const std::vector<Layer>
   return 0;
 }
 
+// pass p of the forward + tangent sweep: conv -> MLP, then (`nse`) the NSE charge update and (`update_a`) a^{p+1} = a^p + delta_a.
+// aimnet_engine_hvp runs every pass through here and the head after them; aimnet_engine_charge_response stops after the charges of
+// pass np-2.
+int forward_pass(const aimnet_engine* e, hipStream_t s, const aimnet_inputs* in, const float* vectors, int p, int K, int cap, bool nse,
+                 bool update_a, HvpWs& W) {
+  const int N = in->n_atoms, n_mol = in->n_mol, nq = e->nq;
+  const size_t kn = (size_t)K * N;
+  const dim3 gik(N, K), gmk(n_mol, K), b256(256);
+  const std::vector<Layer>& Ls = e->mlp[p];
+  const int nl = (int)Ls.size(), ldx = Ls[0].k_in;
+  AIMNET_HIP_CHECK(hipMemsetAsync(W.x[p], 0, (size_t)N * ldx * sizeof(float), s));    // padding columns
+  AIMNET_HIP_CHECK(hipMemsetAsync(W.tx[p], 0, kn * ldx * sizeof(float), s));
+  const float* a_p = p == 0 ? e->afv : W.a[p];
+  const int* row_of = p == 0 ? in->numbers : nullptr;
+  const float *q_p = p > 0 ? W.q[p - 1] : nullptr, *tq_p = p > 0 ? W.tq[p - 1] : nullptr;
+#define HVP_CONV_FWD(NQV)                                                                                                       \
+  hipLaunchKernelGGL((hvp_conv_fwd_kernel<NQV>), gik, b256, 0, s, a_p, row_of, W.ta[p], q_p, tq_p, W.nb_idx, W.nb_cnt, W.pg, cap, \
+                     vectors, e->agh_a, e->agh_q, e->bp, W.x[p], W.tx[p], ldx, W.V[p], W.tV[p], W.Vq[p], W.tVq[p], N)
+  if (p == 0) HVP_CONV_FWD(0);
+  else if (nq == 1) HVP_CONV_FWD(1);
+  else HVP_CONV_FWD(2);
+#undef HVP_CONV_FWD
+  AIMNET_LAUNCH_CHECK();
+  RC(mlp_forward(e, s, Ls, nl, e->arch.last_linear[p] != 0, W.x[p], N, K, W.z[p], W.y[p], W));
+  if (nse) {
+    hipLaunchKernelGGL(hvp_nse_fwd_kernel, gmk, b256, 0, s, W.y[p], W.ty[p], Ls[nl - 1].k_out, nq, q_p, tq_p, W.nl.mol_start,
+                       in->charge, n_mol, N, W.q[p], W.tq[p], W.Fm[p], W.Dm[p], W.tFm[p], W.tDm[p]);
+    AIMNET_LAUNCH_CHECK();
+  }
+  if (update_a) {
+    const size_t n_t = kn * NF;
+    hipLaunchKernelGGL(hvp_update_a_kernel, grid1(n_t), b256, 0, s, a_p, row_of, W.ta[p], W.y[p], W.ty[p], Ls[nl - 1].k_out,
+                       2 * nq, N, n_t, W.a[p + 1], W.ta[p + 1]);
+    AIMNET_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---- charge response: the final NSE charges and their tangents, and the dipole tangent ------------------------------------
+// thread = (direction k, atom i) over the channel-major q [nq][N] / tq [K][nq][N]: dq = sum_ch tq, dspin = tq[0] - tq[1]; the
+// k == 0 part of the grid writes the total charges (qtot: the copy crs_dipole_kernel reads; charges: the caller's, may be NULL)
+__global__ void crs_out_kernel(const float* __restrict__ q, const float* __restrict__ tq, int nq, int N, size_t n_t,
+                               float* __restrict__ qtot, float* __restrict__ charges, float* __restrict__ dq,
+                               float* __restrict__ dspin) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_t) return;
+  const size_t k = e / (size_t)N, i = e % (size_t)N;
+  const float t0 = tq[(k * nq) * N + i], t1 = nq == 2 ? tq[(k * nq + 1) * N + i] : 0.0f;
+  dq[e] = t0 + t1;
+  if (dspin) dspin[e] = t0 - t1;
+  if (k == 0) {
+    const float qv = q[i] + (nq == 2 ? q[(size_t)N + i] : 0.0f);
+    qtot[i] = qv;
+    if (charges) charges[i] = qv;
+  }
+}
+
+// block = (molecule, direction), as hvp_nse_fwd_kernel: t_mu[k][m] = sum_i dq[k][i] x_i + q_i v[k][i] over the atoms of the
+// molecule, x as the caller gave it.  fp32 products, summed in double (strided loop, wave_sum, the four waves in index order):
+// no atomics, the same bits whatever the number of directions.
+__global__ __launch_bounds__(256) void crs_dipole_kernel(const float* __restrict__ dq, const float* __restrict__ qtot,
+                                                        const float* __restrict__ x, const float* __restrict__ tv,
+                                                        const int* __restrict__ mol_start, int n_mol, int N,
+                                                        float* __restrict__ dmu) {
+  __shared__ double sh[4];
+  const int m = blockIdx.x, k = blockIdx.y;
+  const int i0 = mol_start[m], i1 = mol_start[m + 1];
+  const float* tvk = tv + (size_t)k * N * 3;
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+    const float d = dq[(size_t)k * N + i], qi = qtot[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += (double)__fmul_rn(d, x[3 * (size_t)i + c]) + (double)__fmul_rn(qi, tvk[3 * (size_t)i + c]);
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double v = block_sum256(acc[c], sh);
+    if (threadIdx.x == 0) dmu[((size_t)k * n_mol + m) * 3 + c] = (float)v;
+  }
+}
+
+// workspace of aimnet_engine_charge_response: the short-range list and what the kernels of passes 0 .. np-2 touch.  Only the
+// charges (and a^p, which the next pass reads while it is updated) outlive a pass: the MLP input rows, the z rows, the moments V
+// and the NSE sums are ONE set of buffers that every pass writes again.  The fields of HvpWs it leaves alone stay null.
+void crs_layout(const aimnet_engine* e, int N, int n_mol, int K, const aimnet_eval_options* opt, char* base, HvpWs& W) {
+  W = HvpWs{};
+  Carver c{base};
+  const size_t n = (size_t)N, kn = (size_t)K * N;
+  const int npq = e->arch.n_pass - 1, nq = e->nq;  // passes 0 .. np-2 run
+  const int cap = std::max(1, opt->max_nb);
+  char* nl_base = c.take<char>(nlist_scratch_bytes(N, n_mol));
+  if (base) nlist_carve(W.nl, nl_base, N, n_mol);
+  W.nb_idx = c.take<int>(n * cap);
+  W.nb_shift = c.take<int>(n * cap);
+  W.nb_cnt = c.take<int>(n);
+  W.pg = c.take<float4>(n * cap);
+  int ldx = 0, ldy = 0, wz[AIMNET_MAX_LAYERS] = {};
+  bool y_own = false;
+  for (int p = 0; p < npq; ++p) {
+    const int nl = (int)e->mlp[p].size();
+    ldx = std::max(ldx, e->mlp[p][0].k_in);
+    for (int l = 0; l < nl; ++l) wz[l] = std::max(wz[l], e->mlp[p][l].k_out);
+    if (!e->arch.last_linear[p]) {
+      y_own = true;
+      ldy = std::max(ldy, e->mlp[p][nl - 1].k_out);
+    }
+  }
+  float* x = c.take<float>((n + kn) * ldx);
+  float* z[AIMNET_MAX_LAYERS] = {};
+  for (int l = 0; l < AIMNET_MAX_LAYERS; ++l)
+    if (wz[l]) z[l] = c.take<float>((n + kn) * wz[l]);
+  float* y = y_own ? c.take<float>((n + kn) * ldy) : nullptr;
+  float *V = c.take<float>(n * NV * 3), *tV = c.take<float>(kn * NV * 3);
+  float *Vq = c.take<float>(n * nq * H_ * 3), *tVq = c.take<float>(kn * nq * H_ * 3);
+  float *Fm = c.take<float>((size_t)n_mol * nq), *Dm = c.take<float>((size_t)n_mol * nq);
+  float *tFm = c.take<float>((size_t)K * n_mol * nq), *tDm = c.take<float>((size_t)K * n_mol * nq);
+  for (int p = 0; p < npq; ++p) {
+    W.a[p] = p == 0 ? nullptr : c.take<float>(n * NF);
+    W.ta[p] = p == 0 ? nullptr : c.take<float>(kn * NF);
+    W.q[p] = c.take<float>(n * nq);
+    W.tq[p] = c.take<float>(kn * nq);
+    const int nl = (int)e->mlp[p].size(), lx = e->mlp[p][0].k_in;
+    W.x[p] = x;
+    W.tx[p] = x ? x + n * lx : nullptr;
+    for (int l = 0; l < nl; ++l) {
+      W.z[p][l] = z[l];
+      W.tz[p][l] = z[l] ? z[l] + n * e->mlp[p][l].k_out : nullptr;
+    }
+    const bool lin = e->arch.last_linear[p] != 0;
+    W.y[p] = lin ? W.z[p][nl - 1] : y;
+    W.ty[p] = lin ? W.tz[p][nl - 1] : (y ? y + n * e->mlp[p][nl - 1].k_out : nullptr);
+    W.V[p] = V, W.tV[p] = tV, W.Vq[p] = Vq, W.tVq[p] = tVq;
+    W.Fm[p] = Fm, W.Dm[p] = Dm, W.tFm[p] = tFm, W.tDm[p] = tDm;
+  }
+  int mw = 0;  // widest hidden row of these passes (not the energy head's)
+  for (int l = 0; l < AIMNET_MAX_LAYERS; ++l) mw = std::max(mw, wz[l]);
+  for (int b = 0; b < 2; ++b) W.h[b] = c.take<float>((n + kn) * mw);
+  W.qsum = c.take<float>(n);
+  W.total = align_up(c.off, 256);
+}
+
 }  // namespace
 }  // namespace aimnet
 
@@ -1156,40 +1298,14 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
                           status + 7));
 
   // ---- forward + tangent ----
-  const dim3 gik(N, K), gmk(n_mol, K), gwk(ceil_div(N, 4), K), b256(256);
-  for (int p = 0; p < np; ++p) {
-    const std::vector<Layer>& Ls = e->mlp[p];
-    const int nl = (int)Ls.size(), ldx = Ls[0].k_in;
-    AIMNET_HIP_CHECK(hipMemsetAsync(W.x[p], 0, (size_t)N * ldx * sizeof(float), s));    // padding columns
-    AIMNET_HIP_CHECK(hipMemsetAsync(W.tx[p], 0, kn * ldx * sizeof(float), s));
-    const float* a_p = p == 0 ? e->afv : W.a[p];
-    const int* row_of = p == 0 ? in->numbers : nullptr;
-    const float *q_p = p > 0 ? W.q[p - 1] : nullptr, *tq_p = p > 0 ? W.tq[p - 1] : nullptr;
-#define HVP_CONV_FWD(NQV)                                                                                                       \
-  hipLaunchKernelGGL((hvp_conv_fwd_kernel<NQV>), gik, b256, 0, s, a_p, row_of, W.ta[p], q_p, tq_p, W.nb_idx, W.nb_cnt, W.pg, cap, \
-                     vectors, e->agh_a, e->agh_q, e->bp, W.x[p], W.tx[p], ldx, W.V[p], W.tV[p], W.Vq[p], W.tVq[p], N)
-    if (p == 0) HVP_CONV_FWD(0);
-    else if (nq == 1) HVP_CONV_FWD(1);
-    else HVP_CONV_FWD(2);
-#undef HVP_CONV_FWD
-    AIMNET_LAUNCH_CHECK();
-    RC(mlp_forward(e, s, Ls, nl, ar.last_linear[p] != 0, W.x[p], N, K, W.z[p], W.y[p], W));
-    if (p < np - 1) {
-      hipLaunchKernelGGL(hvp_nse_fwd_kernel, gmk, b256, 0, s, W.y[p], W.ty[p], Ls[nl - 1].k_out, nq, q_p, tq_p, W.nl.mol_start,
-                         in->charge, n_mol, N, W.q[p], W.tq[p], W.Fm[p], W.Dm[p], W.tFm[p], W.tDm[p]);
-      AIMNET_LAUNCH_CHECK();
-      const size_t n_t = kn * NF;
-      hipLaunchKernelGGL(hvp_update_a_kernel, grid1(n_t), b256, 0, s, a_p, row_of, W.ta[p], W.y[p], W.ty[p], Ls[nl - 1].k_out,
-                         2 * nq, N, n_t, W.a[p + 1], W.ta[p + 1]);
-      AIMNET_LAUNCH_CHECK();
-    }
-  }
+  for (int p = 0; p < np; ++p) RC(forward_pass(e, s, in, vectors, p, K, cap, p < np - 1, p < np - 1, W));
   const int nh = (int)e->head.size();
   {
     RC(mlp_forward(e, s, e->head, nh - 1, false, W.y[np - 1], N, K, W.hz, nullptr, W));
   }
 
   // ---- Coulomb seeds (+ tangents) of qbar / xbar ----
+  const dim3 gik(N, K), gmk(n_mol, K), gwk(ceil_div(N, 4), K), b256(256);
   CoulombParams cp = coulomb_params(ar, opt);
   int qb = 0;  // index of the live qbar buffers
   const float *q_fin = W.q[np - 2], *tq_fin = W.tq[np - 2];
@@ -1301,6 +1417,92 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
   AIMNET_HIP_CHECK(hipMemcpyAsync(hv, W.txbar, kn * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (forces) {
     hipLaunchKernelGGL(hvp_out_kernel, grid1((size_t)N * 3), b256, 0, s, W.xbar, (size_t)N * 3, forces);
+    AIMNET_LAUNCH_CHECK();
+  }
+  return AIMNET_OK;
+}
+
+size_t aimnet_engine_charge_response_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_vec,
+                                                     const aimnet_eval_options* opt) {
+  if (!e || !opt || n_atoms <= 0 || n_mol <= 0 || n_vec <= 0 || e->arch.n_pass < 2) return 0;
+  HvpWs W;
+  crs_layout(e, n_atoms, n_mol, n_vec, opt, nullptr, W);
+  return W.total;
+}
+
+int aimnet_engine_charge_response(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const float* vectors,
+                                  int32_t n_vec, float* charges, float* dq, float* dspin, float* dmu, int32_t* status,
+                                  void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!e || !in || !opt || !vectors || !status || !workspace || n_vec <= 0) return AIMNET_E_INVALID;
+  if (!dq) {
+    set_last_error("charge_response: dq is required");
+    return AIMNET_E_INVALID;
+  }
+  const int N = in->n_atoms, n_mol = in->n_mol, K = n_vec;
+  if (N <= 0 || n_mol <= 0 || !in->coord || !in->numbers || !in->mol_idx || !in->charge) {
+    set_last_error("charge_response: null or empty input");
+    return AIMNET_E_INVALID;
+  }
+  if (in->nbmat || in->nbmat_lr || in->nbmat_d3) {
+    set_last_error("charge_response: caller-supplied neighbour matrices are not read by the tangent sweep (it builds its own list)");
+    return AIMNET_E_INVALID;
+  }
+  if (n_vec > 65535) {  // the tangent kernels index the directions with grid.y
+    set_last_error("charge_response: at most 65535 directions per sweep (%d given): split them over several calls", n_vec);
+    return AIMNET_E_INVALID;
+  }
+  const aimnet_arch& ar = e->arch;
+  const int np = ar.n_pass, nq = e->nq;
+  if (np < 2) {
+    set_last_error("charge_response: a model with one pass has no charges");
+    return AIMNET_E_INVALID;
+  }
+  if (dspin && nq != 2) {
+    set_last_error("charge_response: dspin is defined for two charge channels; this model has one");
+    return AIMNET_E_INVALID;
+  }
+  const bool pbc = in->cell != nullptr;
+  if (dmu && pbc) {
+    set_last_error("charge_response: the dipole moment of a periodic cell is not defined (pass dmu = NULL)");
+    return AIMNET_E_INVALID;
+  }
+  if (pbc && !(in->n_cell == 1 || in->n_cell == n_mol)) {
+    set_last_error("charge_response: n_cell must be 1 or n_mol");
+    return AIMNET_E_INVALID;
+  }
+  if ((size_t)K * (size_t)N * (size_t)max_width(e) >= (size_t)INT32_MAX) {
+    set_last_error("charge_response: n_vec * n_atoms too large for one sweep (split the directions)");
+    return AIMNET_E_INVALID;
+  }
+  hipStream_t s = (hipStream_t)hip_stream;
+  AIMNET_HIP_CHECK(hipSetDevice(e->device));
+  HvpWs W;
+  crs_layout(e, N, n_mol, K, opt, (char*)workspace, W);
+  if (W.total > workspace_bytes) {
+    set_last_error("charge_response: workspace too small (%zu < %zu)", workspace_bytes, W.total);
+    return AIMNET_E_WORKSPACE;
+  }
+  const int cap = std::max(1, opt->max_nb);
+  const int n_cell = pbc ? in->n_cell : 0;
+
+  // ---- the short-range list + pair geometry, as aimnet_engine_hvp builds them ----
+  AIMNET_HIP_CHECK(hipMemsetAsync(status, 0, 8 * sizeof(int), s));
+  RC(launch_mol_start(s, in->mol_idx, N, n_mol, W.nl.mol_start, W.nl.mol_c, in->numbers, status + 6, nullptr, nullptr, nullptr));
+  const int* mol_c = W.nl.mol_c;
+  RC(launch_wrap(s, in->coord, mol_c, N, n_mol, in->cell, n_cell, in->pbc, W.nl, in->pbc_sys, pbc ? ar.rc : 0.0f));
+  if (!pbc && bbox_applies(N, n_mol)) RC(launch_bbox(s, n_mol, W.nl));
+  RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, ar.rc, ar.rc, cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
+                  status + 0, status + 2, W.pg));
+
+  // ---- forward + tangent up to the NSE of pass np-2: the charges see nothing after it ----
+  for (int p = 0; p < np - 1; ++p) RC(forward_pass(e, s, in, vectors, p, K, cap, true, p < np - 2, W));
+
+  const size_t kn = (size_t)K * N;
+  hipLaunchKernelGGL(crs_out_kernel, grid1(kn), dim3(256), 0, s, W.q[np - 2], W.tq[np - 2], nq, N, kn, W.qsum, charges, dq, dspin);
+  AIMNET_LAUNCH_CHECK();
+  if (dmu) {
+    hipLaunchKernelGGL(crs_dipole_kernel, dim3(n_mol, K), dim3(256), 0, s, dq, W.qsum, in->coord, vectors, W.nl.mol_start, n_mol, N,
+                       dmu);
     AIMNET_LAUNCH_CHECK();
   }
   return AIMNET_OK;

@@ -505,6 +505,55 @@ class HipEngine(capacity.Capacities):
                 k0 += kc
         return {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}
 
+    def charge_response(self, coord, numbers, mol_idx, charge, vectors, cell=None, pbc=(True, True, True),
+                        want_dipole: bool | None = None) -> dict[str, Any]:
+        """The charges and their directional derivatives (csrc/hvp.hip, aimnet_engine_charge_response: the forward tangent half
+        of `hvp`, stopped at the final charges): vectors [K, N, 3] -> `charges` [N], `dq` [K, N], for a 2-channel model `dspin`
+        [K, N] (tangent of alpha - beta), and `dmu` [K, n_mol, 3], the tangent of every molecule's dipole moment sum q x.  Inputs
+        as `hvp`; no Coulomb method or dispersion term enters (the charges do not see them).  The dipole moment of a periodic
+        cell is not defined: `want_dipole` defaults to `cell is None` and `want_dipole=True` with a cell raises.  The K
+        directions are split into sweeps by HVP_BYTES_BUDGET with this entry's own (smaller) workspace per direction."""
+        import torch
+
+        if want_dipole is None:
+            want_dipole = cell is None
+        if want_dipole and cell is not None:
+            raise ValueError("HipEngine.charge_response: the dipole moment of a periodic cell is not defined (want_dipole=True with a cell)")
+        inp, t = self._inputs("hvp", coord, numbers, mol_idx, charge, cell, pbc)
+        n, n_mol, dev = inp.n_atoms, inp.n_mol, self.device
+        K = int(vectors.numel()) // (3 * n)
+        if K == 0:
+            raise ValueError("HipEngine.charge_response: empty input")
+        vectors = vectors.to(device=dev, dtype=torch.float32).reshape(-1, n, 3).contiguous()
+        rq = capacity.Request("hvp", n, n_mol, cell is not None, _lib.COULOMB_NONE, 0.0)  # the short-range rows are all it needs
+        res = {"charges": torch.empty(n, dtype=torch.float32, device=dev), "dq": torch.empty(K, n, dtype=torch.float32, device=dev)}
+        if self.nq == 2:
+            res["dspin"] = torch.empty(K, n, dtype=torch.float32, device=dev)
+        if want_dipole:
+            res["dmu"] = torch.empty(K, n_mol, 3, dtype=torch.float32, device=dev)
+        status = torch.empty(8, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws_bytes = self.lib.aimnet_engine_charge_response_workspace_bytes
+        k0 = 0
+        while k0 < K:
+            opt = self.fill_options(rq)
+            per_dir = int(ws_bytes(self._h, n, n_mol, 2, C.byref(opt))) - int(ws_bytes(self._h, n, n_mol, 1, C.byref(opt)))
+            kc = max(1, min(K - k0, self.HVP_MAX_DIRECTIONS, self.HVP_BYTES_BUDGET // max(1, per_dir)))
+            ws = torch.empty(int(ws_bytes(self._h, n, n_mol, kc, C.byref(opt))) + 4096, dtype=torch.uint8, device=dev)
+            part = {k: v[k0 : k0 + kc].data_ptr() for k, v in res.items() if k != "charges"}
+            with torch.cuda.device(dev):
+                rc = self.lib.aimnet_engine_charge_response(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
+                                                            res["charges"].data_ptr(), part["dq"], part.get("dspin"), part.get("dmu"),
+                                                            status.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+            _lib.check(rc, "aimnet_engine_charge_response")
+            self.last_status = st = status.cpu().numpy()
+            del ws
+            if st[6]:
+                raise ValueError("HipEngine.charge_response: invalid input: " + describe_input_flags(int(st[6]), n_mol))
+            if not self.grow(st, opt, rq):  # (an overflow: the rows have grown - repeat this sweep)
+                k0 += kc
+        return res
+
     def set_profiling(self, level: int, every: int = 1) -> None:
         """0 off, 1 GEMM-vs-rest, 2 per kernel family (HIP events on the eval stream); `every` = record them on every
         n-th evaluation only (the events cost ~3 % of a 2 ms step; read_profile()["evals"] says how many were covered)."""

@@ -264,6 +264,29 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
                       int32_t n_vec, float* hv, float* forces, int32_t* status, void* workspace, size_t workspace_bytes,
                       void* hip_stream);
 
+/* Charge response: the final charges q (those of aimnet_outputs.charges) and their directional derivatives d q / d eps at
+ * x + eps v for n_vec directions at once - the forward tangent half of aimnet_engine_hvp, stopped after the NSE charge update of
+ * the last-but-one pass (specification: the intermediate `_t_q1` of oracle/aimnet2_analytic.py::evaluate_hvp).  The charges depend
+ * on neither the Coulomb method nor the dispersion term, the last pass or the energy head: only the short-range list is built,
+ * opt->max_nb is the one capacity read (opt->coulomb, opt->dftd3 and their fields are not), nothing runs backward, and the
+ * workspace holds the forward buffers of one pass (about 16 KB per direction and atom, 30 % of aimnet_engine_hvp's).
+ * vectors [n_vec, n_atoms, 3], device fp32.  Outputs, device fp32:
+ *   charges [n_atoms]          alpha + beta (may be NULL)
+ *   dq      [n_vec, n_atoms]   its tangent (required)
+ *   dspin   [n_vec, n_atoms]   tangent of alpha - beta: two-channel (NSE) models only, otherwise it must be NULL
+ *   dmu     [n_vec, n_mol, 3]  tangent of the dipole moment sum_i q_i x_i of every molecule, sum_i dq_i x_i + q_i v_i with x as
+ *                              given in in->coord (may be NULL); fp32 products summed in double without atomics: bitwise
+ *                              repeatable and independent of n_vec.  The dipole moment of a periodic cell is not defined: dmu
+ *                              together with in->cell is rejected.
+ * status [8] as for aimnet_engine_hvp (status[2] raised: grow max_nb and call again; status[6]: invalid input).  Rejected with
+ * AIMNET_E_INVALID before anything is launched: null or empty input, caller-supplied neighbour matrices, n_vec > 65535, dspin on
+ * a one-channel model, dmu with a cell, a model with a single pass. */
+size_t aimnet_engine_charge_response_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_vec,
+                                                     const aimnet_eval_options* opt);
+int aimnet_engine_charge_response(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt,
+                                  const float* vectors, int32_t n_vec, float* charges, float* dq, float* dspin, float* dmu,
+                                  int32_t* status, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Test hook: byte offset / element count / element size of a named intermediate inside the
  * workspace of the LAST eval (e.g. "nb_idx", "nb_cnt", "pair_geom", "x0", "y1", "q0", "aim",
  * "e_atom", "xbar0").  Returns AIMNET_E_INVALID for unknown names. */
