@@ -15,6 +15,8 @@ ABI_VERSION = 12  # AIMNET_ABI_VERSION of include/aimnet_hip.h this binding was 
 FORCES, STRESS = 1, 2
 COULOMB_NONE, COULOMB_SIMPLE, COULOMB_DSF, COULOMB_EWALD, COULOMB_PME = 0, 1, 2, 3, 4
 E_INVALID, E_HIP, E_WORKSPACE = -1, -2, -3
+EMBED_CHUNK = 1024  # csrc/kernels.h: sites per chunk of the embedding field pass (the partition depends on n_ext and n_mol alone)
+EMBED_MAX_SLOTS = 64  # csrc/kernels.h: partial sums per atom, min(ceil(ceil(n_ext / n_mol) / EMBED_CHUNK), this)
 PROF_FAMILIES = ("nlist", "geom", "conv_fwd", "gemm", "pointwise", "coulomb", "unconcat", "conv_bwd", "other")
 
 # AIMNET_HIP_LIB names another build of the same library (A/B runs of kernel variants on one box); default: the in-tree build
@@ -48,6 +50,8 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_get_option",
     "aimnet_engine_set_dftd3",
     "aimnet_engine_set_dd",
+    "aimnet_embedding_scratch_bytes",
+    "aimnet_engine_set_embedding",
     "aimnet_neighbor_list",
     "aimnet_neighbor_list_workspace_bytes",
     "aimnet_conv_sv_2d_sp_fwd",
@@ -157,6 +161,24 @@ class DftD3Tables(C.Structure):
     ]
 
 
+class Embedding(C.Structure):
+    """aimnet_embedding: device pointers; point charges, per-atom potential, outputs, caller-owned scratch."""
+
+    _fields_ = [
+        ("n_ext", C.c_int32),
+        ("ext_coord", C.c_void_p),
+        ("ext_charge", C.c_void_p),
+        ("ext_mol_idx", C.c_void_p),
+        ("potential", C.c_void_p),
+        ("potential_grad", C.c_void_p),
+        ("ext_forces", C.c_void_p),
+        ("ext_potential", C.c_void_p),
+        ("energy", C.c_void_p),
+        ("scratch", C.c_void_p),
+        ("scratch_bytes", C.c_size_t),
+    ]
+
+
 class Outputs(C.Structure):
     _fields_ = [
         ("energy", C.c_void_p),
@@ -218,6 +240,10 @@ def load() -> C.CDLL:
     lib.aimnet_engine_set_dftd3.argtypes = [vp, C.POINTER(DftD3Tables)]
     lib.aimnet_engine_set_dd.restype = C.c_int
     lib.aimnet_engine_set_dd.argtypes = [vp, vp, DD_EXCHANGE_FN, vp]
+    lib.aimnet_embedding_scratch_bytes.restype = sz
+    lib.aimnet_embedding_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.aimnet_engine_set_embedding.restype = C.c_int
+    lib.aimnet_engine_set_embedding.argtypes = [vp, C.POINTER(Embedding)]
     lib.aimnet_debug_gemm.restype = C.c_int
     lib.aimnet_debug_gemm.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.aimnet_debug_split_bf3.restype = C.c_int

@@ -61,6 +61,41 @@ def _cell_array(atoms):
     return np.asarray(cell.array if hasattr(cell, "array") else cell, dtype=np.float64)
 
 
+class PointChargeEmbedding:
+    """The point charges AIMNet2ASE.embed() returns: the MM side sets positions (A) and charges (e); `get_forces(calc)` gives the
+    forces on the sites (eV/A) of the calculator's last evaluation, running one if the sites have moved since."""
+
+    def __init__(self, calc, charges=None, positions=None):
+        self.calc, self.charges, self.positions, self.forces = calc, None, None, None
+        if charges is not None:
+            self.set_charges(charges)
+        if positions is not None:
+            self.set_positions(positions)
+
+    def ready(self) -> bool:
+        return self.charges is not None and self.positions is not None
+
+    def set_charges(self, charges):
+        self.charges = np.array(charges, dtype=np.float64).reshape(-1)
+        self._changed()
+
+    def set_positions(self, positions, **_):
+        self.positions = np.array(positions, dtype=np.float64).reshape(-1, 3)
+        self._changed()
+
+    def _changed(self):
+        self.forces = None
+        self.calc.results = {}  # the cached results no longer belong to these sites (the attached atoms stay)
+
+    def get_forces(self, calc=None):
+        calc = self.calc if calc is None else calc
+        if self.forces is None:
+            if getattr(calc, "atoms", None) is None:
+                raise RuntimeError("embedding: get_forces needs a calculator that has atoms attached")
+            calc.calculate(calc.atoms, ["energy", "forces"], all_changes)
+        return self.forces.copy()
+
+
 class AIMNet2ASE(Calculator):
     implemented_properties: ClassVar[list[str]] = ["energy", "forces", "free_energy", "charges", "stress", "dipole_moment"]
 
@@ -171,6 +206,17 @@ class AIMNet2ASE(Calculator):
                                               validate_species=self.validate_species)
         return P.detach().reshape(-1, 3).cpu().numpy()
 
+    _embed = None  # the point charges of embed(), or None
+
+    def embed(self, charges=None, positions=None):
+        """Electrostatic embedding in point charges (the interface ase.calculators.qmmm.EIQMMM drives): returns an object with
+        `set_positions`, `set_charges` and `get_forces(calc)`.  Every later `calculate` includes E_emb = sum_i q_i phi_i in the
+        energy and its exact gradient in the forces (the model's charges are not polarised by the sites), and caches the forces on
+        the sites.  `embed(None)` without arguments switches it off."""
+        self._embed = None if charges is None and positions is None else PointChargeEmbedding(self, charges, positions)
+        self.results = {}
+        return self._embed
+
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
         if properties is None:
             properties = ["energy"]
@@ -191,9 +237,15 @@ class AIMNet2ASE(Calculator):
         if cell is not None:
             data["cell"] = cell.astype(np.float32)
             data["pbc"] = pbc
-        out = self.base_calc.eval(data, forces="forces" in properties, stress="stress" in properties,
+        pc = self._embed if self._embed is not None and self._embed.ready() else None
+        if pc is not None:  # point charges of embed(): part of the energy and forces; the forces on the sites are cached
+            data["ext_coord"], data["ext_charge"] = pc.positions.astype(np.float32), pc.charges.astype(np.float32)
+        out = self.base_calc.eval(data, forces="forces" in properties or pc is not None, stress="stress" in properties,
                                   validate_species=self.validate_species, host_out=True)
         res = {k: v.detach().cpu().numpy() for k, v in out.items()}
+        if pc is not None:
+            pc.forces = res["ext_forces"].astype(np.float64)
+            self.results["embedding_energy"] = float(np.asarray(res["embedding_energy"]).reshape(-1)[0])
         self.results["energy"] = float(np.asarray(res["energy"]).reshape(-1)[0])
         self.results["free_energy"] = self.results["energy"]
         self.results["charges"] = res["charges"]

@@ -445,6 +445,82 @@ class AIMNet2Calculator:
             ext = {k: v for k, v in ext.items() if not k.startswith("shifts")}
         return ext
 
+    # electrostatic embedding (no reference counterpart; include/aimnet_hip.h, aimnet_embedding): optional input keys
+    EMBEDDING_KEYS = ("ext_coord", "ext_charge", "ext_mol_idx", "ext_potential", "ext_potential_grad")
+
+    def _has_embedding(self, data: dict[str, Any]) -> bool:
+        return any(data.get(k) is not None for k in self.EMBEDDING_KEYS)
+
+    def _embedding(self, data: dict[str, Any], coord, pad_mask, cell, forces: bool) -> dict[str, Any]:
+        """The `embedding=` dict of HipEngine.eval from the optional keys `ext_coord` (M,3) / `ext_charge` (M,) [/ `ext_mol_idx`
+        (M,)], and `ext_potential` (N,) / `ext_potential_grad` (N,3) in V and V/A.  For (B,N,3) input: `ext_coord` (B,M,3) and
+        `ext_charge` (B,M) with zero charges as padding (flattened with a repeated molecule index), `ext_potential` (B,N) and
+        `ext_potential_grad` (B,N,3).  Every shape or dtype error is a ValueError raised before the engine is touched."""
+        import torch
+
+        def tensor(key, dtype):
+            v = data.get(key)
+            if v is None:
+                return None
+            try:
+                t = torch.as_tensor(v, device=self.device)
+            except Exception as exc:
+                raise ValueError(f"{key}: not convertible to a tensor ({exc})") from exc
+            if dtype == torch.float32 and not (t.is_floating_point() or t.dtype in (torch.int32, torch.int64)):
+                raise ValueError(f"{key} must be a real array, got dtype {t.dtype}")
+            if dtype == torch.int32 and (t.is_floating_point() or t.dtype == torch.bool or t.is_complex()):
+                raise ValueError(f"{key} must be an integer array, got dtype {t.dtype}")
+            return t.detach().to(dtype)
+
+        xc, qc, mi = tensor("ext_coord", torch.float32), tensor("ext_charge", torch.float32), tensor("ext_mol_idx", torch.int32)
+        pot, pg = tensor("ext_potential", torch.float32), tensor("ext_potential_grad", torch.float32)
+        batch = coord.ndim == 3
+        emb: dict[str, Any] = {}
+        if (xc is None) != (qc is None):
+            raise ValueError("ext_coord and ext_charge are given together")
+        if mi is not None and xc is None:
+            raise ValueError("ext_mol_idx given without ext_coord")
+        if xc is not None:
+            if cell is not None:
+                raise ValueError("ext_coord / ext_charge take non-periodic input (the sites have no images): pass ext_potential / "
+                                 "ext_potential_grad with a cell")
+            if batch:
+                B = coord.shape[0]
+                if xc.ndim != 3 or xc.shape[0] != B or xc.shape[2] != 3 or tuple(qc.shape) != tuple(xc.shape[:2]):
+                    raise ValueError(f"3D input needs ext_coord ({B}, M, 3) and ext_charge ({B}, M), got {tuple(xc.shape)}, {tuple(qc.shape)}")
+                if mi is not None:
+                    raise ValueError("ext_mol_idx is not read with 3D input (the batch axis names the molecule)")
+                mi = torch.arange(B, dtype=torch.int32, device=xc.device).repeat_interleave(xc.shape[1])
+                xc, qc = xc.flatten(0, 1), qc.flatten()
+            else:
+                if xc.ndim != 2 or xc.shape[1] != 3 or tuple(qc.shape) != (xc.shape[0],):
+                    raise ValueError(f"ext_coord must be (M, 3) and ext_charge (M,), got {tuple(xc.shape)}, {tuple(qc.shape)}")
+                if mi is not None and tuple(mi.shape) != (xc.shape[0],):
+                    raise ValueError(f"ext_mol_idx must have shape ({xc.shape[0]},), got {tuple(mi.shape)}")
+                if mi is None and data.get("mol_idx") is not None and int(torch.as_tensor(data["charge"]).numel()) > 1:
+                    raise ValueError("ext_mol_idx is required when mol_idx names more than one molecule")
+            emb.update(ext_coord=xc, ext_charge=qc, want_ext_forces=forces)
+            if mi is not None:
+                emb["ext_mol_idx"] = mi
+        if pg is not None and pot is None:
+            raise ValueError("ext_potential_grad given without ext_potential")
+        if pot is not None:
+            lead = tuple(coord.shape[:-1])
+            if tuple(pot.shape) != lead:
+                raise ValueError(f"ext_potential must have shape {lead}, got {tuple(pot.shape)}")
+            if pg is not None and tuple(pg.shape) != lead + (3,):
+                raise ValueError(f"ext_potential_grad must have shape {lead + (3,)}, got {tuple(pg.shape)}")
+            if pg is None and forces:
+                raise ValueError("forces with ext_potential need ext_potential_grad")
+            if batch:
+                pot, pg = pot.flatten(), (pg.flatten(0, 1) if pg is not None else None)
+                if pad_mask is not None:
+                    pot, pg = pot[pad_mask], (pg[pad_mask] if pg is not None else None)
+            emb["potential"] = pot
+            if pg is not None:
+                emb["potential_grad"] = pg
+        return emb
+
     def eval(self, data: dict[str, Any], forces=False, stress=False, hessian=False, *, validate_species: bool = True,
              host_out: bool = False, defer_status: bool = False) -> dict[str, Any]:
         """calculator.py:879-947.  `host_out=True` (not in the reference) returns CPU tensors that arrived with the engine's one
@@ -456,6 +532,10 @@ class AIMNet2Calculator:
         if validate_species:
             self._validate_species_and_charge(data)
         self._maybe_warn_mult_ignored(data)
+        embedded = self._has_embedding(data)
+        if embedded and (hessian or stress or self._dd is not None):
+            raise NotImplementedError("electrostatic embedding (ext_coord / ext_charge / ext_potential) is carried by energies and "
+                                      "forces only: not with stress=True, hessian=True or domain decomposition")
         if hessian:
             return self._eval_hessian(data, forces=forces, stress=stress, validate_species=validate_species)
         d = self.to_input_tensors(data)
@@ -514,6 +594,8 @@ class AIMNet2Calculator:
         else:
             raise ValueError(f"coord must be (N,3) or (B,N,3), got {tuple(coord.shape)}")
         n_mol = charge.shape[0]
+        # (checked in full before the engine is touched; the keyword is passed only with embedding keys present)
+        emb = self._embedding(data, coord, pad_mask, cell, bool(forces)) if embedded else None
         method, restore = self._coulomb_method, None
         if cell is not None and method == "simple":
             warnings.warn("Switching to DSF Coulomb for PBC for this evaluation; "
@@ -556,6 +638,7 @@ class AIMNet2Calculator:
                     coulomb=method or "none", dsf_rc=self._dsf_rc, dsf_alpha=self._dsf_alpha, ewald_accuracy=self._ewald_accuracy,
                     dftd3=self._dftd3_options(),
                     **({"host_out": True} if host_out else {}), **({"sync": False, "defer": True} if defer_status else {}),
+                    **({"embedding": emb} if emb is not None else {}),
                     **self._check_caller_lists(ext_lists, method, cell))
         finally:
             if restore is not None:
@@ -568,6 +651,10 @@ class AIMNet2Calculator:
             out["forces"] = res["forces"]
         if stress:
             out["stress"] = res["stress"]
+        if emb is not None:
+            out["embedding_energy"] = res["embedding_energy"]
+            if "ext_forces" in res:
+                out["ext_forces"] = res["ext_forces"].view(self._batch, -1, 3) if self._batch is not None else res["ext_forces"]
         if self._batch is not None:
             B = self._batch
             for k in ("charges", "spin_charges", "forces"):
@@ -777,6 +864,8 @@ class AIMNet2Calculator:
 
         if create_graph:
             raise NotImplementedError("create_graph=True needs autograd through the model; the native engine has none")
+        if self._has_embedding(data):
+            raise NotImplementedError("hessian_vector_product: the electrostatic-embedding term is not carried by the tangent sweep")
         if validate_species:
             self._validate_species_and_charge(data)
         self._maybe_warn_mult_ignored(data)

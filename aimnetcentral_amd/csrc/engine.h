@@ -169,6 +169,9 @@ struct aimnet_engine {
   // aimnet_engine_set_dd: spatial domain decomposition of one system over ranks - owned-atom mask of the local cluster and the
   // caller's exchange function (dd.owned == NULL: off)
   aimnet::DdLink dd{nullptr, nullptr, nullptr};
+  // aimnet_engine_set_embedding: electrostatic embedding of the charges (csrc/embed.hip), a copy of the caller's struct
+  bool emb_on = false;
+  aimnet_embedding emb{};
   float* unit_cell = nullptr;  // 3 x 3 identity (device): "cell" of the virial sums of a decomposed evaluation
   double* sae;
   // species slots of the pass-0 moment backward: slot = rank of the atomic number among the embedding rows that

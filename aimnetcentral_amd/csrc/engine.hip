@@ -576,6 +576,7 @@ struct Eval {
     return PairMapRider{W.nb_idx, n_cell > 0 ? W.nb_shift : nullptr, W.nb_cnt, P.layout.cap, N, W.rev_tab, W.rev, ceil_div(N, 4)};
   }
   int prepare(), lists_built(), lists_imported(), forward(), head(SrRiders& rider), coulomb(const SrRiders& head_rider), join();
+  int embedding();
   int head_bwd(float*& zcur, float*& znext), nse_bwd(int p, float* znext), backward(), finalize();
 };
 
@@ -794,6 +795,7 @@ int Eval::coulomb(const SrRiders& head_rider) {
     RC(launch_dftd3(s, grad, want_s, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, P.cap_d3, e->d3,
                     d3_params(opt), opt->d3_cutoff, N, W.d3xs, W.d3w, W.dEdcn, W.ecoul, W.fgrad, W.virial_atom,
                     P.lr_term == LongRange::DsfInD3, cp, q_fin, W.qbar, P.d3_cn_rides, dd));
+  if (e->emb_on) RC(embedding());  // one more addend to ecoul and to the seeds; in front of the copy of qbar: both channels take it
   if (grad && nq == 2) RC(launch_copy_f32(s, W.qbar, W.qbar + N, (size_t)N));  // dE/dq_alpha = dE/dq_beta = dE/dq at this point
   if (dd) {  // halo copies: no energy, no Coulomb adjoint / direct force, no backward seed (model.hip, dd_mask_kernel)
     const int nlp = (int)e->mlp[np - 1].size();
@@ -802,6 +804,21 @@ int Eval::coulomb(const SrRiders& head_rider) {
                       want_s ? W.virial_atom : nullptr, grad ? W.zb0 : nullptr, seed_bytes, N));
   }
   return 0;
+}
+
+// electrostatic embedding (embed.hip): E_emb = sum_i q_i phi_i joins the pair energies, phi_i the adjoint dE/dq_i that the backward
+// sweep carries to the coordinates, q_i grad phi_i the direct dE/dx_i.  The coordinates are the caller's (in->coord), the frame of
+// the sites.  Energy-only requests run the same field and seed passes without the adjoint stores.
+int Eval::embedding() {
+  const aimnet_embedding& m = e->emb;
+  EmbedBuffers b;
+  embed_carve(b, (char*)m.scratch, N, n_mol, m.n_ext);
+  RC(launch_embed_sites(s, m.ext_mol_idx, m.n_ext, n_mol, b, out->status + 6));
+  RC(launch_embed_field(s, in->coord, mol_c, N, n_mol, m.ext_coord, m.ext_charge, m.n_ext, b));
+  RC(launch_embed_seed(s, P.grad, q_fin, N, m.n_ext, m.potential, m.potential_grad, b, W.ecoul, W.qbar, W.fgrad, W.nl.mol_start,
+                       n_mol, m.energy));
+  return launch_embed_site_pass(s, in->coord, q_fin, W.nl.mol_start, n_mol, m.ext_coord, m.ext_charge, m.n_ext, b, m.ext_forces,
+                                m.ext_potential);
 }
 
 // The results of the Coulomb block (ecoul, qbar / fgrad / virial seeds, qtot) are first needed here (energy only) or in front of
@@ -961,6 +978,16 @@ EvalRequest eval_request(const aimnet_engine* e, const aimnet_inputs* in, const 
   r.cell_setup_ok = cell_setup_rides(N, n_mol);
   r.bbox_ok = bbox_applies(N, n_mol);
   r.head_fusable = head_fusable(e);
+  if (e->emb_on) {
+    const aimnet_embedding& m = e->emb;
+    r.emb = 1;
+    r.emb_n_ext = m.n_ext;
+    r.emb_sites_ok = m.n_ext <= 0 || (m.ext_coord && m.ext_charge);
+    r.emb_ext_mol_idx = m.ext_mol_idx != nullptr;
+    r.emb_potential = m.potential != nullptr;
+    r.emb_potential_grad = m.potential_grad != nullptr;
+    r.emb_scratch_ok = m.scratch && m.n_ext >= 0 && m.scratch_bytes >= aimnet_embedding_scratch_bytes(N, n_mol, m.n_ext);
+  }
   return r;
 }
 
@@ -1178,6 +1205,33 @@ int aimnet_engine_set_dd(aimnet_engine* e, const float* owned, aimnet_dd_exchang
     return AIMNET_E_INVALID;
   }
   e->dd = aimnet::DdLink{owned, owned ? fn : nullptr, owned ? ctx : nullptr};
+  return AIMNET_OK;
+}
+
+size_t aimnet_embedding_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext) {
+  if (n_atoms <= 0 || n_mol <= 0 || n_ext < 0) return 0;
+  aimnet::EmbedBuffers b;
+  aimnet::embed_carve(b, nullptr, n_atoms, n_mol, n_ext);
+  return b.total;
+}
+
+int aimnet_engine_set_embedding(aimnet_engine* e, const aimnet_embedding* emb) {
+  if (!e) return AIMNET_E_INVALID;
+  if (!emb) {
+    e->emb_on = false;
+    e->emb = aimnet_embedding{};
+    return AIMNET_OK;
+  }
+  if (emb->n_ext < 0 || (emb->n_ext > 0 && (!emb->ext_coord || !emb->ext_charge))) {
+    set_last_error("set_embedding: n_ext >= 0, and n_ext > 0 needs ext_coord and ext_charge");
+    return AIMNET_E_INVALID;
+  }
+  if (!emb->scratch) {
+    set_last_error("set_embedding: scratch is required (aimnet_embedding_scratch_bytes)");
+    return AIMNET_E_INVALID;
+  }
+  e->emb = *emb;  // (checked against the problem size by every evaluation, eval_plan.h)
+  e->emb_on = true;
   return AIMNET_OK;
 }
 

@@ -77,6 +77,12 @@ struct EvalRequest {
   bool cell_setup_ok;   // cell_setup_rides(N, n_mol)
   bool bbox_ok;         // bbox_applies(N, n_mol)
   bool head_fusable;    // head_fusable(engine)
+  // electrostatic embedding (aimnet_engine_set_embedding); emb == 0: off, nothing below is read
+  int emb;
+  int emb_n_ext;                                            // point charges
+  bool emb_sites_ok;                                        // n_ext == 0, or ext_coord and ext_charge given
+  bool emb_ext_mol_idx, emb_potential, emb_potential_grad;  // which optional arrays are given
+  bool emb_scratch_ok;                                      // scratch given and at least aimnet_embedding_scratch_bytes
 };
 
 enum class Prep { FusedSmall, Separate, SeparateSetupRider };  // launch_prep_small / launch_mol_start + launch_wrap (+ the setup rider)
@@ -173,6 +179,21 @@ inline int eval_validate(const EvalRequest& r, char* msg, size_t n) {
     return plan_reject(msg, n,
                        "eval: a domain-decomposed evaluation takes a non-periodic cluster (no cell, no caller-supplied lists), Coulomb "
                        "'none' or 'dsf'");
+  // electrostatic embedding (aimnet_engine_set_embedding)
+  if (r.emb) {
+    if (want_s) return plan_reject(msg, n, "eval: the embedding term has no stress (AIMNET_STRESS with an embedding set)");
+    if (r.dd) return plan_reject(msg, n, "eval: the embedding term is not carried by a domain-decomposed evaluation");
+    if (r.emb_n_ext < 0 || !r.emb_sites_ok) return plan_reject(msg, n, "eval: embedding: n_ext > 0 needs ext_coord and ext_charge");
+    if (r.emb_n_ext > 0 && r.pbc)
+      return plan_reject(msg, n, "eval: embedding point charges take non-periodic input (no images of the sites): pass a per-atom "
+                                 "potential with a cell");
+    if (r.emb_potential_grad && !r.emb_potential) return plan_reject(msg, n, "eval: embedding: potential_grad without potential");
+    if (r.emb_potential && !r.emb_potential_grad && want_f)
+      return plan_reject(msg, n, "eval: embedding: forces need potential_grad beside potential");
+    if (r.emb_n_ext > 0 && !r.emb_ext_mol_idx && r.L.n_mol > 1)
+      return plan_reject(msg, n, "eval: embedding: ext_mol_idx == NULL is allowed with one molecule only (n_mol = %d)", r.L.n_mol);
+    if (!r.emb_scratch_ok) return plan_reject(msg, n, "eval: embedding: scratch missing or smaller than aimnet_embedding_scratch_bytes");
+  }
   return 0;
 }
 // the checks that follow the workspace-size check: DFT-D3 tables, and the caller's D3 matrix against the layout

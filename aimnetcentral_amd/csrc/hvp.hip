@@ -1209,6 +1209,10 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
     set_last_error("hvp: null or empty input");
     return AIMNET_E_INVALID;
   }
+  if (e->emb_on) {
+    set_last_error("hvp: the embedding term is not carried by the tangent sweep (aimnet_engine_set_embedding(e, NULL) first)");
+    return AIMNET_E_INVALID;
+  }
   if (in->nbmat || in->nbmat_lr || in->nbmat_d3) {
     set_last_error("hvp: caller-supplied neighbour matrices are not read by the tangent sweep (it builds its own lists)");
     return AIMNET_E_INVALID;

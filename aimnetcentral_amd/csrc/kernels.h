@@ -455,4 +455,39 @@ int launch_finalize(hipStream_t s, const float* fgrad, const float* virial_atom,
                     int* nf = nullptr);
 int launch_copy_f32(hipStream_t s, const float* src, float* dst, size_t n);
 
+// ---- embed.hip: electrostatic embedding E_emb = sum_i q_i phi(x_i) (aimnet_engine_set_embedding) ---------------------------------
+// phi_i = k_e sum_A Q_A / |x_i - X_A| + potential_i over the point charges of atom i's molecule, k_e = Hartree * Bohr; the pair
+// terms in fp32, every sum in double, no atomics on results.  The site stream of a molecule is cut into chunks of EMBED_CHUNK sites;
+// slot s of an atom sums the chunks s, s + n_slots, ... of its molecule in that order, n_slots = embed_slots(n_ext, n_mol): the
+// average number of chunks per molecule, at most EMBED_MAX_SLOTS.  The partition depends on the two sizes alone, never on the
+// device or on the data (mirrored in _lib.py); a molecule that owns more than its share of the sites runs more chunks per slot.
+constexpr int EMBED_CHUNK = 1024;
+constexpr int EMBED_MAX_SLOTS = 64;
+constexpr int STATUS_EXT_MOL_IDX = 128;  // bit of status[6]: ext_mol_idx holds an entry outside [0, n_mol) or is not sorted
+static inline int embed_slots(int n_ext, int n_mol) {
+  const long long per_mol = ((long long)n_ext + n_mol - 1) / (n_mol > 0 ? n_mol : 1);
+  const long long c = (per_mol + EMBED_CHUNK - 1) / EMBED_CHUNK;
+  return (int)(c < EMBED_MAX_SLOTS ? c : EMBED_MAX_SLOTS);
+}
+struct EmbedBuffers {  // carved from the caller's scratch (embed_carve; base == NULL: sizes only)
+  int* ext_start;   // [n_mol + 1] first site of every molecule
+  int* ext_mol_c;   // [n_ext] ext_mol_idx clamped to [0, n_mol)
+  double* part;     // [n_atoms][n_slots][4] partial (phi, grad phi) of the field pass
+  double* e_atom;   // [n_atoms] q_i phi_i
+  size_t total;
+};
+void embed_carve(EmbedBuffers& b, char* base, int n_atoms, int n_mol, int n_ext);
+// ext_start / ext_mol_c from ext_mol_idx (NULL: every site belongs to molecule 0); raises STATUS_EXT_MOL_IDX in *status6
+int launch_embed_sites(hipStream_t s, const int* ext_mol_idx, int n_ext, int n_mol, const EmbedBuffers& b, int* status6);
+// field pass: one block per (atom, slot); x: the coordinates as the caller gave them
+int launch_embed_field(hipStream_t s, const float* x, const int* mol_c, int n_atoms, int n_mol, const float* ext_coord,
+                       const float* ext_charge, int n_ext, const EmbedBuffers& b);
+// seed pass: ecoul += q phi; grad: qbar += phi, fgrad += q grad phi; then the molecule sums of q phi into energy (may be NULL)
+int launch_embed_seed(hipStream_t s, bool grad, const float* q, int n_atoms, int n_ext, const float* potential,
+                      const float* potential_grad, const EmbedBuffers& b, double* ecoul, float* qbar, float* fgrad,
+                      const int* mol_start, int n_mol, double* energy);
+// site pass: ext_forces[A] = -dE_emb/dX_A, ext_potential[A] = k_e sum_i q_i / |x_i - X_A| (either may be NULL)
+int launch_embed_site_pass(hipStream_t s, const float* x, const float* q, const int* mol_start, int n_mol, const float* ext_coord,
+                           const float* ext_charge, int n_ext, const EmbedBuffers& b, float* ext_forces, float* ext_potential);
+
 }  // namespace aimnet

@@ -287,11 +287,13 @@ class DomainDecomposedEngine:
 
     def eval(self, coord, numbers, cell, charge: float = 0.0, forces: bool = True, stress: bool = False, coulomb: str = "dsf",
              dsf_rc: float = 15.0, dsf_alpha: float = 0.2, dftd3: dict[str, float] | None = None, halo: float | None = None,
-             axis: int | None = None, grid=None) -> dict[str, Any]:
+             axis: int | None = None, grid=None, embedding=None) -> dict[str, Any]:
         import torch
         import torch.distributed as dist
 
         eng = self.engine
+        if embedding is not None:
+            raise ValueError("DomainDecomposedEngine: the electrostatic-embedding term is not carried by a decomposed evaluation")
         if coulomb not in ("none", "dsf"):
             raise ValueError("DomainDecomposedEngine: coulomb must be 'none' or 'dsf' (Ewald / PME reciprocal sums and the all-pairs "
                              "'simple' form are not decomposed)")

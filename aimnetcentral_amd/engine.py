@@ -56,6 +56,7 @@ class NeighborOverflowError(RuntimeError):
 
 
 EWALD_LIST_SHORT_FLAG = 64  # status[6] bit 6 (csrc/kernels.h STATUS_EWALD_LIST_SHORT): aimnet_engine_hvp, list cutoff below an Ewald r_c
+EXT_MOL_IDX_FLAG = 128  # status[6] bit 7 (csrc/kernels.h STATUS_EXT_MOL_IDX): embedding, ext_mol_idx out of range or not sorted
 NONFINITE_FLAG = 32  # status[6] bit 5 (csrc/kernels.h STATUS_NONFINITE): a non-finite energy or force was written - not an input flag
 
 
@@ -76,8 +77,11 @@ def describe_input_flags(flags: int, n_mol: int | None = None) -> str:
     if flags & EWALD_LIST_SHORT_FLAG:
         what.append("Ewald summation in the tangent sweep: options.dsf_rc (the cutoff of the real-space list) is below a system's "
                     "real-space cutoff")
-    if flags & ~(31 | EWALD_LIST_SHORT_FLAG):
-        what.append(f"unknown flag bits {flags & ~(31 | EWALD_LIST_SHORT_FLAG):#x}")
+    if flags & EXT_MOL_IDX_FLAG:
+        what.append("embedding: ext_mol_idx entries outside [0, %s) or not sorted (the sites of a molecule must be contiguous)"
+                    % ("n_mol" if n_mol is None else n_mol))
+    if flags & ~(31 | EWALD_LIST_SHORT_FLAG | EXT_MOL_IDX_FLAG):
+        what.append(f"unknown flag bits {flags & ~(31 | EWALD_LIST_SHORT_FLAG | EXT_MOL_IDX_FLAG):#x}")
     return " and ".join(what) if what else "no flags"
 
 
@@ -355,7 +359,7 @@ class HipEngine(capacity.Capacities):
     def eval(self, coord, numbers, mol_idx, charge, cell=None, pbc=(True, True, True), forces: bool = False, stress: bool = False,
              coulomb: str = "simple", dsf_rc: float = 15.0, dsf_alpha: float = 0.2, ewald_accuracy: float = 1e-6, sync: bool = True,
              dftd3: dict[str, float] | None = None, host_out: bool = False, defer: bool = False, nbmat=None, shifts=None,
-             nbmat_lr=None, shifts_lr=None, nbmat_d3=None, shifts_d3=None) -> dict[str, Any]:
+             nbmat_lr=None, shifts_lr=None, nbmat_d3=None, shifts_d3=None, embedding: dict[str, Any] | None = None) -> dict[str, Any]:
         """One evaluation on device tensors (coord f32 [N,3], numbers/mol_idx i32 [N], charge f32
         [n_mol] - for a 2-channel NSE model [n_mol, 2] = the alpha / beta charges of aimnet2.py:94-100 -,
         cell f32 [3,3]|[n_mol,3,3]).  Returns device tensors (NSE: plus spin_charges); retries with x1.5 row
@@ -365,9 +369,20 @@ class HipEngine(capacity.Capacities):
         ASE adapter's path: no further .cpu() round trips).
         `nbmat` (+ `shifts`, `nbmat_lr` / `shifts_lr`, `nbmat_d3` / `shifts_d3`): caller-supplied FULL neighbour matrices, int
         [N, width] with entries outside [0, N) as padding, integer shifts [N, width, 3] - the engine then builds no list and takes the
-        coordinates as given (include/aimnet_hip.h, aimnet_inputs.nbmat)."""
+        coordinates as given (include/aimnet_hip.h, aimnet_inputs.nbmat).
+        `embedding`: electrostatic embedding of the charges, E_emb = sum_i q_i phi_i (include/aimnet_hip.h, aimnet_embedding) - a
+        dict with point charges `ext_coord` [M,3], `ext_charge` [M] (+ `ext_mol_idx` [M], sorted, for more than one molecule) and / or
+        a per-atom `potential` [N] (V) with `potential_grad` [N,3] (V/A); `want_ext_forces` / `want_ext_potential` ask for the
+        forces on the sites and the potential of the atoms' charges at them.  The energy and forces include the term; the
+        result gains `embedding_energy` [n_mol] (and `ext_forces` [M,3], `ext_potential` [M]).  Not with `stress`."""
         import torch
 
+        if embedding is not None:
+            return self._eval_embedded(embedding, dict(
+                coord=coord, numbers=numbers, mol_idx=mol_idx, charge=charge, cell=cell, pbc=pbc, forces=forces, stress=stress,
+                coulomb=coulomb, dsf_rc=dsf_rc, dsf_alpha=dsf_alpha, ewald_accuracy=ewald_accuracy, sync=sync, dftd3=dftd3,
+                host_out=host_out, defer=defer, nbmat=nbmat, shifts=shifts, nbmat_lr=nbmat_lr, shifts_lr=shifts_lr, nbmat_d3=nbmat_d3,
+                shifts_d3=shifts_d3))
         inp, t = self._inputs("eval", coord, numbers, mol_idx, charge, cell, pbc)
         n, n_mol, cell = inp.n_atoms, inp.n_mol, t["cell"]
         method = _METHODS[coulomb]
@@ -425,6 +440,79 @@ class HipEngine(capacity.Capacities):
                     self._pending_energy.append(res["energy"])
         if stress and cell is not None and cell.ndim == 2:
             res["stress"] = res["stress"][0]
+        return res
+
+    EMBEDDING_KEYS = ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "want_ext_forces", "want_ext_potential")
+
+    def _eval_embedded(self, emb: dict[str, Any], kw: dict[str, Any]) -> dict[str, Any]:
+        """`eval` with an embedding: check it, allocate its scratch and outputs, set it (aimnet_engine_set_embedding), evaluate,
+        and switch it off again whatever happens."""
+        import torch
+
+        unknown = set(emb) - set(self.EMBEDDING_KEYS)
+        if unknown:
+            raise ValueError(f"HipEngine.eval: unknown embedding keys {sorted(unknown)}")
+        if kw["stress"]:
+            raise ValueError("HipEngine.eval: the embedding term has no stress")
+        dev, f32 = self.device, torch.float32
+        n = int(kw["coord"].shape[0])
+        n_mol = int(kw["charge"].shape[0]) if self.nq == 2 else int(kw["charge"].numel())
+        xc, qc, mi = emb.get("ext_coord"), emb.get("ext_charge"), emb.get("ext_mol_idx")
+        if (xc is None) != (qc is None):
+            raise ValueError("HipEngine.eval: embedding point charges need both ext_coord and ext_charge")
+        m = 0
+        if xc is not None:
+            xc = torch.as_tensor(xc).to(device=dev, dtype=f32).contiguous()
+            qc = torch.as_tensor(qc).to(device=dev, dtype=f32).contiguous()
+            if xc.ndim != 2 or xc.shape[1] != 3 or tuple(qc.shape) != (xc.shape[0],):
+                raise ValueError(f"HipEngine.eval: ext_coord must be [M, 3] and ext_charge [M], got {tuple(xc.shape)}, {tuple(qc.shape)}")
+            m = int(xc.shape[0])
+            if m and kw["cell"] is not None:
+                raise ValueError("HipEngine.eval: embedding point charges take non-periodic input; pass a per-atom potential with a cell")
+            if mi is not None:
+                mi = torch.as_tensor(mi).to(device=dev, dtype=torch.int32).contiguous()
+                if tuple(mi.shape) != (m,):
+                    raise ValueError(f"HipEngine.eval: ext_mol_idx must have shape ({m},), got {tuple(mi.shape)}")
+            elif n_mol > 1 and m:
+                raise ValueError("HipEngine.eval: embedding point charges of more than one molecule need ext_mol_idx")
+        elif mi is not None:
+            raise ValueError("HipEngine.eval: ext_mol_idx given without ext_coord")
+        pot, pg = emb.get("potential"), emb.get("potential_grad")
+        if pot is not None:
+            pot = torch.as_tensor(pot).to(device=dev, dtype=f32).contiguous()
+            if tuple(pot.shape) != (n,):
+                raise ValueError(f"HipEngine.eval: embedding potential must have shape ({n},), got {tuple(pot.shape)}")
+        if pg is not None:
+            if pot is None:
+                raise ValueError("HipEngine.eval: embedding potential_grad given without potential")
+            pg = torch.as_tensor(pg).to(device=dev, dtype=f32).contiguous()
+            if tuple(pg.shape) != (n, 3):
+                raise ValueError(f"HipEngine.eval: embedding potential_grad must have shape ({n}, 3), got {tuple(pg.shape)}")
+        elif pot is not None and kw["forces"]:
+            raise ValueError("HipEngine.eval: forces with an embedding potential need potential_grad")
+        outs = {"embedding_energy": torch.empty(n_mol, dtype=torch.float64, device=dev)}
+        if emb.get("want_ext_forces") and xc is not None:
+            outs["ext_forces"] = torch.empty(m, 3, dtype=f32, device=dev)
+        if emb.get("want_ext_potential") and xc is not None:
+            outs["ext_potential"] = torch.empty(m, dtype=f32, device=dev)
+        nbytes = int(self.lib.aimnet_embedding_scratch_bytes(n, n_mol, m))
+        scratch = getattr(self, "_emb_scratch", None)  # one buffer, grown on demand, ordered like the workspace (_workspace)
+        if scratch is None or scratch.numel() < nbytes:
+            if scratch is not None and self._ws_stream is not None:
+                scratch.record_stream(self._ws_stream)
+            self._emb_scratch = scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        ptr = lambda v: v.data_ptr() if v is not None and v.numel() else None  # noqa: E731
+        s = _lib.Embedding(n_ext=m, ext_coord=ptr(xc), ext_charge=ptr(qc), ext_mol_idx=ptr(mi), potential=ptr(pot), potential_grad=ptr(pg),
+                           ext_forces=ptr(outs.get("ext_forces")), ext_potential=ptr(outs.get("ext_potential")),
+                           energy=outs["embedding_energy"].data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
+        _lib.check(self.lib.aimnet_engine_set_embedding(self._h, C.byref(s)), "aimnet_engine_set_embedding")
+        try:
+            res = self.eval(**kw)
+        finally:
+            self.lib.aimnet_engine_set_embedding(self._h, None)
+        if kw["host_out"]:
+            outs = {k: v.cpu() for k, v in outs.items()}
+        res.update(outs)
         return res
 
     # ------------------------------------------------------------------------------------------

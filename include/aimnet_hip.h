@@ -183,6 +183,8 @@ typedef struct aimnet_outputs {
                                 repeat the evaluation (the bf16x3 operands have fp32's range); still raised, the input is the cause.
                                 Bit 6 (64), aimnet_engine_hvp with AIMNET_COULOMB_EWALD only: options.dsf_rc, there the cutoff of the
                                 real-space list, is below a system's real-space cutoff - the list misses pairs, hv is meaningless.
+                                Bit 7 (128), with aimnet_engine_set_embedding only: ext_mol_idx holds an entry outside [0, n_mol)
+                                or is not sorted.
                               7 Ewald: k-array entries the batch needs (compare with options.ewald_max_k); PME: mesh points the
                                 largest system needs (compare with options.pme_max_mesh); 0 for other methods */
   float* spin_charges; /* [n_atoms] alpha - beta of an NSE model (aimnet2.py:103), or NULL; must be NULL for 1-channel models */
@@ -234,6 +236,44 @@ int aimnet_engine_set_dftd3(aimnet_engine* e, const aimnet_dftd3_tables* t);
 #define AIMNET_DD_ROWS 2
 typedef int (*aimnet_dd_exchange_fn)(void* ctx, int32_t what, void* dev_ptr, int64_t n_float, void* hip_stream);
 int aimnet_engine_set_dd(aimnet_engine* e, const float* owned, aimnet_dd_exchange_fn fn, void* ctx);
+
+/* Electrostatic embedding (ML/MM; no reference counterpart - its docs name the use, docs/external/amber.md, openmm.md): the
+ * model's total charges q_i (aimnet_outputs.charges) interact with an external potential,
+ *   E_emb = sum_i q_i phi_i ,   phi_i = k_e sum_A Q_A / |x_i - X_A| + potential_i ,   k_e = Hartree * Bohr = 14.39964 eV A / e^2,
+ * the full product (the sites are not atoms).  The charges are NOT polarised by the field: this is the first-order coupling, with
+ * its exact gradient  -F_i = q_i grad phi_i + sum_j phi_j dq_j/dx_i  (the second term runs through the backward sweep).
+ * Two sources, alone or together:
+ *   point charges  n_ext sites, ext_coord [n_ext, 3] in A, in the frame of aimnet_inputs.coord as given; ext_charge [n_ext] in e;
+ *                  ext_mol_idx [n_ext], non-decreasing: a site acts on the atoms of its own molecule only (NULL: n_mol must be
+ *                  1).  A molecule may own no site.  Non-periodic input only (no images of the sites).  A site on top of an atom
+ *                  is caller error and surfaces as status[6] bit 5.
+ *   per atom       potential [n_atoms] in V and potential_grad [n_atoms, 3] in V / A, computed by the caller (an MM engine's mesh
+ *                  sum, a uniform field phi = -E.x, grad phi = -E); allowed with a cell.  potential_grad may be NULL for an
+ *                  energy-only request.
+ * Outputs (device, each may be NULL): ext_forces [n_ext, 3] = -dE_emb/dX_A in eV / A, ext_potential [n_ext] = k_e sum_i q_i /
+ * |x_i - X_A| in V, energy [n_mol] = E_emb of every molecule in eV (aimnet_outputs.energy and forces INCLUDE the term).
+ * scratch: device memory of at least aimnet_embedding_scratch_bytes(n_atoms, n_mol, n_ext) bytes, owned by the caller like the
+ * workspace.  Pair terms are fp32, all sums fp64 in a fixed order without atomics: results are bitwise repeatable.
+ * The struct is copied; every pointer must stay valid while evaluations run.  emb == NULL switches the mode off, and with it off
+ * aimnet_engine_eval launches exactly what it launched before.  While it is on: AIMNET_STRESS, domain decomposition and
+ * aimnet_engine_hvp are rejected (the term is carried by neither), aimnet_engine_charge_response ignores it (the charges do not
+ * see the field).  status[6] bit 7 (128): ext_mol_idx holds an entry outside [0, n_mol) or is not sorted (the kernels index
+ * through clamped copies; the results are meaningless). */
+typedef struct aimnet_embedding {
+  int32_t n_ext;
+  const float* ext_coord;
+  const float* ext_charge;
+  const int32_t* ext_mol_idx;
+  const float* potential;
+  const float* potential_grad;
+  float* ext_forces;
+  float* ext_potential;
+  double* energy;
+  void* scratch;
+  size_t scratch_bytes;
+} aimnet_embedding;
+size_t aimnet_embedding_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext);
+int aimnet_engine_set_embedding(aimnet_engine* e, const aimnet_embedding* emb);
 
 /* Bytes of scratch `aimnet_engine_eval` needs for the given problem size. */
 size_t aimnet_engine_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_cell,
