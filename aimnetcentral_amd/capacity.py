@@ -50,6 +50,14 @@ def pme_mesh_capacity(need: int) -> int:
     return int(need) * 9 // 8 + 64
 
 
+def ewald_list_cutoff(volumes, counts, accuracy: float) -> float:
+    """Cutoff of the real-space list of Ewald summation in `hvp`: the largest r_c over the systems' cell `volumes` and atom `counts` -
+    the host copy of ewald_setup_kernel's formula (the device verifies it, status[6] bit 6), widened by the rounding between the two."""
+    vols, counts = np.asarray(volumes, dtype=np.float64), np.asarray(counts, dtype=np.float64)
+    eta = (vols * vols / np.maximum(counts, 1)) ** (1.0 / 6.0) / math.sqrt(2.0 * math.pi)
+    return float(np.max(math.sqrt(-2.0 * math.log(float(accuracy))) * eta)) * (1.0 + 1e-5)
+
+
 def same_cutoff(a: float, b: float) -> bool:
     """`d3_cutoff == dsf_rc` as the engine decides it (engine.hip, d3_shares_lr_list / np_walk): on the float32 values of
     aimnet_eval_options - every host-side copy of that rule goes through here."""

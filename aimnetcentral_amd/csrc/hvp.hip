@@ -27,9 +27,11 @@
 // These kernels are written for clarity and exactness, not for the roofline: a Hessian of a 40-atom molecule is 120
 // directions x 40 atoms = 4 800 tangent rows (the GEMMs see a 4 800-row batch), everything else is far below a millisecond.
 #include <algorithm>
+#include <type_traits>
 
 #include "conv_common.h"
 #include "engine.h"
+#include "tangent_plan.h"
 
 namespace aimnet {
 namespace {
@@ -874,8 +876,7 @@ struct HvpWs {
   float* wlast;
   EwaldBuffers ew;  // Ewald summation: per-system parameters, fractional coordinates, k entries (ewald.hip)
   double* ew_tk;    // [K][max_k][2] tangent structure factors (t_P, t_Q)
-  float* ew_qtot;   // [N] alpha + beta of a two-channel model
-  float* qsum;      // [N] (aimnet_engine_charge_response) alpha + beta of every atom, read by crs_dipole_kernel
+  float* qsum;      // [N] alpha + beta of every atom: for the structure factors of a two-channel model, and for crs_dipole_kernel
   // external DFT-D3 block (4 K displaced copies as one batch)
   int *d3_idx, *d3_shift, *d3_cnt, *aslot, *d3c_idx, *d3c_shift, *d3c_cnt, *d3c_mol, *d3c_aslot;
   unsigned long long* present_part;
@@ -885,111 +886,145 @@ struct HvpWs {
   size_t total;
 };
 
-void hvp_layout(const aimnet_engine* e, int N, int n_mol, int K, const aimnet_eval_options* opt, char* base, HvpWs& W) {
+// One layout for both entries: which buffers exist, and whether the passes own theirs, is the plan's decision (tangent_plan.h);
+// nothing is re-derived here.  The fields a plan leaves out stay null.
+void tangent_layout(const aimnet_engine* e, int N, int n_mol, int K, const TangentPlan& P, char* base, HvpWs& W) {
+  W = HvpWs{};
   Carver c{base};
   const size_t n = (size_t)N, kn = (size_t)K * N;
-  const int np = e->arch.n_pass, nq = e->nq;
-  const int cap = std::max(1, opt->max_nb), cap_lr = std::max(0, opt->max_nb_lr);
+  const int nfp = P.n_fwd_pass, nq = e->nq;
   char* nl_base = c.take<char>(nlist_scratch_bytes(N, n_mol));
   if (base) nlist_carve(W.nl, nl_base, N, n_mol);
-  W.nb_idx = c.take<int>(n * cap);
-  W.nb_shift = c.take<int>(n * cap);
-  W.nb_cnt = c.take<int>(n);
-  W.lr_idx = c.take<int>(n * cap_lr);
-  W.lr_shift = c.take<int>(n * cap_lr);
-  W.lr_cnt = c.take<int>(n);
-  W.pg = c.take<float4>(n * cap);
-  const int mw = max_width(e);
-  for (int p = 0; p < np; ++p) {
-    W.a[p] = p == 0 ? nullptr : c.take<float>(n * NF);
-    W.ta[p] = p == 0 ? nullptr : c.take<float>(kn * NF);
-    W.q[p] = c.take<float>(n * nq);
-    W.tq[p] = c.take<float>(kn * nq);
-    const int ldx = e->mlp[p][0].k_in;
-    W.x[p] = c.take<float>((n + kn) * ldx);  // rows that go through a GEMM: primal rows on top of the tangent rows, one launch
-    W.tx[p] = W.x[p] ? W.x[p] + n * ldx : nullptr;
-    W.V[p] = c.take<float>(n * NV * 3);
-    W.tV[p] = c.take<float>(kn * NV * 3);
-    W.Vq[p] = c.take<float>(n * nq * H_ * 3);
-    W.tVq[p] = c.take<float>(kn * nq * H_ * 3);
-    const int nl = (int)e->mlp[p].size();
-    for (int l = 0; l < nl; ++l) {
-      W.z[p][l] = c.take<float>((n + kn) * e->mlp[p][l].k_out);
-      W.tz[p][l] = W.z[p][l] ? W.z[p][l] + n * e->mlp[p][l].k_out : nullptr;
+  W.nb_idx = c.take<int>(n * P.cap), W.nb_shift = c.take<int>(n * P.cap), W.nb_cnt = c.take<int>(n);
+  W.pg = c.take<float4>(n * P.cap);
+  for (int p = 0; p < nfp; ++p) {  // the charges, and a^p (the next pass reads it while it is updated), outlive their pass
+    if (p > 0) W.a[p] = c.take<float>(n * NF), W.ta[p] = c.take<float>(kn * NF);
+    W.q[p] = c.take<float>(n * nq), W.tq[p] = c.take<float>(kn * nq);
+  }
+  // MLP input rows, z rows, moments and NSE sums: the passes [p0, p1) write ONE set of buffers, as wide as the widest of them.
+  // Rows that go through a GEMM are stacked, primal rows on top of the tangent rows: one launch.
+  int mw = 0;  // widest hidden row of the passes
+  for (int p0 = 0, p1; p0 < nfp; p0 = p1) {
+    p1 = P.keep_passes ? p0 + 1 : nfp;
+    int ldx = 0, ldy = 0, wz[AIMNET_MAX_LAYERS] = {};
+    for (int p = p0; p < p1; ++p) {
+      const int nl = (int)e->mlp[p].size();
+      ldx = std::max(ldx, e->mlp[p][0].k_in);
+      for (int l = 0; l < nl; ++l) wz[l] = std::max(wz[l], e->mlp[p][l].k_out);
+      if (!e->arch.last_linear[p]) ldy = std::max(ldy, e->mlp[p][nl - 1].k_out);  // (an MLP that ends linear: y aliases its last z)
     }
-    if (e->arch.last_linear[p]) {
-      W.y[p] = W.z[p][nl - 1];
-      W.ty[p] = W.tz[p][nl - 1];
-    } else {
-      W.y[p] = c.take<float>((n + kn) * e->mlp[p][nl - 1].k_out);
-      W.ty[p] = W.y[p] ? W.y[p] + n * e->mlp[p][nl - 1].k_out : nullptr;
+    float* x = c.take<float>((n + kn) * ldx);
+    float* z[AIMNET_MAX_LAYERS] = {};
+    for (int l = 0; l < AIMNET_MAX_LAYERS; ++l) {
+      if (wz[l]) z[l] = c.take<float>((n + kn) * wz[l]);
+      mw = std::max(mw, wz[l]);
     }
-    W.Fm[p] = c.take<float>((size_t)n_mol * nq);
-    W.Dm[p] = c.take<float>((size_t)n_mol * nq);
-    W.tFm[p] = c.take<float>((size_t)K * n_mol * nq);
-    W.tDm[p] = c.take<float>((size_t)K * n_mol * nq);
+    float* y = ldy ? c.take<float>((n + kn) * ldy) : nullptr;
+    float *V = c.take<float>(n * NV * 3), *tV = c.take<float>(kn * NV * 3);
+    float *Vq = c.take<float>(n * nq * H_ * 3), *tVq = c.take<float>(kn * nq * H_ * 3);
+    float *Fm = c.take<float>((size_t)n_mol * nq), *Dm = c.take<float>((size_t)n_mol * nq);
+    float *tFm = c.take<float>((size_t)K * n_mol * nq), *tDm = c.take<float>((size_t)K * n_mol * nq);
+    for (int p = p0; p < p1; ++p) {
+      const int nl = (int)e->mlp[p].size();
+      W.x[p] = x;
+      W.tx[p] = x ? x + n * e->mlp[p][0].k_in : nullptr;
+      for (int l = 0; l < nl; ++l) {
+        W.z[p][l] = z[l];
+        W.tz[p][l] = z[l] ? z[l] + n * e->mlp[p][l].k_out : nullptr;
+      }
+      const bool lin = e->arch.last_linear[p] != 0;
+      W.y[p] = lin ? W.z[p][nl - 1] : y;
+      W.ty[p] = lin ? W.tz[p][nl - 1] : (y ? y + n * e->mlp[p][nl - 1].k_out : nullptr);
+      W.V[p] = V, W.tV[p] = tV, W.Vq[p] = Vq, W.tVq[p] = tVq;
+      W.Fm[p] = Fm, W.Dm[p] = Dm, W.tFm[p] = tFm, W.tDm[p] = tDm;
+    }
   }
-  for (size_t l = 0; l + 1 < e->head.size(); ++l) {
-    W.hz[l] = c.take<float>((n + kn) * e->head[l].k_out);
-    W.thz[l] = W.hz[l] ? W.hz[l] + n * e->head[l].k_out : nullptr;
+  if (P.head) {
+    mw = max_width(e);  // (the energy head's rows go through the same ping-pong buffers)
+    for (size_t l = 0; l + 1 < e->head.size(); ++l) {
+      W.hz[l] = c.take<float>((n + kn) * e->head[l].k_out);
+      W.thz[l] = W.hz[l] ? W.hz[l] + n * e->head[l].k_out : nullptr;
+    }
   }
-  for (int b = 0; b < 2; ++b) {
-    W.h[b] = c.take<float>((n + kn) * mw);  // stacked like x / z; the tangent rows start N * (row width in use) floats in
-    W.g[b] = c.take<float>((n + kn) * mw);
-    W.qbar[b] = c.take<float>(n * nq);
-    W.tqbar[b] = c.take<float>(kn * nq);
-  }
-  W.Sbar = c.take<float>(n * NF * 4);
-  W.tSbar = c.take<float>(kn * NF * 4);
-  W.Sqbar = c.take<float>(n * nq * G_ * 4);
-  W.tSqbar = c.take<float>(kn * nq * G_ * 4);
-  W.abar = c.take<float>(n * NF);
-  W.tabar = c.take<float>(kn * NF);
-  W.xbar = c.take<float>(n * 3);
-  W.txbar = c.take<float>(kn * 3);
-  W.wlast = c.take<float>((size_t)mw);
-  {  // Ewald summation: the buffers of aimnet_engine_eval + the tangent structure factors of every direction
-    const bool ew = opt->coulomb == AIMNET_COULOMB_EWALD;
-    W.ew = EwaldBuffers{};
-    W.ew.max_k = ew ? std::max(EWALD_KB, opt->ewald_max_k / EWALD_KB * EWALD_KB) : 0;
-    W.ew.sys = c.take<EwaldSystem>(ew ? (size_t)n_mol : 0);
-    W.ew.frac = c.take<double>(ew ? n * 3 : 0);
-    W.ew.k = c.take<EwaldK>(ew ? (size_t)W.ew.max_k : 0);
-    W.ew_tk = c.take<double>(ew ? 2 * (size_t)K * W.ew.max_k : 0);
-    W.ew_qtot = c.take<float>(ew && nq == 2 ? n : 0);
-  }
-  if (opt->dftd3 != 0) {
-    const int cap_d3 = std::max(1, opt->max_nb_d3);
-    const size_t cn = 4 * kn;
-    W.d3_idx = c.take<int>(n * cap_d3);
-    W.d3_shift = c.take<int>(n * cap_d3);
-    W.d3_cnt = c.take<int>(n);
-    W.aslot = c.take<int>(n);
-    W.present_part = c.take<unsigned long long>((n + 255) / 256);
-    W.d3c_idx = c.take<int>(cn * cap_d3);
-    W.d3c_shift = c.take<int>(cn * cap_d3);
-    W.d3c_cnt = c.take<int>(cn);
-    W.d3c_mol = c.take<int>(cn);
-    W.d3c_aslot = c.take<int>(cn);
-    W.d3c_x = c.take<float>(cn * 3);
-    W.d3c_w = c.take<float>(cn * 12);
-    W.d3c_dEdcn = c.take<float>(cn);
-    W.d3c_g = c.take<float>(cn * 3);
-    W.d3c_xs = c.take<float4>(cn);
-    W.d3c_e = c.take<double>(cn);
-    W.d3_scale = c.take<float>((size_t)K);
+  // h / g: stacked like x / z; the tangent rows start N * (row width in use) floats in
+  for (int b = 0; b < 2; ++b) W.h[b] = c.take<float>((n + kn) * mw);
+  if (!P.backward) W.qsum = c.take<float>(n);  // the outputs follow the forward: alpha + beta of every atom for crs_dipole_kernel
+  if (P.backward) {
+    W.lr_idx = c.take<int>(n * P.cap_lr), W.lr_shift = c.take<int>(n * P.cap_lr), W.lr_cnt = c.take<int>(n);
+    for (int b = 0; b < 2; ++b) {
+      W.g[b] = c.take<float>((n + kn) * mw);
+      W.qbar[b] = c.take<float>(n * nq), W.tqbar[b] = c.take<float>(kn * nq);
+    }
+    W.Sbar = c.take<float>(n * NF * 4), W.tSbar = c.take<float>(kn * NF * 4);
+    W.Sqbar = c.take<float>(n * nq * G_ * 4), W.tSqbar = c.take<float>(kn * nq * G_ * 4);
+    W.abar = c.take<float>(n * NF), W.tabar = c.take<float>(kn * NF);
+    W.xbar = c.take<float>(n * 3), W.txbar = c.take<float>(kn * 3);
+    W.wlast = c.take<float>((size_t)mw);
+    // Ewald summation: the buffers of aimnet_engine_eval + the tangent structure factors of every direction
+    W.ew.max_k = P.ewald_max_k;
+    W.ew.sys = c.take<EwaldSystem>(P.ewald ? (size_t)n_mol : 0);
+    W.ew.frac = c.take<double>(P.ewald ? n * 3 : 0);
+    W.ew.k = c.take<EwaldK>((size_t)P.ewald_max_k);
+    W.ew_tk = c.take<double>(2 * (size_t)K * P.ewald_max_k);
+    W.qsum = c.take<float>(P.ewald_qtot ? n : 0);
+    if (P.d3_block) {
+      const size_t cn = 4 * kn, cap_d3 = (size_t)P.cap_d3;
+      W.d3_idx = c.take<int>(n * cap_d3), W.d3_shift = c.take<int>(n * cap_d3), W.d3_cnt = c.take<int>(n);
+      W.aslot = c.take<int>(n), W.present_part = c.take<unsigned long long>((n + 255) / 256);
+      W.d3c_idx = c.take<int>(cn * cap_d3), W.d3c_shift = c.take<int>(cn * cap_d3), W.d3c_cnt = c.take<int>(cn);
+      W.d3c_mol = c.take<int>(cn), W.d3c_aslot = c.take<int>(cn);
+      W.d3c_x = c.take<float>(cn * 3), W.d3c_g = c.take<float>(cn * 3);
+      W.d3c_w = c.take<float>(cn * 12), W.d3c_dEdcn = c.take<float>(cn);
+      W.d3c_xs = c.take<float4>(cn);
+      W.d3c_e = c.take<double>(cn);
+      W.d3_scale = c.take<float>((size_t)K);
+    }
   }
   W.total = align_up(c.off, 256);
 }
 
 inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+// the pair kernels of pass p are instantiated for the charge channels the pass reads: 0 (pass 0: no charges yet), 1 or 2
+template <typename F>
+void nq_dispatch(int p, int nq, F&& launch) {
+  if (p == 0) launch(std::integral_constant<int, 0>{});
+  else if (nq == 1) launch(std::integral_constant<int, 1>{});
+  else launch(std::integral_constant<int, 2>{});
+}
+
+// ---- one tangent sweep in stages ------------------------------------------------------------------------------------------
+// tangent_plan.h decides, once, what runs; every stage below (a member of this context) reads it from the plan.
+struct Tangent {
+  aimnet_engine* e;
+  hipStream_t s;
+  const aimnet_inputs* in;
+  const aimnet_eval_options* opt;
+  const float* vectors;  // [K][N][3]
+  int K;
+  int* status;
+  TangentPlan P;  // (from here on: filled by open())
+  HvpWs W;
+  int N, n_mol, n_cell, np, nq;
+  bool pbc;
+  const int* mol_c;  // mol_idx clamped to [0, n_mol): memory-safe whatever the caller passed (status[6] reports it)
+  CoulombParams cp;
+  int qb = 0;        // index of the live qbar buffers
+  int cur = -1;      // pair of W.g holding the live adjoint rows (mlp_backward)
+  size_t kn() const { return (size_t)K * N; }
+  int open(const TangentRequest& rq, void* workspace, size_t workspace_bytes);
+  int mlp_forward(const std::vector<Layer>& Ls, int n_layers, bool last_linear, const float* hin, float* const* z, float* y);
+  int mlp_backward(const std::vector<Layer>& Ls, int n_layers, bool last_linear, const float* g_ext, float* const* z);
+  int lists(), forward(), coulomb_seeds(), backward(), d3_block(bool want_forces);
+  int head_forward() { return mlp_forward(e->head, (int)e->head.size() - 1, false, W.y[np - 1], W.hz, nullptr); }
+  int write_hvp(float* hv, float* forces), write_charge_response(float* charges, float* dq, float* dspin, float* dmu);
+};
+
 // forward of one MLP (pass MLP or energy head) on the stacked rows [N primal | K N tangent]: one bias-free GEMM per layer
 // (a second, biased one for the primal rows of a layer that ends the MLP linearly), then the activation kernel.
 // `hin` = stacked input rows, `y` = stacked buffer for the output rows of an MLP that ends with GELU (may be NULL: discarded)
-int mlp_forward(const aimnet_engine* e, hipStream_t s, const std::vector<Layer>& Ls, int n_layers, bool last_linear, const float* hin,
-                int N, int K, float* const* z, float* y, HvpWs& W) {
-  const size_t kn = (size_t)K * N;
+int Tangent::mlp_forward(const std::vector<Layer>& Ls, int n_layers, bool last_linear, const float* hin, float* const* z, float* y) {
+  const size_t kn = this->kn();
   const int M = (int)(kn + N);
   int ld_in = Ls[0].k_in;
   for (int l = 0; l < n_layers; ++l) {
@@ -1013,14 +1048,12 @@ int mlp_forward(const aimnet_engine* e, hipStream_t s, const std::vector<Layer>&
 }
 
 // backward of one MLP: (g, tg) = adjoint of its OUTPUT rows (after the last activation) -> adjoint of its input rows.
-// The rows live in the stacked ping-pong buffers W.g[b] (tangent rows behind the N primal rows); *src = index of the pair holding the input, or -1 when the input
-// is the external broadcast row `g_ext` with a zero tangent (the energy head's last layer).  Every step reads pair src and writes
-// the other one; on return *src names the pair holding the result.
-int mlp_backward(const aimnet_engine* e, hipStream_t s, const std::vector<Layer>& Ls, int n_layers, bool last_linear,
-                 const float* g_ext, int N, int K, float* const* z, HvpWs& W, int* src) {
-  const size_t kn = (size_t)K * N;
+// The rows live in the stacked ping-pong buffers W.g[b] (tangent rows behind the N primal rows); `cur` = index of the pair holding
+// the input, or -1 when the input is the external broadcast row `g_ext` with a zero tangent (the energy head's last layer).  Every
+// step reads pair cur and writes the other one; on return cur names the pair holding the result.
+int Tangent::mlp_backward(const std::vector<Layer>& Ls, int n_layers, bool last_linear, const float* g_ext, float* const* z) {
+  const size_t kn = this->kn();
   const int M = (int)(kn + N);
-  int cur = *src;
   for (int l = n_layers - 1; l >= 0; --l) {
     const Layer& L = Ls[l];
     const size_t toff = (size_t)N * L.k_out;
@@ -1040,44 +1073,38 @@ int mlp_backward(const aimnet_engine* e, hipStream_t s, const std::vector<Layer>
     RC(mlp_gemm(e, s, EPI_NONE, W.g[cur], L.k_out, L, false, 0, 0, M, L.k_in, L.k_out, nullptr, W.g[dst], nullptr, L.k_in));
     cur = dst;
   }
-  *src = cur;
   return 0;
 }
 
-// pass p of the forward + tangent sweep: conv -> MLP, then (`nse`) the NSE charge update and (`update_a`) a^{p+1} = a^p + delta_a.
-// aimnet_engine_hvp runs every pass through here and the head after them; aimnet_engine_charge_response stops after the charges of
-// pass np-2.
-int forward_pass(const aimnet_engine* e, hipStream_t s, const aimnet_inputs* in, const float* vectors, int p, int K, int cap, bool nse,
-                 bool update_a, HvpWs& W) {
-  const int N = in->n_atoms, n_mol = in->n_mol, nq = e->nq;
-  const size_t kn = (size_t)K * N;
+// the forward + tangent sweep, per pass: conv -> MLP, then (plan) the NSE charge update and a^{p+1} = a^p + delta_a
+int Tangent::forward() {
   const dim3 gik(N, K), gmk(n_mol, K), b256(256);
-  const std::vector<Layer>& Ls = e->mlp[p];
-  const int nl = (int)Ls.size(), ldx = Ls[0].k_in;
-  AIMNET_HIP_CHECK(hipMemsetAsync(W.x[p], 0, (size_t)N * ldx * sizeof(float), s));    // padding columns
-  AIMNET_HIP_CHECK(hipMemsetAsync(W.tx[p], 0, kn * ldx * sizeof(float), s));
-  const float* a_p = p == 0 ? e->afv : W.a[p];
-  const int* row_of = p == 0 ? in->numbers : nullptr;
-  const float *q_p = p > 0 ? W.q[p - 1] : nullptr, *tq_p = p > 0 ? W.tq[p - 1] : nullptr;
-#define HVP_CONV_FWD(NQV)                                                                                                       \
-  hipLaunchKernelGGL((hvp_conv_fwd_kernel<NQV>), gik, b256, 0, s, a_p, row_of, W.ta[p], q_p, tq_p, W.nb_idx, W.nb_cnt, W.pg, cap, \
-                     vectors, e->agh_a, e->agh_q, e->bp, W.x[p], W.tx[p], ldx, W.V[p], W.tV[p], W.Vq[p], W.tVq[p], N)
-  if (p == 0) HVP_CONV_FWD(0);
-  else if (nq == 1) HVP_CONV_FWD(1);
-  else HVP_CONV_FWD(2);
-#undef HVP_CONV_FWD
-  AIMNET_LAUNCH_CHECK();
-  RC(mlp_forward(e, s, Ls, nl, e->arch.last_linear[p] != 0, W.x[p], N, K, W.z[p], W.y[p], W));
-  if (nse) {
-    hipLaunchKernelGGL(hvp_nse_fwd_kernel, gmk, b256, 0, s, W.y[p], W.ty[p], Ls[nl - 1].k_out, nq, q_p, tq_p, W.nl.mol_start,
-                       in->charge, n_mol, N, W.q[p], W.tq[p], W.Fm[p], W.Dm[p], W.tFm[p], W.tDm[p]);
+  for (int p = 0; p < P.n_fwd_pass; ++p) {
+    const std::vector<Layer>& Ls = e->mlp[p];
+    const int nl = (int)Ls.size(), ldx = Ls[0].k_in;
+    AIMNET_HIP_CHECK(hipMemsetAsync(W.x[p], 0, (size_t)N * ldx * sizeof(float), s));  // padding columns
+    AIMNET_HIP_CHECK(hipMemsetAsync(W.tx[p], 0, kn() * ldx * sizeof(float), s));
+    const float* a_p = p == 0 ? e->afv : W.a[p];
+    const int* row_of = p == 0 ? in->numbers : nullptr;
+    const float *q_p = p > 0 ? W.q[p - 1] : nullptr, *tq_p = p > 0 ? W.tq[p - 1] : nullptr;
+    nq_dispatch(p, nq, [&](auto nqv) {
+      hipLaunchKernelGGL((hvp_conv_fwd_kernel<decltype(nqv)::value>), gik, b256, 0, s, a_p, row_of, W.ta[p], q_p, tq_p, W.nb_idx,
+                         W.nb_cnt, W.pg, P.cap, vectors, e->agh_a, e->agh_q, e->bp, W.x[p], W.tx[p], ldx, W.V[p], W.tV[p], W.Vq[p],
+                         W.tVq[p], N);
+    });
     AIMNET_LAUNCH_CHECK();
-  }
-  if (update_a) {
-    const size_t n_t = kn * NF;
-    hipLaunchKernelGGL(hvp_update_a_kernel, grid1(n_t), b256, 0, s, a_p, row_of, W.ta[p], W.y[p], W.ty[p], Ls[nl - 1].k_out,
-                       2 * nq, N, n_t, W.a[p + 1], W.ta[p + 1]);
-    AIMNET_LAUNCH_CHECK();
+    RC(mlp_forward(Ls, nl, e->arch.last_linear[p] != 0, W.x[p], W.z[p], W.y[p]));
+    if (P.nse[p]) {
+      hipLaunchKernelGGL(hvp_nse_fwd_kernel, gmk, b256, 0, s, W.y[p], W.ty[p], Ls[nl - 1].k_out, nq, q_p, tq_p, W.nl.mol_start,
+                         in->charge, n_mol, N, W.q[p], W.tq[p], W.Fm[p], W.Dm[p], W.tFm[p], W.tDm[p]);
+      AIMNET_LAUNCH_CHECK();
+    }
+    if (P.update_a[p]) {
+      const size_t n_t = kn() * NF;
+      hipLaunchKernelGGL(hvp_update_a_kernel, grid1(n_t), b256, 0, s, a_p, row_of, W.ta[p], W.y[p], W.ty[p], Ls[nl - 1].k_out,
+                         2 * nq, N, n_t, W.a[p + 1], W.ta[p + 1]);
+      AIMNET_LAUNCH_CHECK();
+    }
   }
   return 0;
 }
@@ -1125,64 +1152,192 @@ __global__ __launch_bounds__(256) void crs_dipole_kernel(const float* __restrict
   }
 }
 
-// workspace of aimnet_engine_charge_response: the short-range list and what the kernels of passes 0 .. np-2 touch.  Only the
-// charges (and a^p, which the next pass reads while it is updated) outlive a pass: the MLP input rows, the z rows, the moments V
-// and the NSE sums are ONE set of buffers that every pass writes again.  The fields of HvpWs it leaves alone stay null.
-void crs_layout(const aimnet_engine* e, int N, int n_mol, int K, const aimnet_eval_options* opt, char* base, HvpWs& W) {
-  W = HvpWs{};
-  Carver c{base};
-  const size_t n = (size_t)N, kn = (size_t)K * N;
-  const int npq = e->arch.n_pass - 1, nq = e->nq;  // passes 0 .. np-2 run
-  const int cap = std::max(1, opt->max_nb);
-  char* nl_base = c.take<char>(nlist_scratch_bytes(N, n_mol));
-  if (base) nlist_carve(W.nl, nl_base, N, n_mol);
-  W.nb_idx = c.take<int>(n * cap);
-  W.nb_shift = c.take<int>(n * cap);
-  W.nb_cnt = c.take<int>(n);
-  W.pg = c.take<float4>(n * cap);
-  int ldx = 0, ldy = 0, wz[AIMNET_MAX_LAYERS] = {};
-  bool y_own = false;
-  for (int p = 0; p < npq; ++p) {
-    const int nl = (int)e->mlp[p].size();
-    ldx = std::max(ldx, e->mlp[p][0].k_in);
-    for (int l = 0; l < nl; ++l) wz[l] = std::max(wz[l], e->mlp[p][l].k_out);
-    if (!e->arch.last_linear[p]) {
-      y_own = true;
-      ldy = std::max(ldy, e->mlp[p][nl - 1].k_out);
+// status words, molecule offsets (+ species slots), wrapping, and the lists with the pair geometry (u, d) of the short-range one
+int Tangent::lists() {
+  const float rc = e->arch.rc;
+  AIMNET_HIP_CHECK(hipMemsetAsync(status, 0, 8 * sizeof(int), s));
+  RC(launch_mol_start(s, in->mol_idx, N, n_mol, W.nl.mol_start, W.nl.mol_c, in->numbers, status + 6,
+                      P.want_species ? e->slot_of_z : nullptr, W.aslot, W.present_part));
+  RC(launch_wrap(s, in->coord, mol_c, N, n_mol, in->cell, n_cell, in->pbc, W.nl, in->pbc_sys, pbc ? rc : 0.0f));
+  if (P.bbox) RC(launch_bbox(s, n_mol, W.nl));
+  RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, rc, rc, P.cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
+                  status + 0, status + 2, W.pg));
+  if (P.lr_list)
+    RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->dsf_rc, -1.0f, P.cap_lr, N, 0, W.nl, W.lr_idx, W.lr_shift,
+                    W.lr_cnt, status + 1, status + 3));
+  if (P.ewald)  // per-system (alpha, rc, kc) and k boxes from the cell, fractional coordinates in double; status[7] = k entries needed
+    RC(launch_ewald_setup(s, in->cell, n_cell, W.nl.mol_start, mol_c, W.nl.xw, in->charge, nq, N, n_mol, opt->ewald_accuracy, W.ew,
+                          status + 7));
+  return 0;
+}
+
+// Coulomb seeds (+ tangents) of qbar / xbar
+int Tangent::coulomb_seeds() {
+  const dim3 gwk(ceil_div(N, 4), K), b256(256);
+  const float *q_fin = W.q[np - 2], *tq_fin = W.tq[np - 2];
+  hipLaunchKernelGGL(hvp_coulomb_sr_kernel, gwk, b256, 0, s, e->arch.sr_coulomb != 0, q_fin, tq_fin, nq, W.nb_idx, W.nb_cnt, W.pg,
+                     P.cap, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar);
+  AIMNET_LAUNCH_CHECK();
+  auto long_range = [&](auto mode) {
+    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<decltype(mode)::value>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c,
+                       W.nl.mol_start, in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, P.cap_lr, vectors, cp, N, W.qbar[qb],
+                       W.tqbar[qb], W.xbar, W.txbar, status + 6);
+  };
+  if (opt->coulomb == AIMNET_COULOMB_SIMPLE) long_range(std::integral_constant<LrMode, LrMode::Simple>{});
+  if (opt->coulomb == AIMNET_COULOMB_DSF) long_range(std::integral_constant<LrMode, LrMode::Dsf>{});
+  AIMNET_LAUNCH_CHECK();
+  if (P.ewald) {  // real space over the list, then reciprocal space + background (ewald.hip): both add onto the seeds
+    cp.ewald = W.ew.sys;
+    long_range(std::integral_constant<LrMode, LrMode::Ewald>{});
+    AIMNET_LAUNCH_CHECK();
+    const float* q_tot = q_fin;
+    if (P.ewald_qtot) {  // the structure factors see alpha + beta
+      hipLaunchKernelGGL(hvp_qtot_kernel, grid1((size_t)N), b256, 0, s, q_fin, N, W.qsum);
+      AIMNET_LAUNCH_CHECK();
+      q_tot = W.qsum;
     }
+    RC(launch_ewald_sfac(s, q_tot, W.nl.mol_start, n_mol, W.ew));
+    RC(launch_ewald_tangent(s, q_tot, tq_fin, nq, vectors, mol_c, W.nl.mol_start, N, n_mol, K, W.ew, W.ew_tk, cp.factor, W.qbar[qb],
+                            W.tqbar[qb], W.xbar, W.txbar));
   }
-  float* x = c.take<float>((n + kn) * ldx);
-  float* z[AIMNET_MAX_LAYERS] = {};
-  for (int l = 0; l < AIMNET_MAX_LAYERS; ++l)
-    if (wz[l]) z[l] = c.take<float>((n + kn) * wz[l]);
-  float* y = y_own ? c.take<float>((n + kn) * ldy) : nullptr;
-  float *V = c.take<float>(n * NV * 3), *tV = c.take<float>(kn * NV * 3);
-  float *Vq = c.take<float>(n * nq * H_ * 3), *tVq = c.take<float>(kn * nq * H_ * 3);
-  float *Fm = c.take<float>((size_t)n_mol * nq), *Dm = c.take<float>((size_t)n_mol * nq);
-  float *tFm = c.take<float>((size_t)K * n_mol * nq), *tDm = c.take<float>((size_t)K * n_mol * nq);
-  for (int p = 0; p < npq; ++p) {
-    W.a[p] = p == 0 ? nullptr : c.take<float>(n * NF);
-    W.ta[p] = p == 0 ? nullptr : c.take<float>(kn * NF);
-    W.q[p] = c.take<float>(n * nq);
-    W.tq[p] = c.take<float>(kn * nq);
-    const int nl = (int)e->mlp[p].size(), lx = e->mlp[p][0].k_in;
-    W.x[p] = x;
-    W.tx[p] = x ? x + n * lx : nullptr;
-    for (int l = 0; l < nl; ++l) {
-      W.z[p][l] = z[l];
-      W.tz[p][l] = z[l] ? z[l] + n * e->mlp[p][l].k_out : nullptr;
-    }
-    const bool lin = e->arch.last_linear[p] != 0;
-    W.y[p] = lin ? W.z[p][nl - 1] : y;
-    W.ty[p] = lin ? W.tz[p][nl - 1] : (y ? y + n * e->mlp[p][nl - 1].k_out : nullptr);
-    W.V[p] = V, W.tV[p] = tV, W.Vq[p] = Vq, W.tVq[p] = tVq;
-    W.Fm[p] = Fm, W.Dm[p] = Dm, W.tFm[p] = tFm, W.tDm[p] = tDm;
+  return 0;
+}
+
+// backward + tangent: the energy head, then the passes from the last to the first
+int Tangent::backward() {
+  const dim3 gik(N, K), gmk(n_mol, K), b256(256);
+  const int nh = (int)e->head.size();
+  AIMNET_HIP_CHECK(hipMemsetAsync(W.abar, 0, (size_t)N * NF * sizeof(float), s));
+  AIMNET_HIP_CHECK(hipMemsetAsync(W.tabar, 0, kn() * NF * sizeof(float), s));
+  const int ld = e->head[nh - 2].k_out;  // the head's last layer is the broadcast row W.wlast
+  hipLaunchKernelGGL(hvp_pad_row_kernel, dim3(ceil_div(ld, 256)), b256, 0, s, e->head_w_last, e->head[nh - 1].n_in, ld, W.wlast);
+  AIMNET_LAUNCH_CHECK();
+  RC(mlp_backward(e->head, nh - 1, false, W.wlast, W.hz));
+  for (int p = np - 1; p >= 0; --p) {
+    const std::vector<Layer>& Ls = e->mlp[p];
+    const int nl = (int)Ls.size(), ldx = Ls[0].k_in;
+    RC(mlp_backward(Ls, nl, e->arch.last_linear[p] != 0, nullptr, W.z[p]));
+    const float *xb = W.g[cur], *txb = W.g[cur] + (size_t)N * ldx;
+    const float* a_p = p == 0 ? e->afv : W.a[p];
+    const int* row_of = p == 0 ? in->numbers : nullptr;
+    const float *q_p = p > 0 ? W.q[p - 1] : nullptr, *tq_p = p > 0 ? W.tq[p - 1] : nullptr;
+    float* abar_u = p > 0 ? W.abar : nullptr;  // a^0 is the constant embedding: its adjoint is not needed
+    nq_dispatch(p, nq, [&](auto nqv) {
+      hipLaunchKernelGGL((hvp_unconcat_kernel<decltype(nqv)::value>), gik, b256, 0, s, xb, txb, ldx, W.V[p], W.tV[p], W.Vq[p],
+                         W.tVq[p], e->agh_a, e->agh_q, abar_u, W.tabar, W.qbar[qb], W.tqbar[qb], W.Sbar, W.tSbar, W.Sqbar, W.tSqbar,
+                         N);
+    });
+    AIMNET_LAUNCH_CHECK();
+    nq_dispatch(p, nq, [&](auto nqv) {
+      hipLaunchKernelGGL((hvp_conv_bwd_kernel<decltype(nqv)::value>), gik, b256, 0, s, p > 0, a_p, row_of, W.ta[p], q_p, tq_p,
+                         W.Sbar, W.tSbar, W.Sqbar, W.tSqbar, W.nb_idx, W.nb_cnt, W.pg, P.cap, vectors, e->bp, W.abar, W.tabar,
+                         W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar, N);
+    });
+    AIMNET_LAUNCH_CHECK();
+    if (p == 0) break;
+    const std::vector<Layer>& Lq = e->mlp[p - 1];
+    const int ldy = Lq[Lq.size() - 1].k_out;
+    cur ^= 1;  // xb has been consumed: the adjoint rows of pass p-1's MLP output go into the other ping-pong pair
+    hipLaunchKernelGGL(hvp_nse_bwd_kernel, gmk, b256, 0, s, W.qbar[qb], W.tqbar[qb], W.abar, W.tabar, W.y[p - 1], W.ty[p - 1], ldy, nq,
+                       W.Fm[p - 1], W.Dm[p - 1], W.tFm[p - 1], W.tDm[p - 1], W.nl.mol_start, n_mol, N, p - 1 > 0 ? 1 : 0, W.g[cur],
+                       W.g[cur] + (size_t)N * ldy, W.qbar[qb ^ 1], W.tqbar[qb ^ 1]);
+    AIMNET_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hvp_ybar_a_kernel, grid1(kn() * ldy), b256, 0, s, W.abar, W.tabar, ldy, nq, N, kn() * ldy, W.g[cur],
+                       W.g[cur] + (size_t)N * ldy);
+    AIMNET_LAUNCH_CHECK();
+    qb ^= 1;
   }
-  int mw = 0;  // widest hidden row of these passes (not the energy head's)
-  for (int l = 0; l < AIMNET_MAX_LAYERS; ++l) mw = std::max(mw, wz[l]);
-  for (int b = 0; b < 2; ++b) W.h[b] = c.take<float>((n + kn) * mw);
-  W.qsum = c.take<float>(n);
-  W.total = align_up(c.off, 256);
+  return 0;
+}
+
+// the dispersion block: central difference of the D3 gradient over all directions in one batch (see the kernels)
+int Tangent::d3_block(bool want_forces) {
+  const int cap_d3 = P.cap_d3, NC = 4 * K * N;
+  const float h = 4e-3f;
+  const dim3 b256(256);
+  RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->d3_cutoff, -1.0f, cap_d3, N, 0, W.nl, W.d3_idx, W.d3_shift,
+                  W.d3_cnt, status + 4, status + 5));
+  hipLaunchKernelGGL(hvp_d3_scale_kernel, dim3(K), b256, 0, s, vectors, N, K, W.d3_scale);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hvp_d3_replicate_kernel, dim3(N, 4 * K), dim3(64), 0, s, W.nl.xw, vectors, W.d3_scale, mol_c, W.aslot, W.d3_idx,
+                     W.d3_shift, W.d3_cnt, cap_d3, N, K, h, W.d3c_x, W.d3c_mol, W.d3c_aslot, W.d3c_idx, W.d3c_shift, W.d3c_cnt);
+  AIMNET_LAUNCH_CHECK();
+  AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_g, 0, (size_t)NC * 3 * sizeof(float), s));
+  AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_e, 0, (size_t)NC * sizeof(double), s));
+  const D3Params dp = d3_params(opt);
+  RC(launch_dftd3(s, true, false, W.d3c_x, W.d3c_mol, in->cell, n_cell, W.d3c_aslot, W.d3c_idx, W.d3c_shift, W.d3c_cnt, cap_d3, e->d3,
+                  dp, opt->d3_cutoff, NC, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, W.d3c_g, nullptr, false, cp, nullptr, nullptr));
+  hipLaunchKernelGGL(hvp_d3_combine_kernel, grid1(kn() * 3), b256, 0, s, W.d3c_g, W.d3_scale, N, kn() * 3, h, W.txbar);
+  AIMNET_LAUNCH_CHECK();
+  if (want_forces) {  // the forces of the sweep include the dispersion term: its gradient at x itself (one more evaluation)
+    AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_e, 0, (size_t)N * sizeof(double), s));
+    RC(launch_dftd3(s, true, false, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp,
+                    opt->d3_cutoff, N, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, W.xbar, nullptr, false, cp, nullptr, nullptr));
+  }
+  return 0;
+}
+
+int Tangent::write_hvp(float* hv, float* forces) {
+  AIMNET_HIP_CHECK(hipMemcpyAsync(hv, W.txbar, kn() * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (forces) {
+    hipLaunchKernelGGL(hvp_out_kernel, grid1((size_t)N * 3), dim3(256), 0, s, W.xbar, (size_t)N * 3, forces);
+    AIMNET_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+int Tangent::write_charge_response(float* charges, float* dq, float* dspin, float* dmu) {
+  hipLaunchKernelGGL(crs_out_kernel, grid1(kn()), dim3(256), 0, s, W.q[np - 2], W.tq[np - 2], nq, N, kn(), W.qsum, charges, dq, dspin);
+  AIMNET_LAUNCH_CHECK();
+  if (dmu) {
+    hipLaunchKernelGGL(crs_dipole_kernel, dim3(n_mol, K), dim3(256), 0, s, dq, W.qsum, in->coord, vectors, W.nl.mol_start, n_mol, N,
+                       dmu);
+    AIMNET_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// the plain values tangent_plan.h works on; `in` == NULL: the size queries (what the layout reads depends on no input)
+TangentRequest tangent_request(TangentEntry entry, const aimnet_engine* e, int N, int n_mol, int K, const aimnet_eval_options* opt,
+                               const aimnet_inputs* in) {
+  TangentRequest r{};
+  r.entry = entry; r.N = N; r.n_mol = n_mol; r.n_vec = K;
+  r.nq = e->nq; r.n_pass = e->arch.n_pass; r.max_width = max_width(e);
+  r.coulomb = opt->coulomb; r.dftd3 = opt->dftd3; r.dsf_rc_set = opt->dsf_rc > 0.0f;
+  r.max_nb = opt->max_nb; r.max_nb_lr = opt->max_nb_lr; r.max_nb_d3 = opt->max_nb_d3; r.ewald_max_k = opt->ewald_max_k;
+  r.ewald_kb = EWALD_KB; r.d3_tables = e->d3.ns != 0; r.emb_on = e->emb_on; r.bbox_ok = bbox_applies(N, n_mol);
+  if (!in) return r;
+  r.pbc = in->cell != nullptr; r.n_cell = in->n_cell;
+  r.ewald_args = entry == TangentEntry::Hvp && opt->coulomb == AIMNET_COULOMB_EWALD ? ewald_args_check(in, opt) : 0;
+  r.arrays = in->coord && in->numbers && in->mol_idx && in->charge;
+  r.nbmat = in->nbmat != nullptr; r.nbmat_lr = in->nbmat_lr != nullptr; r.nbmat_d3 = in->nbmat_d3 != nullptr;
+  return r;
+}
+
+size_t tangent_workspace_bytes(TangentEntry entry, const aimnet_engine* e, int N, int n_mol, int K, const aimnet_eval_options* opt) {
+  HvpWs W;
+  tangent_layout(e, N, n_mol, K, tangent_plan(tangent_request(entry, e, N, n_mol, K, opt, nullptr)), nullptr, W);
+  return W.total;
+}
+
+// validate, plan, lay out: 0 with the context filled; nothing is launched either way
+int Tangent::open(const TangentRequest& rq, void* workspace, size_t workspace_bytes) {
+  char msg[512];
+  if (const int rc = tangent_validate(rq, msg, sizeof(msg))) {
+    set_last_error("%s", msg);
+    return rc;
+  }
+  P = tangent_plan(rq);
+  AIMNET_HIP_CHECK(hipSetDevice(e->device));
+  tangent_layout(e, rq.N, rq.n_mol, K, P, (char*)workspace, W);
+  if (W.total > workspace_bytes) {
+    set_last_error("%s: workspace too small (%zu < %zu)", rq.entry == TangentEntry::Hvp ? "hvp" : "charge_response", workspace_bytes,
+                   W.total);
+    return AIMNET_E_WORKSPACE;
+  }
+  N = rq.N, n_mol = rq.n_mol, n_cell = rq.pbc ? rq.n_cell : 0, np = rq.n_pass, nq = rq.nq, pbc = rq.pbc;
+  mol_c = W.nl.mol_c, cp = coulomb_params(e->arch, opt);
+  return 0;
 }
 
 }  // namespace
@@ -1195,321 +1350,43 @@ extern "C" {
 size_t aimnet_engine_hvp_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_vec,
                                          const aimnet_eval_options* opt) {
   if (!e || !opt || n_atoms <= 0 || n_mol <= 0 || n_vec <= 0) return 0;
-  HvpWs W;
-  hvp_layout(e, n_atoms, n_mol, n_vec, opt, nullptr, W);
-  return W.total;
+  return tangent_workspace_bytes(TangentEntry::Hvp, e, n_atoms, n_mol, n_vec, opt);
 }
 
 int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const float* vectors,
                       int32_t n_vec, float* hv, float* forces, int32_t* status, void* workspace, size_t workspace_bytes,
                       void* hip_stream) {
   if (!e || !in || !opt || !vectors || !hv || !status || !workspace || n_vec <= 0) return AIMNET_E_INVALID;
-  const int N = in->n_atoms, n_mol = in->n_mol, K = n_vec;
-  if (N <= 0 || n_mol <= 0 || !in->coord || !in->numbers || !in->mol_idx || !in->charge) {
-    set_last_error("hvp: null or empty input");
-    return AIMNET_E_INVALID;
-  }
-  if (e->emb_on) {
-    set_last_error("hvp: the embedding term is not carried by the tangent sweep (aimnet_engine_set_embedding(e, NULL) first)");
-    return AIMNET_E_INVALID;
-  }
-  if (in->nbmat || in->nbmat_lr || in->nbmat_d3) {
-    set_last_error("hvp: caller-supplied neighbour matrices are not read by the tangent sweep (it builds its own lists)");
-    return AIMNET_E_INVALID;
-  }
-  const bool d3 = opt->dftd3 != 0;
-  if (d3 && e->d3.ns == 0) {
-    set_last_error("hvp: DFT-D3 requested but aimnet_engine_set_dftd3 was never called");
-    return AIMNET_E_INVALID;
-  }
-  // the tangent kernels index the directions with grid.y (HIP limit 65535); the D3 block replicates every direction four times
-  if (n_vec > (d3 ? 16383 : 65535)) {
-    set_last_error("hvp: at most %d directions per sweep (%d given): split them over several calls", d3 ? 16383 : 65535, n_vec);
-    return AIMNET_E_INVALID;
-  }
-  if (d3 && 4 * (size_t)n_vec * (size_t)in->n_atoms * (size_t)std::max(1, opt->max_nb_d3) >= (size_t)INT32_MAX) {
-    set_last_error("hvp: n_vec * n_atoms * max_nb_d3 too large for one sweep (split the directions)");
-    return AIMNET_E_INVALID;
-  }
-  const bool pbc = in->cell != nullptr;
-  const int coulomb = opt->coulomb;
-  if (coulomb == AIMNET_COULOMB_DSF && opt->max_nb_lr <= 0) {
-    set_last_error("hvp: DSF Coulomb needs max_nb_lr > 0 (the tangent sweep runs on the neighbour list, also for periodic input)");
-    return AIMNET_E_INVALID;
-  }
-  if (coulomb == AIMNET_COULOMB_PME) {
-    set_last_error("hvp: the analytic tangent sweep does not cover particle-mesh Ewald (use the exact Ewald sum or DSF, or differences "
-                   "of forces as the reference does for its PME block, lr.py:903-926)");
-    return AIMNET_E_INVALID;
-  }
-  const bool ewald = coulomb == AIMNET_COULOMB_EWALD;
-  if (ewald) {
-    const int bad = ewald_args_check(in, opt);
-    if (bad == 1) {
-      set_last_error("hvp: Ewald summation needs a cell that is periodic along all three axes (lr.py:655-657)");
-      return AIMNET_E_INVALID;
-    }
-    if (bad) {
-      set_last_error("hvp: Ewald summation needs 0 < ewald_accuracy < 1 and ewald_max_k >= %d", EWALD_KB);
-      return AIMNET_E_INVALID;
-    }
-    if (opt->max_nb_lr <= 0 || !(opt->dsf_rc > 0.0f)) {
-      set_last_error("hvp: Ewald summation runs its real-space term on the neighbour list: dsf_rc (the list cutoff, at least every "
-                     "system's real-space cutoff) and max_nb_lr must be > 0");
-      return AIMNET_E_INVALID;
-    }
-  }
-  if (coulomb == AIMNET_COULOMB_SIMPLE && pbc) {
-    set_last_error("hvp: 'simple' Coulomb is undefined for periodic input");
-    return AIMNET_E_INVALID;
-  }
-  if (pbc && !(in->n_cell == 1 || in->n_cell == n_mol)) {
-    set_last_error("hvp: n_cell must be 1 or n_mol");
-    return AIMNET_E_INVALID;
-  }
-  if ((size_t)K * (size_t)N * (size_t)max_width(e) >= (size_t)INT32_MAX) {
-    set_last_error("hvp: n_vec * n_atoms too large for one sweep (split the directions)");
-    return AIMNET_E_INVALID;
-  }
-  hipStream_t s = (hipStream_t)hip_stream;
-  AIMNET_HIP_CHECK(hipSetDevice(e->device));
-  HvpWs W;
-  hvp_layout(e, N, n_mol, K, opt, (char*)workspace, W);
-  if (W.total > workspace_bytes) {
-    set_last_error("hvp: workspace too small (%zu < %zu)", workspace_bytes, W.total);
-    return AIMNET_E_WORKSPACE;
-  }
-  const aimnet_arch& ar = e->arch;
-  const int np = ar.n_pass, nq = e->nq;
-  const int cap = std::max(1, opt->max_nb), cap_lr = std::max(0, opt->max_nb_lr);
-  const int n_cell = pbc ? in->n_cell : 0;
-  const size_t kn = (size_t)K * N;
-
-  // ---- lists + pair geometry: the same builders as aimnet_engine_eval ----
-  AIMNET_HIP_CHECK(hipMemsetAsync(status, 0, 8 * sizeof(int), s));
-  RC(launch_mol_start(s, in->mol_idx, N, n_mol, W.nl.mol_start, W.nl.mol_c, in->numbers, status + 6, d3 ? e->slot_of_z : nullptr,
-                      d3 ? W.aslot : nullptr, d3 ? W.present_part : nullptr));
-  const int* mol_c = W.nl.mol_c;
-  RC(launch_wrap(s, in->coord, mol_c, N, n_mol, in->cell, n_cell, in->pbc, W.nl, in->pbc_sys, pbc ? ar.rc : 0.0f));
-  if (!pbc && bbox_applies(N, n_mol)) RC(launch_bbox(s, n_mol, W.nl));
-  RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, ar.rc, ar.rc, cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
-                  status + 0, status + 2, W.pg));
-  if (coulomb == AIMNET_COULOMB_DSF || ewald)
-    RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->dsf_rc, -1.0f, cap_lr, N, 0, W.nl, W.lr_idx, W.lr_shift,
-                    W.lr_cnt, status + 1, status + 3));
-  if (ewald)  // per-system (alpha, rc, kc) and k boxes from the cell, fractional coordinates in double; status[7] = k entries needed
-    RC(launch_ewald_setup(s, in->cell, n_cell, W.nl.mol_start, mol_c, W.nl.xw, in->charge, nq, N, n_mol, opt->ewald_accuracy, W.ew,
-                          status + 7));
-
-  // ---- forward + tangent ----
-  for (int p = 0; p < np; ++p) RC(forward_pass(e, s, in, vectors, p, K, cap, p < np - 1, p < np - 1, W));
-  const int nh = (int)e->head.size();
-  {
-    RC(mlp_forward(e, s, e->head, nh - 1, false, W.y[np - 1], N, K, W.hz, nullptr, W));
-  }
-
-  // ---- Coulomb seeds (+ tangents) of qbar / xbar ----
-  const dim3 gik(N, K), gmk(n_mol, K), gwk(ceil_div(N, 4), K), b256(256);
-  CoulombParams cp = coulomb_params(ar, opt);
-  int qb = 0;  // index of the live qbar buffers
-  const float *q_fin = W.q[np - 2], *tq_fin = W.tq[np - 2];
-  hipLaunchKernelGGL(hvp_coulomb_sr_kernel, gwk, b256, 0, s, ar.sr_coulomb != 0, q_fin, tq_fin, nq, W.nb_idx, W.nb_cnt, W.pg, cap,
-                     vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar);
-  AIMNET_LAUNCH_CHECK();
-  if (coulomb == AIMNET_COULOMB_SIMPLE) {
-    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<LrMode::Simple>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start,
-                       in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar,
-                       W.txbar, status + 6);
-    AIMNET_LAUNCH_CHECK();
-  } else if (coulomb == AIMNET_COULOMB_DSF) {
-    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<LrMode::Dsf>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start,
-                       in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar,
-                       W.txbar, status + 6);
-    AIMNET_LAUNCH_CHECK();
-  } else if (ewald) {  // real space over the list, then reciprocal space + background (ewald.hip): both add onto the seeds
-    cp.ewald = W.ew.sys;
-    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<LrMode::Ewald>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c, W.nl.mol_start,
-                       in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, cap_lr, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar,
-                       W.txbar, status + 6);
-    AIMNET_LAUNCH_CHECK();
-    const float* q_tot = q_fin;
-    if (nq == 2) {  // the structure factors see alpha + beta
-      hipLaunchKernelGGL(hvp_qtot_kernel, grid1((size_t)N), b256, 0, s, q_fin, N, W.ew_qtot);
-      AIMNET_LAUNCH_CHECK();
-      q_tot = W.ew_qtot;
-    }
-    RC(launch_ewald_sfac(s, q_tot, W.nl.mol_start, n_mol, W.ew));
-    RC(launch_ewald_tangent(s, q_tot, tq_fin, nq, vectors, mol_c, W.nl.mol_start, N, n_mol, K, W.ew, W.ew_tk, cp.factor, W.qbar[qb],
-                            W.tqbar[qb], W.xbar, W.txbar));
-  }
-
-  // ---- backward + tangent ----
-  AIMNET_HIP_CHECK(hipMemsetAsync(W.abar, 0, (size_t)N * NF * sizeof(float), s));
-  AIMNET_HIP_CHECK(hipMemsetAsync(W.tabar, 0, kn * NF * sizeof(float), s));
-  int cur = -1;
-  {
-    const Layer& Ll = e->head[nh - 1];
-    const int ld = e->head[nh - 2].k_out;
-    hipLaunchKernelGGL(hvp_pad_row_kernel, dim3(ceil_div(ld, 256)), b256, 0, s, e->head_w_last, Ll.n_in, ld, W.wlast);
-    AIMNET_LAUNCH_CHECK();
-    RC(mlp_backward(e, s, e->head, nh - 1, false, W.wlast, N, K, W.hz, W, &cur));
-  }
-  for (int p = np - 1; p >= 0; --p) {
-    const std::vector<Layer>& Ls = e->mlp[p];
-    const int nl = (int)Ls.size(), ldx = Ls[0].k_in;
-    RC(mlp_backward(e, s, Ls, nl, ar.last_linear[p] != 0, nullptr, N, K, W.z[p], W, &cur));
-    const float *xb = W.g[cur], *txb = W.g[cur] + (size_t)N * ldx;
-    const float* a_p = p == 0 ? e->afv : W.a[p];
-    const int* row_of = p == 0 ? in->numbers : nullptr;
-    const float *q_p = p > 0 ? W.q[p - 1] : nullptr, *tq_p = p > 0 ? W.tq[p - 1] : nullptr;
-    float* abar_u = p > 0 ? W.abar : nullptr;  // a^0 is the constant embedding: its adjoint is not needed
-#define HVP_UNCONCAT(NQV)                                                                                                         \
-  hipLaunchKernelGGL((hvp_unconcat_kernel<NQV>), gik, b256, 0, s, xb, txb, ldx, W.V[p], W.tV[p], W.Vq[p], W.tVq[p], e->agh_a,     \
-                     e->agh_q, abar_u, W.tabar, W.qbar[qb], W.tqbar[qb], W.Sbar, W.tSbar, W.Sqbar, W.tSqbar, N)
-#define HVP_CONV_BWD(NQV)                                                                                                         \
-  hipLaunchKernelGGL((hvp_conv_bwd_kernel<NQV>), gik, b256, 0, s, p > 0, a_p, row_of, W.ta[p], q_p, tq_p, W.Sbar, W.tSbar, W.Sqbar, \
-                     W.tSqbar, W.nb_idx, W.nb_cnt, W.pg, cap, vectors, e->bp, W.abar, W.tabar, W.qbar[qb], W.tqbar[qb], W.xbar,  \
-                     W.txbar, N)
-    if (p == 0) HVP_UNCONCAT(0);
-    else if (nq == 1) HVP_UNCONCAT(1);
-    else HVP_UNCONCAT(2);
-    AIMNET_LAUNCH_CHECK();
-    if (p == 0) HVP_CONV_BWD(0);
-    else if (nq == 1) HVP_CONV_BWD(1);
-    else HVP_CONV_BWD(2);
-    AIMNET_LAUNCH_CHECK();
-#undef HVP_UNCONCAT
-#undef HVP_CONV_BWD
-    if (p == 0) break;
-    const std::vector<Layer>& Lq = e->mlp[p - 1];
-    const int ldy = Lq[Lq.size() - 1].k_out;
-    cur ^= 1;  // xb has been consumed: the adjoint rows of pass p-1's MLP output go into the other ping-pong pair
-    hipLaunchKernelGGL(hvp_nse_bwd_kernel, gmk, b256, 0, s, W.qbar[qb], W.tqbar[qb], W.abar, W.tabar, W.y[p - 1], W.ty[p - 1], ldy, nq,
-                       W.Fm[p - 1], W.Dm[p - 1], W.tFm[p - 1], W.tDm[p - 1], W.nl.mol_start, n_mol, N, p - 1 > 0 ? 1 : 0, W.g[cur],
-                       W.g[cur] + (size_t)N * ldy, W.qbar[qb ^ 1], W.tqbar[qb ^ 1]);
-    AIMNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(hvp_ybar_a_kernel, grid1(kn * ldy), b256, 0, s, W.abar, W.tabar, ldy, nq, N, kn * ldy, W.g[cur], W.g[cur] + (size_t)N * ldy);
-    AIMNET_LAUNCH_CHECK();
-    qb ^= 1;
-  }
-  if (d3) {  // the dispersion block: central difference of the D3 gradient over all directions in one batch (see the kernels)
-    const int cap_d3 = std::max(1, opt->max_nb_d3);
-    const float h = 4e-3f;
-    const int NC = 4 * K * N;
-    RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->d3_cutoff, -1.0f, cap_d3, N, 0, W.nl, W.d3_idx, W.d3_shift,
-                    W.d3_cnt, status + 4, status + 5));
-    hipLaunchKernelGGL(hvp_d3_scale_kernel, dim3(K), b256, 0, s, vectors, N, K, W.d3_scale);
-    AIMNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(hvp_d3_replicate_kernel, dim3(N, 4 * K), dim3(64), 0, s, W.nl.xw, vectors, W.d3_scale, mol_c, W.aslot,
-                       W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, N, K, h, W.d3c_x, W.d3c_mol, W.d3c_aslot, W.d3c_idx, W.d3c_shift,
-                       W.d3c_cnt);
-    AIMNET_LAUNCH_CHECK();
-    AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_g, 0, (size_t)NC * 3 * sizeof(float), s));
-    AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_e, 0, (size_t)NC * sizeof(double), s));
-    const D3Params dp = d3_params(opt);
-    RC(launch_dftd3(s, true, false, W.d3c_x, W.d3c_mol, in->cell, n_cell, W.d3c_aslot, W.d3c_idx, W.d3c_shift, W.d3c_cnt, cap_d3,
-                    e->d3, dp, opt->d3_cutoff, NC, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, W.d3c_g, nullptr, false, cp, nullptr,
-                    nullptr));
-    hipLaunchKernelGGL(hvp_d3_combine_kernel, grid1(kn * 3), b256, 0, s, W.d3c_g, W.d3_scale, N, kn * 3, h, W.txbar);
-    AIMNET_LAUNCH_CHECK();
-    if (forces) {  // the forces of the sweep include the dispersion term: its gradient at x itself (one more evaluation)
-      AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_e, 0, (size_t)N * sizeof(double), s));
-      RC(launch_dftd3(s, true, false, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp,
-                      opt->d3_cutoff, N, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, W.xbar, nullptr, false, cp, nullptr, nullptr));
-    }
-  }
-  AIMNET_HIP_CHECK(hipMemcpyAsync(hv, W.txbar, kn * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (forces) {
-    hipLaunchKernelGGL(hvp_out_kernel, grid1((size_t)N * 3), b256, 0, s, W.xbar, (size_t)N * 3, forces);
-    AIMNET_LAUNCH_CHECK();
-  }
-  return AIMNET_OK;
+  TangentRequest rq = tangent_request(TangentEntry::Hvp, e, in->n_atoms, in->n_mol, n_vec, opt, in);
+  rq.hv = true; rq.forces = forces != nullptr;
+  Tangent t{e, (hipStream_t)hip_stream, in, opt, vectors, n_vec, status};
+  RC(t.open(rq, workspace, workspace_bytes));
+  RC(t.lists());
+  RC(t.forward());
+  RC(t.head_forward());
+  RC(t.coulomb_seeds());
+  RC(t.backward());
+  if (t.P.d3_block) RC(t.d3_block(forces != nullptr));
+  return t.write_hvp(hv, forces);
 }
 
 size_t aimnet_engine_charge_response_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_vec,
                                                      const aimnet_eval_options* opt) {
   if (!e || !opt || n_atoms <= 0 || n_mol <= 0 || n_vec <= 0 || e->arch.n_pass < 2) return 0;
-  HvpWs W;
-  crs_layout(e, n_atoms, n_mol, n_vec, opt, nullptr, W);
-  return W.total;
+  return tangent_workspace_bytes(TangentEntry::ChargeResponse, e, n_atoms, n_mol, n_vec, opt);
 }
 
 int aimnet_engine_charge_response(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const float* vectors,
                                   int32_t n_vec, float* charges, float* dq, float* dspin, float* dmu, int32_t* status,
                                   void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!e || !in || !opt || !vectors || !status || !workspace || n_vec <= 0) return AIMNET_E_INVALID;
-  if (!dq) {
-    set_last_error("charge_response: dq is required");
-    return AIMNET_E_INVALID;
-  }
-  const int N = in->n_atoms, n_mol = in->n_mol, K = n_vec;
-  if (N <= 0 || n_mol <= 0 || !in->coord || !in->numbers || !in->mol_idx || !in->charge) {
-    set_last_error("charge_response: null or empty input");
-    return AIMNET_E_INVALID;
-  }
-  if (in->nbmat || in->nbmat_lr || in->nbmat_d3) {
-    set_last_error("charge_response: caller-supplied neighbour matrices are not read by the tangent sweep (it builds its own list)");
-    return AIMNET_E_INVALID;
-  }
-  if (n_vec > 65535) {  // the tangent kernels index the directions with grid.y
-    set_last_error("charge_response: at most 65535 directions per sweep (%d given): split them over several calls", n_vec);
-    return AIMNET_E_INVALID;
-  }
-  const aimnet_arch& ar = e->arch;
-  const int np = ar.n_pass, nq = e->nq;
-  if (np < 2) {
-    set_last_error("charge_response: a model with one pass has no charges");
-    return AIMNET_E_INVALID;
-  }
-  if (dspin && nq != 2) {
-    set_last_error("charge_response: dspin is defined for two charge channels; this model has one");
-    return AIMNET_E_INVALID;
-  }
-  const bool pbc = in->cell != nullptr;
-  if (dmu && pbc) {
-    set_last_error("charge_response: the dipole moment of a periodic cell is not defined (pass dmu = NULL)");
-    return AIMNET_E_INVALID;
-  }
-  if (pbc && !(in->n_cell == 1 || in->n_cell == n_mol)) {
-    set_last_error("charge_response: n_cell must be 1 or n_mol");
-    return AIMNET_E_INVALID;
-  }
-  if ((size_t)K * (size_t)N * (size_t)max_width(e) >= (size_t)INT32_MAX) {
-    set_last_error("charge_response: n_vec * n_atoms too large for one sweep (split the directions)");
-    return AIMNET_E_INVALID;
-  }
-  hipStream_t s = (hipStream_t)hip_stream;
-  AIMNET_HIP_CHECK(hipSetDevice(e->device));
-  HvpWs W;
-  crs_layout(e, N, n_mol, K, opt, (char*)workspace, W);
-  if (W.total > workspace_bytes) {
-    set_last_error("charge_response: workspace too small (%zu < %zu)", workspace_bytes, W.total);
-    return AIMNET_E_WORKSPACE;
-  }
-  const int cap = std::max(1, opt->max_nb);
-  const int n_cell = pbc ? in->n_cell : 0;
-
-  // ---- the short-range list + pair geometry, as aimnet_engine_hvp builds them ----
-  AIMNET_HIP_CHECK(hipMemsetAsync(status, 0, 8 * sizeof(int), s));
-  RC(launch_mol_start(s, in->mol_idx, N, n_mol, W.nl.mol_start, W.nl.mol_c, in->numbers, status + 6, nullptr, nullptr, nullptr));
-  const int* mol_c = W.nl.mol_c;
-  RC(launch_wrap(s, in->coord, mol_c, N, n_mol, in->cell, n_cell, in->pbc, W.nl, in->pbc_sys, pbc ? ar.rc : 0.0f));
-  if (!pbc && bbox_applies(N, n_mol)) RC(launch_bbox(s, n_mol, W.nl));
-  RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, ar.rc, ar.rc, cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
-                  status + 0, status + 2, W.pg));
-
-  // ---- forward + tangent up to the NSE of pass np-2: the charges see nothing after it ----
-  for (int p = 0; p < np - 1; ++p) RC(forward_pass(e, s, in, vectors, p, K, cap, true, p < np - 2, W));
-
-  const size_t kn = (size_t)K * N;
-  hipLaunchKernelGGL(crs_out_kernel, grid1(kn), dim3(256), 0, s, W.q[np - 2], W.tq[np - 2], nq, N, kn, W.qsum, charges, dq, dspin);
-  AIMNET_LAUNCH_CHECK();
-  if (dmu) {
-    hipLaunchKernelGGL(crs_dipole_kernel, dim3(n_mol, K), dim3(256), 0, s, dq, W.qsum, in->coord, vectors, W.nl.mol_start, n_mol, N,
-                       dmu);
-    AIMNET_LAUNCH_CHECK();
-  }
-  return AIMNET_OK;
+  TangentRequest rq = tangent_request(TangentEntry::ChargeResponse, e, in->n_atoms, in->n_mol, n_vec, opt, in);
+  rq.charges = charges != nullptr; rq.dq = dq != nullptr; rq.dspin = dspin != nullptr; rq.dmu = dmu != nullptr;
+  Tangent t{e, (hipStream_t)hip_stream, in, opt, vectors, n_vec, status};
+  RC(t.open(rq, workspace, workspace_bytes));
+  RC(t.lists());
+  RC(t.forward());
+  return t.write_charge_response(charges, dq, dspin, dmu);
 }
 
 }  // extern "C"

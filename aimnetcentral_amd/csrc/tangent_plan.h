@@ -1,0 +1,120 @@
+// tangent_plan.h - every decision of one aimnet_engine_hvp / aimnet_engine_charge_response call, taken once from plain values, as
+// eval_plan.h does for aimnet_engine_eval.  Host code only (no HIP): hvp.hip fills a TangentRequest, checks it (tangent_validate),
+// plans it (tangent_plan), lays the workspace out and runs its stages off the plan; tests/tangent_plan_main.cpp walks the same
+// functions on the CPU.  What the layout reads depends on (engine, sizes, options) alone: the size queries fill no inputs or outputs.
+#pragma once
+
+#include "eval_plan.h"  // plan_reject
+
+namespace aimnet {
+
+enum class TangentEntry { Hvp, ChargeResponse };
+
+struct TangentRequest {
+  TangentEntry entry;
+  int N, n_mol, n_vec, n_cell;  // n_cell as the caller passed it (read with pbc only)
+  bool pbc;                     // inputs.cell given
+  int nq, n_pass, max_width;    // engine: charge channels, passes, max_width(engine)
+  int coulomb, dftd3, max_nb, max_nb_lr, max_nb_d3, ewald_max_k;  // the options the sweeps read ...
+  bool dsf_rc_set;                                                // ... and options.dsf_rc > 0
+  int ewald_kb, ewald_args;  // EWALD_KB (kernels.h); Ewald only: ewald_args_check (engine.h) of the inputs, else 0
+  bool d3_tables, emb_on;    // aimnet_engine_set_dftd3 was called; an embedding is set (aimnet_engine_set_embedding)
+  bool bbox_ok, arrays;      // bbox_applies(N, n_mol); coord, numbers, mol_idx and charge are all given
+  bool nbmat, nbmat_lr, nbmat_d3;            // caller-supplied matrices
+  bool hv, forces, dq, dspin, dmu, charges;  // outputs given: of Hvp (hv, forces), of ChargeResponse (the other four)
+};
+
+// ---- argument checks: 0, or AIMNET_E_INVALID with the message in msg.  Nothing has been launched when they run --------------------
+inline int tangent_validate(const TangentRequest& r, char* msg, size_t n) {
+  const bool hvp = r.entry == TangentEntry::Hvp;
+  const char* who = hvp ? "hvp" : "charge_response";
+  const bool d3 = hvp && r.dftd3 != 0;
+  if (!hvp && !r.dq) return plan_reject(msg, n, "charge_response: dq is required");
+  if (r.N <= 0 || r.n_mol <= 0 || !r.arrays) return plan_reject(msg, n, "%s: null or empty input", who);
+  if (hvp && r.emb_on)
+    return plan_reject(msg, n, "hvp: the embedding term is not carried by the tangent sweep (aimnet_engine_set_embedding(e, NULL) first)");
+  if (r.nbmat || r.nbmat_lr || r.nbmat_d3)
+    return plan_reject(msg, n, "%s: caller-supplied neighbour matrices are not read by the tangent sweep (it builds its own %s)", who,
+                       hvp ? "lists" : "list");
+  if (d3 && !r.d3_tables) return plan_reject(msg, n, "hvp: DFT-D3 requested but aimnet_engine_set_dftd3 was never called");
+  // the tangent kernels index the directions with grid.y (HIP limit 65535); the D3 block replicates every direction four times
+  const int k_max = d3 ? 16383 : 65535;
+  if (r.n_vec > k_max)
+    return plan_reject(msg, n, "%s: at most %d directions per sweep (%d given): split them over several calls", who, k_max, r.n_vec);
+  if (hvp) {
+    if (d3 && 4 * (size_t)r.n_vec * (size_t)r.N * (size_t)std::max(1, r.max_nb_d3) >= (size_t)INT32_MAX)
+      return plan_reject(msg, n, "hvp: n_vec * n_atoms * max_nb_d3 too large for one sweep (split the directions)");
+    if (r.coulomb == AIMNET_COULOMB_DSF && r.max_nb_lr <= 0)
+      return plan_reject(msg, n,
+                         "hvp: DSF Coulomb needs max_nb_lr > 0 (the tangent sweep runs on the neighbour list, also for periodic input)");
+    if (r.coulomb == AIMNET_COULOMB_PME)
+      return plan_reject(msg, n,
+                         "hvp: the analytic tangent sweep does not cover particle-mesh Ewald (use the exact Ewald sum or DSF, or "
+                         "differences of forces as the reference does for its PME block, lr.py:903-926)");
+    if (r.coulomb == AIMNET_COULOMB_EWALD) {
+      if (r.ewald_args == 1)
+        return plan_reject(msg, n, "hvp: Ewald summation needs a cell that is periodic along all three axes (lr.py:655-657)");
+      if (r.ewald_args)
+        return plan_reject(msg, n, "hvp: Ewald summation needs 0 < ewald_accuracy < 1 and ewald_max_k >= %d", r.ewald_kb);
+      if (r.max_nb_lr <= 0 || !r.dsf_rc_set)
+        return plan_reject(msg, n,
+                           "hvp: Ewald summation runs its real-space term on the neighbour list: dsf_rc (the list cutoff, at least every "
+                           "system's real-space cutoff) and max_nb_lr must be > 0");
+    }
+    if (r.coulomb == AIMNET_COULOMB_SIMPLE && r.pbc) return plan_reject(msg, n, "hvp: 'simple' Coulomb is undefined for periodic input");
+  } else {
+    if (r.n_pass < 2) return plan_reject(msg, n, "charge_response: a model with one pass has no charges");
+    if (r.dspin && r.nq != 2)
+      return plan_reject(msg, n, "charge_response: dspin is defined for two charge channels; this model has one");
+    if (r.dmu && r.pbc)
+      return plan_reject(msg, n, "charge_response: the dipole moment of a periodic cell is not defined (pass dmu = NULL)");
+  }
+  if (r.pbc && !(r.n_cell == 1 || r.n_cell == r.n_mol)) return plan_reject(msg, n, "%s: n_cell must be 1 or n_mol", who);
+  if ((size_t)r.n_vec * (size_t)r.N * (size_t)r.max_width >= (size_t)INT32_MAX)
+    return plan_reject(msg, n, "%s: n_vec * n_atoms too large for one sweep (split the directions)", who);
+  return 0;
+}
+
+// ---- the plan of a request that passed the checks ---------------------------------------------------------------------------------
+struct TangentPlan {
+  // forward + tangent: Hvp runs every pass and the energy head after them; ChargeResponse stops after the NSE charges of pass
+  // n_pass - 2 (the charges see nothing after it).  Pass p ends with the NSE charge update / with a^{p+1} = a^p + delta_a:
+  int n_fwd_pass;
+  bool nse[AIMNET_MAX_PASS], update_a[AIMNET_MAX_PASS];
+  bool head;      // energy head, forward and backward
+  bool backward;  // Coulomb seeds of qbar / xbar and the backward + tangent sweep (with the buffers of both)
+  // the backward reads the MLP rows x / z / y, the moments V / Vq and the NSE sums Fm / Dm of every pass again: each pass owns
+  // its set.  Without it ONE set, sized by the widest pass, is written again by every pass.
+  bool keep_passes;
+  int cap, cap_lr, cap_d3;  // row capacities: short-range list, long-range buffers, D3 list (0: no D3 block)
+  bool lr_list;             // a long-range list is built (DSF, or the real-space term of Ewald summation)
+  bool ewald, ewald_qtot;   // Ewald stages; a two-channel model: the structure factors see alpha + beta, formed in a buffer of its own
+  int ewald_max_k;          // Ewald k entries (0: method not chosen)
+  bool d3_block;            // the external DFT-D3 block (central difference of its gradient over all directions)
+  bool want_species;        // species slots + present masks are formed (DFT-D3)
+  bool bbox;                // non-periodic: bounding-box cell grid
+};
+
+inline TangentPlan tangent_plan(const TangentRequest& r) {
+  TangentPlan P{};
+  const bool hvp = r.entry == TangentEntry::Hvp;
+  P.n_fwd_pass = hvp ? r.n_pass : r.n_pass - 1;
+  for (int p = 0; p < P.n_fwd_pass; ++p) {  // (Hvp: the last pass feeds the energy head only)
+    P.nse[p] = p < r.n_pass - 1;
+    P.update_a[p] = p + 1 < P.n_fwd_pass;
+  }
+  P.head = P.backward = P.keep_passes = hvp;
+  P.cap = std::max(1, r.max_nb);
+  P.cap_lr = hvp ? std::max(0, r.max_nb_lr) : 0;
+  P.d3_block = hvp && r.dftd3 != 0;
+  P.cap_d3 = P.d3_block ? std::max(1, r.max_nb_d3) : 0;
+  P.ewald = hvp && r.coulomb == AIMNET_COULOMB_EWALD;
+  P.lr_list = hvp && (r.coulomb == AIMNET_COULOMB_DSF || P.ewald);
+  P.ewald_max_k = P.ewald ? std::max(r.ewald_kb, r.ewald_max_k / r.ewald_kb * r.ewald_kb) : 0;
+  P.ewald_qtot = P.ewald && r.nq == 2;
+  P.want_species = P.d3_block;
+  P.bbox = !r.pbc && r.bbox_ok;
+  return P;
+}
+
+}  // namespace aimnet

@@ -257,8 +257,8 @@ class HipEngine(capacity.Capacities):
                                         "the row capacity has been grown - repeat them" % len(st))
 
     def _inputs(self, who: str, coord, numbers, mol_idx, charge, cell, pbc):
-        """Device tensors of the right dtype and layout for `eval` / `hvp` (`who`, for the messages): the filled aimnet_inputs and
-        the tensors it points into (keep them alive for as long as it is used)."""
+        """Device tensors of the right dtype and layout for `eval` / `hvp` / `charge_response` (`who`, for the messages): the filled
+        aimnet_inputs and the tensors it points into (keep them alive for as long as it is used)."""
         import torch
 
         dev = self.device
@@ -269,7 +269,7 @@ class HipEngine(capacity.Capacities):
             if charge.ndim != 2 or charge.shape[1] != 2:
                 raise ValueError(f"HipEngine.{who}: a 2-channel (NSE) model needs charge of shape [n_mol, 2] (alpha, beta)")
             charge = charge.t().contiguous()  # channel-major planes, include/aimnet_hip.h aimnet_inputs.charge
-        elif who == "hvp":
+        elif who != "eval":
             charge = charge.reshape(-1)
         elif charge.ndim != 1:
             raise ValueError("HipEngine.eval: charge must have shape [n_mol]")
@@ -277,7 +277,7 @@ class HipEngine(capacity.Capacities):
         n, n_mol = t["coord"].shape[0], charge.shape[-1]
         inp = _lib.Inputs(n_atoms=n, n_mol=n_mol)
         if n == 0 or n_mol == 0:
-            raise ValueError("HipEngine.eval: empty input (no atoms or no molecules)" if who == "eval" else "HipEngine.hvp: empty input")
+            raise ValueError(f"HipEngine.{who}: empty input" + (" (no atoms or no molecules)" if who == "eval" else ""))
         if cell is not None:
             t["cell"] = cell = cell.to(device=dev, dtype=torch.float32).contiguous()
             inp.cell, inp.n_cell = cell.data_ptr(), 1 if cell.ndim == 2 else cell.shape[0]
@@ -558,40 +558,49 @@ class HipEngine(capacity.Capacities):
                 raise ValueError("HipEngine.hvp: coulomb='ewald' needs a periodic cell")
             if not (0.0 < float(ewald_accuracy) < 1.0):
                 raise ValueError("HipEngine.hvp: ewald_accuracy must lie in (0, 1)")
-            # the real-space term runs on a list: its cutoff is the largest r_c of the batch (ewald_setup_kernel's formula on the
-            # host; the device verifies it, status[6] bit 6), widened by the rounding between the two
+            # the real-space term runs on a list: its cutoff is the largest r_c of the batch
             counts = torch.bincount(t["mol_idx"].long().clamp(0, n_mol - 1), minlength=n_mol).cpu().numpy()
             vols = np.abs(np.linalg.det(t["cell"].detach().cpu().numpy().astype(np.float64).reshape(-1, 3, 3)))
             vols = np.broadcast_to(vols, (n_mol,)) if vols.shape[0] == 1 else vols
             if vols.shape[0] != n_mol:
                 raise ValueError("HipEngine.hvp: cell must be [3, 3] or [n_mol, 3, 3]")
-            eta = (vols * vols / np.maximum(counts, 1)) ** (1.0 / 6.0) / math.sqrt(2.0 * math.pi)
-            lr_rc = float(np.max(math.sqrt(-2.0 * math.log(float(ewald_accuracy))) * eta)) * (1.0 + 1e-5)
+            lr_rc = capacity.ewald_list_cutoff(vols, counts, float(ewald_accuracy))
         rq = capacity.Request("hvp", n, n_mol, cell is not None, method, lr_rc, float(dsf_alpha), float(ewald_accuracy), dftd3)
         hv = torch.empty_like(vectors)
         f_out = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_forces else None
+
+        def call(opt, k0, kc, *tail):
+            return self.lib.aimnet_engine_hvp(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
+                                              hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None, *tail)
+        kmax = self.HVP_MAX_DIRECTIONS // (4 if dftd3 is not None else 1)  # grid.y limit of the tangent kernels
+        self._tangent_sweeps("hvp", self.lib.aimnet_engine_hvp_workspace_bytes, rq, K, kmax, call)
+        return {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}
+
+    def _tangent_sweeps(self, name: str, ws_bytes_fn, rq: capacity.Request, K: int, kmax: int, call) -> None:
+        """The K directions of `hvp` / `charge_response` (`name`) in sweeps of at most `kmax`, and of as many as HVP_BYTES_BUDGET
+        holds at `ws_bytes_fn`'s bytes per direction.  `call(opt, k0, kc, status, workspace, workspace_bytes, stream)` makes the C
+        call for the directions [k0, k0 + kc); a sweep whose status words report an overflow is repeated at the grown capacities."""
+        import torch
+
+        n, n_mol, dev = rq.n, rq.n_mol, self.device
         status = torch.empty(8, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ws_bytes = self.lib.aimnet_engine_hvp_workspace_bytes
+        ws_bytes = lambda k, opt: int(ws_bytes_fn(self._h, n, n_mol, k, C.byref(opt)))  # noqa: E731
         k0 = 0
         while k0 < K:
             opt = self.fill_options(rq)
-            per_dir = int(ws_bytes(self._h, n, n_mol, 2, C.byref(opt))) - int(ws_bytes(self._h, n, n_mol, 1, C.byref(opt)))
-            kmax = self.HVP_MAX_DIRECTIONS // (4 if dftd3 is not None else 1)  # grid.y limit of the tangent kernels
+            per_dir = ws_bytes(2, opt) - ws_bytes(1, opt)
             kc = max(1, min(K - k0, kmax, self.HVP_BYTES_BUDGET // max(1, per_dir)))
-            ws = torch.empty(int(ws_bytes(self._h, n, n_mol, kc, C.byref(opt))) + 4096, dtype=torch.uint8, device=dev)
+            ws = torch.empty(ws_bytes(kc, opt) + 4096, dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                rc = self.lib.aimnet_engine_hvp(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
-                                                hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None,
-                                                status.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-            _lib.check(rc, "aimnet_engine_hvp")
+                rc = call(opt, k0, kc, status.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+            _lib.check(rc, "aimnet_engine_" + name)
             self.last_status = st = status.cpu().numpy()
             del ws
             if st[6]:
-                raise ValueError("HipEngine.hvp: invalid input: " + describe_input_flags(int(st[6]), n_mol))
+                raise ValueError(f"HipEngine.{name}: invalid input: " + describe_input_flags(int(st[6]), n_mol))
             if not self.grow(st, opt, rq):  # (an overflow: the capacities have grown - repeat this sweep)
                 k0 += kc
-        return {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}
 
     def charge_response(self, coord, numbers, mol_idx, charge, vectors, cell=None, pbc=(True, True, True),
                         want_dipole: bool | None = None) -> dict[str, Any]:
@@ -607,7 +616,7 @@ class HipEngine(capacity.Capacities):
             want_dipole = cell is None
         if want_dipole and cell is not None:
             raise ValueError("HipEngine.charge_response: the dipole moment of a periodic cell is not defined (want_dipole=True with a cell)")
-        inp, t = self._inputs("hvp", coord, numbers, mol_idx, charge, cell, pbc)
+        inp, t = self._inputs("charge_response", coord, numbers, mol_idx, charge, cell, pbc)
         n, n_mol, dev = inp.n_atoms, inp.n_mol, self.device
         K = int(vectors.numel()) // (3 * n)
         if K == 0:
@@ -619,27 +628,12 @@ class HipEngine(capacity.Capacities):
             res["dspin"] = torch.empty(K, n, dtype=torch.float32, device=dev)
         if want_dipole:
             res["dmu"] = torch.empty(K, n_mol, 3, dtype=torch.float32, device=dev)
-        status = torch.empty(8, dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws_bytes = self.lib.aimnet_engine_charge_response_workspace_bytes
-        k0 = 0
-        while k0 < K:
-            opt = self.fill_options(rq)
-            per_dir = int(ws_bytes(self._h, n, n_mol, 2, C.byref(opt))) - int(ws_bytes(self._h, n, n_mol, 1, C.byref(opt)))
-            kc = max(1, min(K - k0, self.HVP_MAX_DIRECTIONS, self.HVP_BYTES_BUDGET // max(1, per_dir)))
-            ws = torch.empty(int(ws_bytes(self._h, n, n_mol, kc, C.byref(opt))) + 4096, dtype=torch.uint8, device=dev)
+
+        def call(opt, k0, kc, *tail):
             part = {k: v[k0 : k0 + kc].data_ptr() for k, v in res.items() if k != "charges"}
-            with torch.cuda.device(dev):
-                rc = self.lib.aimnet_engine_charge_response(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
-                                                            res["charges"].data_ptr(), part["dq"], part.get("dspin"), part.get("dmu"),
-                                                            status.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-            _lib.check(rc, "aimnet_engine_charge_response")
-            self.last_status = st = status.cpu().numpy()
-            del ws
-            if st[6]:
-                raise ValueError("HipEngine.charge_response: invalid input: " + describe_input_flags(int(st[6]), n_mol))
-            if not self.grow(st, opt, rq):  # (an overflow: the rows have grown - repeat this sweep)
-                k0 += kc
+            return self.lib.aimnet_engine_charge_response(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
+                                                          res["charges"].data_ptr(), part["dq"], part.get("dspin"), part.get("dmu"), *tail)
+        self._tangent_sweeps("charge_response", self.lib.aimnet_engine_charge_response_workspace_bytes, rq, K, self.HVP_MAX_DIRECTIONS, call)
         return res
 
     def set_profiling(self, level: int, every: int = 1) -> None:

@@ -123,3 +123,17 @@ def test_deferred_growth_has_no_request():
     assert c.max_nb == 176 and c._max_nb_lr == {15.0: 4256, 12.0: 3104} and c._ewald_max_k == 11256 and c._pme_max_mesh == 8192
     assert not c.grow_deferred(np.stack([st(), st(s7=9000)]), False)
     assert c.grow_deferred(np.stack([st(s7=9000)]), True) and c._pme_max_mesh == 10189  # status[7] counts mesh points: 9000 * 9 // 8 + 64
+
+
+def test_ewald_list_cutoff():
+    from oracle import aimnet2_oracle as O
+
+    # 10 atoms in a (10 A)^3 cell at 1e-6: the 14.287 A of tests/test_host_driver.py (test_hvp_ewald_list_capacity_only_grows)
+    assert abs(cap.ewald_list_cutoff([1000.0], [10], 1e-6) - 14.287) < 1e-3
+    for n, vol, acc in ((10, 1000.0, 1e-6), (96, 1234.5, 1e-4), (1, 27.0, 0.5)):
+        want = O.ewald_parameters(n, vol, acc)[1] * (1.0 + 1e-5)  # f eta, widened
+        assert abs(cap.ewald_list_cutoff(np.array([vol]), np.array([n]), acc) - want) <= 1e-12 * want
+    # a batch: the larger of its systems' cutoffs (the list is built at one cutoff)
+    one, two = cap.ewald_list_cutoff([1000.0], [10], 1e-6), cap.ewald_list_cutoff([8000.0], [10], 1e-6)
+    assert two > one and cap.ewald_list_cutoff([1000.0, 8000.0], [10, 10], 1e-6) == two
+    assert cap.ewald_list_cutoff([8000.0, 1000.0], [10, 10], 1e-6) == two

@@ -56,6 +56,13 @@ class ScriptedLib:
         self._answer(opt, status, k=int(k))
         return 0
 
+    def aimnet_engine_charge_response_workspace_bytes(self, h, n, n_mol, k, opt):
+        return 500 + 50 * k  # 50 B per direction
+
+    def aimnet_engine_charge_response(self, h, inp, opt, vectors, k, charges, dq, dspin, dmu, status, ws, ws_bytes, stream):
+        self._answer(opt, status, k=int(k), dspin=dspin is not None, dmu=dmu is not None)
+        return 0
+
     def sent(self, field):
         return [c[field] for c in self.calls]
 
@@ -278,3 +285,33 @@ def test_hvp_ewald_list_capacity_only_grows():
     eng.has_dftd3 = True
     eng.hvp(**system(periodic=True), vectors=torch.ones(1, 10, 3), coulomb="dsf", dsf_rc=12.0, dftd3=D3)
     assert lib.sent("max_nb_lr")[3:] == [1456] and lib.sent("max_nb_d3")[3:] == [2832] and eng._max_nb_lr == {12.0: 1456, 15.0: 2832}
+
+
+def test_charge_response_repeats_an_overflowed_sweep():
+    lib = ScriptedLib([(st(), True), (st(130, s2=1), True)])
+    eng = make_engine(lib)
+    eng.HVP_BYTES_BUDGET = 100  # two directions of 50 B per sweep
+    s = system()
+    res = eng.charge_response(**s, vectors=torch.ones(5, 10, 3))
+    assert lib.sent("k") == [2, 2, 2, 1] and lib.sent("max_nb") == [112, 112, 176, 176]  # round16(112 * 1.5)
+    assert lib.sent("max_nb_lr") == [0] * 4 and lib.sent("coulomb") == [_lib.COULOMB_NONE] * 4  # the short-range rows are all it needs
+    assert lib.sent("dspin") == [False] * 4 and lib.sent("dmu") == [True] * 4  # one channel; no cell: the dipole by default
+    assert set(res) == {"charges", "dq", "dmu"} and res["dq"].shape == (5, 10) and res["dmu"].shape == (5, 1, 3)
+    assert eng.max_nb == 176 and list(eng.last_status) == st()  # no shrink, as hvp
+    lib.script = [(st(s6=4), True)]
+    with pytest.raises(ValueError, match="HipEngine.charge_response: invalid input: mol_idx is not sorted"):
+        eng.charge_response(**s, vectors=torch.ones(1, 10, 3))
+    # the entry's own name in the messages of the input checks
+    with pytest.raises(ValueError, match=r"HipEngine.charge_response: a 2-channel \(NSE\) model needs charge of shape"):
+        make_engine(ScriptedLib(), nq=2).charge_response(**s, vectors=torch.ones(1, 10, 3))
+    with pytest.raises(ValueError, match="HipEngine.charge_response: empty input"):
+        eng.charge_response(**system(n=0), vectors=torch.ones(0, 0, 3))
+
+
+def test_a_budget_of_one_byte_gives_one_call_per_direction():
+    for method in ("hvp", "charge_response"):
+        lib = ScriptedLib()
+        eng = make_engine(lib)
+        eng.HVP_BYTES_BUDGET = 1  # less than one direction's bytes (100 B, 50 B): a sweep is never empty
+        getattr(eng, method)(**system(), vectors=torch.ones(3, 10, 3))
+        assert lib.sent("k") == [1, 1, 1], method
