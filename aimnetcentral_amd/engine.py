@@ -281,8 +281,8 @@ class HipEngine(capacity.Capacities):
         if cell is not None:
             t["cell"] = cell = cell.to(device=dev, dtype=torch.float32).contiguous()
             inp.cell, inp.n_cell = cell.data_ptr(), 1 if cell.ndim == 2 else cell.shape[0]
-        # pbc: three flags, or (eval) per-system flags [n_cell, 3] (tensor / array): normalize_pbc, neighbors.py:309-321
-        if who == "eval" and cell is not None and not isinstance(pbc, (tuple, list)) and getattr(pbc, "ndim", 1) == 2:
+        # pbc: three flags, or per-system flags [n_cell, 3] (tensor / array): normalize_pbc, neighbors.py:309-321
+        if cell is not None and not isinstance(pbc, (tuple, list)) and getattr(pbc, "ndim", 1) == 2:
             t["pbc_sys"] = pbc_sys = torch.as_tensor(pbc).to(device=dev, dtype=torch.int32).contiguous()
             if tuple(pbc_sys.shape) != (inp.n_cell, 3):
                 raise ValueError(f"pbc must have shape (3,) or ({inp.n_cell}, 3), got {tuple(pbc_sys.shape)}")
@@ -527,9 +527,9 @@ class HipEngine(capacity.Capacities):
             dsf_rc: float = 15.0, dsf_alpha: float = 0.2, want_forces: bool = False,
             dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6) -> dict[str, Any]:
         """Analytic Hessian-vector products (csrc/hvp.hip, aimnet_engine_hvp): vectors [K, N, 3] -> hv [K, N, 3] on the device
-        (+ the forces of the same sweep with `want_forces`).  Inputs as `eval`; with `dftd3` the dispersion block is added as a
-        central difference of the D3 gradient inside the same call.  The K directions are processed in as many sweeps as the
-        workspace budget asks for.  `coulomb`: "none", "simple", "dsf" or "ewald" (the exact structure-factor sum at
+        (+ the forces of the same sweep with `want_forces`).  Inputs as `eval` (`pbc`: three flags or per-system [n_cell, 3]);
+        with `dftd3` the dispersion block is added as a central difference of the D3 gradient inside the same call.  The K
+        directions are processed in as many sweeps as the workspace budget asks for.  `coulomb`: "none", "simple", "dsf" or "ewald" (the exact structure-factor sum at
         `ewald_accuracy`, periodic cells only; `dsf_rc` / `dsf_alpha` are not read with it); "pme" raises - its tangent is not
         carried, AIMNet2Calculator takes differences of forces there."""
         import torch
