@@ -34,13 +34,35 @@ import warnings
 import weakref
 from collections.abc import Collection
 from types import MappingProxyType
-from typing import Any, ClassVar
+from typing import Any, ClassVar, NamedTuple
 
 import numpy as np
 
 from . import loader
 from ._lib import HipLibraryError
 from .engine import HipEngine, ModelSpec
+
+
+class _LongRange(NamedTuple):
+    """The long-range terms of ONE call, resolved from the calculator's state and the call's cell by
+    `AIMNet2Calculator._long_range`: every entry point takes its engine keywords from `kwargs()`."""
+    method: str | None  # None: no external Coulomb
+    dsf_rc: float
+    dsf_alpha: float
+    ewald_accuracy: float
+    dftd3: dict[str, float] | None
+    periodic: bool
+    switched: bool = False  # "simple" met a cell: DSF at the setter's defaults (15 A, alpha 0.2), for this call only
+
+    def require_cell(self) -> None:
+        if self.method in ("ewald", "pme") and not self.periodic:  # calculator.py:1063-1068
+            raise ValueError(f"Coulomb method '{self.method}' requires a periodic 'cell' in the input data. Provide a (3,3) or (B,3,3) cell "
+                             "tensor, or switch to a non-periodic method via set_lrcoulomb_method('simple' | 'dsf').")
+
+    def kwargs(self) -> dict[str, Any]:
+        """Keywords of HipEngine.eval, HipEngine.hvp and DomainDecomposedEngine.eval (the accuracy is read by the Ewald methods alone)."""
+        kw = {"coulomb": self.method or "none", "dsf_rc": self.dsf_rc, "dsf_alpha": self.dsf_alpha, "dftd3": self.dftd3}
+        return dict(kw, ewald_accuracy=self.ewald_accuracy) if self.method in ("ewald", "pme") else kw
 
 
 class AIMNet2Calculator:
@@ -157,8 +179,6 @@ class AIMNet2Calculator:
         if d3_tables is not None:
             self.engine.set_dftd3_tables(d3_tables)
         self.device = str(self.engine.device)
-        self._batch: int | None = None
-        self._max_mol_size = 0
         self._mult_ignored_checked = False
         self._species_cache: tuple[Any, Any] | None = None
         self._molidx_cache: tuple[Any, Any] | None = None
@@ -306,12 +326,32 @@ class AIMNet2Calculator:
         self._dd = DomainDecomposedEngine(self.engine, group)
         self._dd_grid = grid
 
-    def _dftd3_options(self) -> dict[str, float] | None:
+    def _long_range(self, cell) -> _LongRange:
+        """The long-range request of a call with this `cell`: a pure function of the calculator's state, which no call changes.
+        A cell under "simple" takes DSF at the defaults of `set_lrcoulomb_method` for this call; `eval` announces it (`switched`)."""
         d3 = self.external_dftd3
-        if d3 is None:
-            return None
-        return {"s6": d3.s6, "s8": d3.s8, "a1": d3.a1, "a2": d3.a2, "cutoff": d3.smoothing_off,
-                "smoothing_fraction": d3.smoothing_fraction}
+        dftd3 = None if d3 is None else {"s6": d3.s6, "s8": d3.s8, "a1": d3.a1, "a2": d3.a2, "cutoff": d3.smoothing_off,
+                                         "smoothing_fraction": d3.smoothing_fraction}
+        method, rc, alpha = self._coulomb_method, self._dsf_rc, self._dsf_alpha
+        switched = cell is not None and method == "simple"
+        if switched:
+            method, rc, alpha = "dsf", self._default_dsf_cutoff, 0.2
+        return _LongRange(method, rc, alpha, self._ewald_accuracy, dftd3, cell is not None, switched)
+
+    def _normalize_pbc(self, pbc, n_sys: int):
+        """`pbc` as the engine takes it (normalize_pbc, neighbors.py:309-321): absent -> all three directions; (3,) -> a tuple of
+        bools; (n_sys, 3) -> that tuple where the rows agree, else the per-system array as it is (the engine uploads it)."""
+        if pbc is None:
+            return (True, True, True)
+        p = pbc.detach().cpu().numpy().astype(bool)
+        if p.ndim == 2:
+            if p.shape != (n_sys, 3):
+                raise ValueError(f"pbc must have shape (3,) or ({n_sys}, 3), got {tuple(p.shape)}")
+            if (p == p[0]).all():
+                p = p[0]
+        if p.ndim == 1 and p.shape != (3,):
+            raise ValueError("pbc must have shape (3,) or (B, 3)")
+        return tuple(bool(x) for x in p) if p.ndim == 1 else pbc
 
     def set_lr_cutoff(self, cutoff: float) -> None:
         self._coulomb_cutoff = cutoff
@@ -429,19 +469,19 @@ class AIMNet2Calculator:
                 out[role] = torch.where(pm[:n].to(torch.bool), torch.full_like(out[role], n), out[role])
         return out
 
-    def _check_caller_lists(self, ext: dict[str, Any], method, cell) -> dict[str, Any]:
+    def _check_caller_lists(self, ext: dict[str, Any], lr: _LongRange) -> dict[str, Any]:
         """What the model would look up itself: the external Coulomb / DFT-D3 modules read the `_lr` matrices (nbops.resolve_suffix)
         and fail without them; periodic input needs the shifts."""
         if not ext:
             return {}
-        if method in ("ewald", "pme"):
+        if lr.method in ("ewald", "pme"):
             raise ValueError("caller-supplied neighbour matrices are not taken with the Ewald methods: the real-space sum walks the "
                              "engine's own cell grid (the reference builds its own per-call list for them too, calculator.py:1560-1603)")
-        if "nbmat_lr" not in ext and (method in ("simple", "dsf") or self._dftd3_options() is not None):
+        if "nbmat_lr" not in ext and (lr.method in ("simple", "dsf") or lr.dftd3 is not None):
             raise KeyError("nbmat_lr: with a caller-supplied 'nbmat' the external Coulomb / DFT-D3 terms need 'nbmat_lr' as well")
-        if cell is not None and ("shifts" not in ext or ("nbmat_lr" in ext and "shifts_lr" not in ext)):
+        if lr.periodic and ("shifts" not in ext or ("nbmat_lr" in ext and "shifts_lr" not in ext)):
             raise KeyError("shifts: caller-supplied neighbour matrices of a periodic system need their shifts")
-        if cell is None:
+        if not lr.periodic:
             ext = {k: v for k, v in ext.items() if not k.startswith("shifts")}
         return ext
 
@@ -521,49 +561,26 @@ class AIMNet2Calculator:
                 emb["potential_grad"] = pg
         return emb
 
-    def eval(self, data: dict[str, Any], forces=False, stress=False, hessian=False, *, validate_species: bool = True,
-             host_out: bool = False, defer_status: bool = False) -> dict[str, Any]:
-        """calculator.py:879-947.  `host_out=True` (not in the reference) returns CPU tensors that arrived with the engine's one
-        status copy - for host-side drivers such as the ASE adapter that would otherwise pay one D2H round trip per output.
-        `defer_status=True` (device-resident drivers): no host read at all in this call - the evaluation is only enqueued, its
-        neighbour-overflow status is queued on the engine and verified by `check_status()` every K steps."""
+    def _flatten(self, data: dict[str, Any], d: dict[str, Any]) -> tuple:
+        """The engine's flat layout of the input tensors `d` (mol_flatten, calculator.py:1475-1511) as (coord, numbers, mol_idx)
+        and what `_unflatten` needs: B of a dense (B, N, 3) batch and, where that had padding atoms, the flat mask of the real ones."""
         import torch
 
-        if validate_species:
-            self._validate_species_and_charge(data)
-        self._maybe_warn_mult_ignored(data)
-        embedded = self._has_embedding(data)
-        if embedded and (hessian or stress or self._dd is not None):
-            raise NotImplementedError("electrostatic embedding (ext_coord / ext_charge / ext_potential) is carried by energies and "
-                                      "forces only: not with stress=True, hessian=True or domain decomposition")
-        if hessian:
-            return self._eval_hessian(data, forces=forces, stress=stress, validate_species=validate_species)
-        d = self.to_input_tensors(data)
         coord, numbers, charge = d["coord"], d["numbers"], d["charge"]
-        ext_lists = self._caller_lists(d)
-        cell = d.get("cell")
-        pbc = d.get("pbc")
-        if stress and cell is None:
-            raise AssertionError("Stress calculation requires cell")
-        # ---- layout (mol_flatten, calculator.py:1475-1511): the engine is always flat ---------------
-        pad_mask = None
-        self._batch = None
+        batch = pad_mask = None
         if coord.ndim == 3:
-            B, N = coord.shape[:2]
-            self._batch = B
-            if numbers.ndim != 2 or numbers.shape[0] != B:
+            batch, N = coord.shape[:2]
+            if numbers.ndim != 2 or numbers.shape[0] != batch:
                 raise ValueError("numbers must have shape (B, N) for 3D coord input")
-            if charge.shape[0] != B:
-                raise ValueError(f"charge must have one entry per molecule ({B}) for 3D coord input, got {charge.shape[0]}")
+            if charge.shape[0] != batch:
+                raise ValueError(f"charge must have one entry per molecule ({batch}) for 3D coord input, got {charge.shape[0]}")
             real = (numbers > 0).flatten()
-            mol_idx = torch.arange(B, device=self.device, dtype=torch.int32).repeat_interleave(N)
-            coord_f, numbers_f = coord.flatten(0, 1), numbers.flatten()
+            mol_idx = torch.arange(batch, device=self.device, dtype=torch.int32).repeat_interleave(N)
+            coord, numbers = coord.flatten(0, 1), numbers.flatten()
             if not bool(real.all()):
                 pad_mask = real
-                coord_f, numbers_f, mol_idx = coord_f[real], numbers_f[real], mol_idx[real]
-            self._max_mol_size = N
+                coord, numbers, mol_idx = coord[real], numbers[real], mol_idx[real]
         elif coord.ndim == 2:
-            coord_f, numbers_f = coord, numbers
             mol_idx = d.get("mol_idx")
             if mol_idx is None:
                 mol_idx = torch.zeros(coord.shape[0], dtype=torch.int32, device=self.device)
@@ -593,70 +610,17 @@ class AIMNet2Calculator:
                         self._molidx_cache = (key, weakref.ref(raw))
         else:
             raise ValueError(f"coord must be (N,3) or (B,N,3), got {tuple(coord.shape)}")
-        n_mol = charge.shape[0]
-        # (checked in full before the engine is touched; the keyword is passed only with embedding keys present)
-        emb = self._embedding(data, coord, pad_mask, cell, bool(forces)) if embedded else None
-        method, restore = self._coulomb_method, None
-        if cell is not None and method == "simple":
-            warnings.warn("Switching to DSF Coulomb for PBC for this evaluation; "
-                          "call set_lrcoulomb_method() to select a periodic method persistently.", stacklevel=2)
-            restore = (self._coulomb_method, self._coulomb_cutoff, self.cutoff_lr, self._dsf_alpha, self._dsf_rc)
-            self.set_lrcoulomb_method("dsf")
-            method = "dsf"
-        if method in ("ewald", "pme") and cell is None:  # calculator.py:1063-1068
-            raise ValueError(f"Coulomb method '{method}' requires a periodic 'cell' in the input data. Provide a (3,3) or (B,3,3) cell "
-                             "tensor, or switch to a non-periodic method via set_lrcoulomb_method('simple' | 'dsf').")
-        try:
-            pbc3 = (True, True, True)
-            if pbc is not None:
-                p = pbc.detach().cpu().numpy().astype(bool)
-                if p.ndim == 2:  # per-system flags (normalize_pbc, neighbors.py:309-321)
-                    n_sys = 1 if (cell is None or cell.ndim == 2) else int(cell.shape[0])
-                    if p.shape != (n_sys, 3):
-                        raise ValueError(f"pbc must have shape (3,) or ({n_sys}, 3), got {tuple(p.shape)}")
-                    if (p == p[0]).all():
-                        p = p[0]
-                if p.ndim == 1 and p.shape != (3,):
-                    raise ValueError("pbc must have shape (3,) or (B, 3)")
-                pbc3 = tuple(bool(x) for x in p) if p.ndim == 1 else pbc  # per-system flags: the engine uploads them as int32
-            if self._dd is not None:
-                if (coord.ndim != 2 or n_mol != 1 or cell is None or cell.ndim != 2 or pbc3 != (True, True, True) or ext_lists or
-                        method not in (None, "dsf") or defer_status):
-                    raise ValueError("domain decomposition (set_domain_decomposition) takes ONE fully periodic system in the flat (N, 3) "
-                                     "layout with Coulomb method 'dsf' or none, evaluated synchronously")
-                q_sys = self._engine_charge(charge, d.get("mult")).detach().cpu().numpy().reshape(-1)
-                res = self._dd.eval(coord_f, numbers_f, cell, charge=(q_sys if q_sys.size == 2 else float(q_sys[0])), forces=bool(forces),
-                                    stress=bool(stress), coulomb=method or "none", dsf_rc=self._dsf_rc, dsf_alpha=self._dsf_alpha,
-                                    dftd3=self._dftd3_options(), grid=self._dd_grid)
-                res["energy"] = res["energy"].reshape(1)
-                if host_out:  # (the ASE adapter's request: CPU tensors)
-                    res = {k: v.cpu() for k, v in res.items()}
-            else:
-                res = self.engine.eval(
-                    coord_f, numbers_f, mol_idx, self._engine_charge(charge, d.get("mult")), cell=cell, pbc=pbc3, forces=bool(forces),
-                    stress=bool(stress),
-                    coulomb=method or "none", dsf_rc=self._dsf_rc, dsf_alpha=self._dsf_alpha, ewald_accuracy=self._ewald_accuracy,
-                    dftd3=self._dftd3_options(),
-                    **({"host_out": True} if host_out else {}), **({"sync": False, "defer": True} if defer_status else {}),
-                    **({"embedding": emb} if emb is not None else {}),
-                    **self._check_caller_lists(ext_lists, method, cell))
-        finally:
-            if restore is not None:
-                (self._coulomb_method, self._coulomb_cutoff, self.cutoff_lr, self._dsf_alpha, self._dsf_rc) = restore
-        # ---- process_output: un-flatten (calculator.py:1240-1245,1513-1519) -------------------------
-        out: dict[str, Any] = {"energy": res["energy"], "charges": res["charges"]}
-        if "spin_charges" in res:
-            out["spin_charges"] = res["spin_charges"]
-        if forces:
-            out["forces"] = res["forces"]
-        if stress:
-            out["stress"] = res["stress"]
-        if emb is not None:
-            out["embedding_energy"] = res["embedding_energy"]
-            if "ext_forces" in res:
-                out["ext_forces"] = res["ext_forces"].view(self._batch, -1, 3) if self._batch is not None else res["ext_forces"]
-        if self._batch is not None:
-            B = self._batch
+        return coord, numbers, mol_idx, batch, pad_mask
+
+    def _unflatten(self, res: dict[str, Any], keys, batch, pad_mask) -> dict[str, Any]:
+        """process_output (calculator.py:1240-1245,1513-1519): the entries `keys` of the engine's result, per-atom ones back in the
+        (B, N, ...) shape of a dense batch with zeros on its padding atoms."""
+        import torch
+
+        out = {k: res[k] for k in keys}
+        if batch is not None:
+            if "ext_forces" in out:
+                out["ext_forces"] = out["ext_forces"].view(batch, -1, 3)
             for k in ("charges", "spin_charges", "forces"):
                 if k in out:
                     v = out[k]
@@ -664,8 +628,60 @@ class AIMNet2Calculator:
                         full = torch.zeros((pad_mask.shape[0],) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device)
                         full[pad_mask.to(v.device)] = v
                         v = full
-                    out[k] = v.view(B, -1, *v.shape[1:])
-        assert n_mol == out["energy"].shape[0]
+                    out[k] = v.view(batch, -1, *v.shape[1:])
+        return out
+
+    def eval(self, data: dict[str, Any], forces=False, stress=False, hessian=False, *, validate_species: bool = True,
+             host_out: bool = False, defer_status: bool = False) -> dict[str, Any]:
+        """calculator.py:879-947.  `host_out=True` (not in the reference) returns CPU tensors that arrived with the engine's one
+        status copy - for host-side drivers such as the ASE adapter that would otherwise pay one D2H round trip per output.
+        `defer_status=True` (device-resident drivers): no host read at all in this call - the evaluation is only enqueued, its
+        neighbour-overflow status is queued on the engine and verified by `check_status()` every K steps."""
+        if validate_species:
+            self._validate_species_and_charge(data)
+        self._maybe_warn_mult_ignored(data)
+        embedded = self._has_embedding(data)
+        if embedded and (hessian or stress or self._dd is not None):
+            raise NotImplementedError("electrostatic embedding (ext_coord / ext_charge / ext_potential) is carried by energies and "
+                                      "forces only: not with stress=True, hessian=True or domain decomposition")
+        if hessian:
+            return self._eval_hessian(data, forces=forces, stress=stress, validate_species=validate_species)
+        d = self.to_input_tensors(data)
+        ext_lists = self._caller_lists(d)
+        charge, cell = d["charge"], d.get("cell")
+        if stress and cell is None:
+            raise AssertionError("Stress calculation requires cell")
+        coord, numbers, mol_idx, batch, pad_mask = self._flatten(data, d)
+        # (checked in full before the engine is touched; the keyword is passed only with embedding keys present)
+        emb = self._embedding(data, d["coord"], pad_mask, cell, bool(forces)) if embedded else None
+        lr = self._long_range(cell)
+        if lr.switched:
+            warnings.warn("Switching to DSF Coulomb for PBC for this evaluation; "
+                          "call set_lrcoulomb_method() to select a periodic method persistently.", stacklevel=2)
+        lr.require_cell()
+        pbc3 = self._normalize_pbc(d.get("pbc"), 1 if (cell is None or cell.ndim == 2) else int(cell.shape[0]))
+        if self._dd is not None:
+            if (batch is not None or charge.shape[0] != 1 or cell is None or cell.ndim != 2 or pbc3 != (True, True, True) or ext_lists or
+                    lr.method not in (None, "dsf") or defer_status):
+                raise ValueError("domain decomposition (set_domain_decomposition) takes ONE fully periodic system in the flat (N, 3) "
+                                 "layout with Coulomb method 'dsf' or none, evaluated synchronously")
+            q_sys = self._engine_charge(charge, d.get("mult")).detach().cpu().numpy().reshape(-1)
+            res = self._dd.eval(coord, numbers, cell, charge=(q_sys if q_sys.size == 2 else float(q_sys[0])), forces=bool(forces),
+                                stress=bool(stress), grid=self._dd_grid, **lr.kwargs())
+            res["energy"] = res["energy"].reshape(1)
+            if host_out:  # (the ASE adapter's request: CPU tensors)
+                res = {k: v.cpu() for k, v in res.items()}
+        else:
+            res = self.engine.eval(
+                coord, numbers, mol_idx, self._engine_charge(charge, d.get("mult")), cell=cell, pbc=pbc3, forces=bool(forces),
+                stress=bool(stress), **lr.kwargs(),
+                **({"host_out": True} if host_out else {}), **({"sync": False, "defer": True} if defer_status else {}),
+                **({"embedding": emb} if emb is not None else {}),
+                **self._check_caller_lists(ext_lists, lr))
+        wanted = {"energy": True, "charges": True, "spin_charges": "spin_charges" in res, "forces": forces, "stress": stress,
+                  "embedding_energy": emb is not None, "ext_forces": emb is not None and "ext_forces" in res}
+        out = self._unflatten(res, [k for k, on in wanted.items() if on], batch, pad_mask)
+        assert charge.shape[0] == out["energy"].shape[0]
         return out
 
     def check_status(self) -> None:
@@ -711,7 +727,7 @@ class AIMNet2Calculator:
     # central-difference stencils for dF/dh: offsets k h (k = +-1 .. +-order/2), weights of +k (those of -k are the negatives)
     _FD_STENCILS = {4: (2 / 3, -1 / 12), 6: (3 / 4, -3 / 20, 1 / 60), 8: (4 / 5, -1 / 5, 4 / 105, -1 / 280)}
 
-    def _fd_hvp(self, d: dict[str, Any], dirs, step: float | None = None, order: int | None = None):
+    def _fd_hvp(self, d: dict[str, Any], dirs, lr: _LongRange, pbc3, step: float | None = None, order: int | None = None):
         """H @ v for K directions `dirs` (K,N,3) of ONE structure by central differences of the analytic forces,
             H u = -dF(x + t u)/dt ~ -(1/h) sum_k w_k [F(x + k h u) - F(x - k h u)],   u = v / max_i |v_i|,
         4th order (k = 1, 2; w = 2/3, -1/12) at h = 5e-3 A by default (FD_ORDER / FD_STEP; 6- and 8-point stencils are there);
@@ -738,12 +754,6 @@ class AIMNet2Calculator:
         scale = dirs.norm(dim=-1).amax(dim=-1)                       # (K,) largest per-atom displacement
         unit = dirs / scale.clamp_min(1e-30).view(K, 1, 1)
         out = torch.zeros_like(dirs)
-        method = self._coulomb_method
-        if cell is not None and method == "simple":
-            method = "dsf"
-        pbc3 = (True, True, True)
-        if d.get("pbc") is not None:
-            pbc3 = tuple(bool(x) for x in d["pbc"].detach().cpu().numpy().astype(bool).reshape(-1)[:3])
         offsets = torch.tensor([s * (k + 1) for k in range(len(ws)) for s in (1.0, -1.0)], device=self.device).view(1, m, 1, 1) * h
         weights = torch.tensor([-s * w for w in ws for s in (1.0, -1.0)], device=self.device).view(1, m, 1, 1) / h
         kb = max(1, self.FD_MAX_ATOMS // (m * n))
@@ -753,9 +763,7 @@ class AIMNet2Calculator:
             x = (coord.view(1, 1, n, 3) + offsets * u.view(kk, 1, n, 3)).reshape(kk * m * n, 3)
             res = self.engine.eval(
                 x, numbers.repeat(kk * m), torch.arange(kk * m, device=self.device, dtype=torch.int32).repeat_interleave(n),
-                charge.repeat(kk * m, *([1] * (charge.ndim - 1))), cell=cell, pbc=pbc3, forces=True, stress=False,
-                coulomb=method or "none",
-                dsf_rc=self._dsf_rc, dsf_alpha=self._dsf_alpha, ewald_accuracy=self._ewald_accuracy, dftd3=self._dftd3_options())
+                charge.repeat(kk * m, *([1] * (charge.ndim - 1))), cell=cell, pbc=pbc3, forces=True, stress=False, **lr.kwargs())
             f = res["forces"].view(kk, m, n, 3)
             out[k0 : k0 + kk] = (f * weights).sum(dim=1) * scale[k0 : k0 + kk].view(kk, 1, 1)
         return out
@@ -774,67 +782,56 @@ class AIMNet2Calculator:
 
         if self.hvp_method not in ("analytic", "fd"):
             raise ValueError(f"hvp_method must be 'analytic' or 'fd', got {self.hvp_method!r}")
-        if self.hvp_method == "fd" or self._coulomb_method == "pme":
+        cell = d.get("cell")
+        lr = self._long_range(cell)
+        lr.require_cell()
+        pbc3 = self._normalize_pbc(d.get("pbc"), 1)
+        if self.hvp_method == "fd" or lr.method == "pme":
             # particle-mesh Ewald: differences of the analytic forces (what the reference does for its PME block, lr.py:903-926);
             # the tangent sweep of csrc/hvp.hip carries the pair-wise Coulomb methods and the exact Ewald sum, not the mesh
-            return self._fd_hvp(d, dirs, eps)
-        cell = d.get("cell")
-        method = self._coulomb_method
-        if cell is not None and method == "simple":
-            method = "dsf"
-        pbc3 = (True, True, True)
-        if d.get("pbc") is not None:
-            pbc3 = tuple(bool(x) for x in d["pbc"].detach().cpu().numpy().astype(bool).reshape(-1)[:3])
+            return self._fd_hvp(d, dirs, lr, pbc3, eps)
         n = d["coord"].shape[0]
         res = self.engine.hvp(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
-                              self._engine_charge(d["charge"], d.get("mult")), dirs, cell=cell, pbc=pbc3, coulomb=method or "none",
-                              dsf_rc=self._dsf_rc, dsf_alpha=self._dsf_alpha, dftd3=self._dftd3_options(),
-                              **({"ewald_accuracy": self._ewald_accuracy} if method == "ewald" else {}))
+                              self._engine_charge(d["charge"], d.get("mult")), dirs, cell=cell, pbc=pbc3, **lr.kwargs())
         return res["hv"]
+
+    def _split_structures(self, data: dict[str, Any]):
+        """The structures of a batched input as single-structure dicts and whether their results stack - those of a (B, N, 3) batch
+        do (calculator.py:1414-1450), the generally ragged molecules of flat `mol_idx` input do not; (None, False) for one structure."""
+        import torch
+
+        coord = torch.as_tensor(data["coord"])
+        if coord.ndim == 3 and coord.shape[0] > 1:
+            count, stack = int(coord.shape[0]), True
+            atoms = lambda t, m: t[m]  # noqa: E731
+        elif coord.ndim == 2 and data.get("mol_idx") is not None and int(torch.as_tensor(data["mol_idx"]).max()) > 0:
+            mol = torch.as_tensor(data["mol_idx"]).to("cpu")
+            count, stack = int(mol.max()) + 1, False
+            atoms = lambda t, m: t[(mol == m).to(t.device)]  # noqa: E731
+        else:
+            return None, False
+        subs = []
+        for m in range(count):
+            sub = {}
+            for k, v in data.items():
+                if v is None or k == "mol_idx":
+                    continue
+                t = torch.as_tensor(v)
+                if k in ("coord", "numbers"):
+                    sub[k] = atoms(t, m)
+                elif k in ("charge", "mult"):
+                    sub[k] = t[m] if t.ndim >= 1 and t.shape[0] == count else t
+                elif k == "cell":
+                    sub[k] = t[m] if t.ndim == 3 else t
+                else:
+                    sub[k] = v
+            subs.append(sub)
+        return subs, stack
 
     def _eval_hessian(self, data, *, forces: bool, stress: bool, validate_species: bool) -> dict[str, Any]:
         import torch
 
-        coord_in = torch.as_tensor(data["coord"])
-        subs = None
-        if coord_in.ndim == 3 and coord_in.shape[0] > 1:  # per-structure Hessians, stacked (calculator.py:1414-1450)
-            B = int(coord_in.shape[0])
-            subs, stack = [], True
-            for b in range(B):
-                sub = {}
-                for k, v in data.items():
-                    if v is None or k == "mol_idx":
-                        continue
-                    t = torch.as_tensor(v)
-                    if k in ("coord", "numbers"):
-                        sub[k] = t[b]
-                    elif k in ("charge", "mult"):
-                        sub[k] = t[b] if t.ndim >= 1 and t.shape[0] == B else t
-                    elif k == "cell":
-                        sub[k] = t[b] if t.ndim == 3 else t
-                    else:
-                        sub[k] = v
-                subs.append(sub)
-        elif coord_in.ndim == 2 and data.get("mol_idx") is not None and int(torch.as_tensor(data["mol_idx"]).max()) > 0:
-            mol = torch.as_tensor(data["mol_idx"]).to("cpu")
-            nm = int(mol.max()) + 1
-            subs, stack = [], False  # independent, generally ragged molecules -> lists
-            for m in range(nm):
-                sel = mol == m
-                sub = {}
-                for k, v in data.items():
-                    if v is None or k == "mol_idx":
-                        continue
-                    t = torch.as_tensor(v)
-                    if k in ("coord", "numbers"):
-                        sub[k] = t[sel.to(t.device)]
-                    elif k in ("charge", "mult"):
-                        sub[k] = t[m] if t.ndim >= 1 and t.shape[0] == nm else t
-                    elif k == "cell":
-                        sub[k] = t[m] if t.ndim == 3 else t
-                    else:
-                        sub[k] = v
-                subs.append(sub)
+        subs, stack = self._split_structures(data)
         if subs is not None:
             results = [self.eval(sub, forces=forces, stress=stress, hessian=True, validate_species=validate_species) for sub in subs]
             out: dict[str, Any] = {}
@@ -855,13 +852,19 @@ class AIMNet2Calculator:
             out.pop("forces", None)
         return out
 
+    def _directions(self, vectors, n: int):
+        import torch
+
+        v = torch.as_tensor(vectors, dtype=torch.float32, device=self.device)
+        if v.shape[-2:] != (n, 3) or v.ndim not in (2, 3):
+            raise ValueError(f"vectors must have shape ({n}, 3) or (K, {n}, 3), got {tuple(v.shape)}")
+        return v
+
     def hessian_vector_product(self, data: dict[str, Any], vectors, *, eps: float | None = None,
                                validate_species: bool = True, create_graph: bool = False):
         """Matrix-free H @ v for one structure (calculator.py:1753-1989): `vectors` (N,3) or (K,N,3) -> same shape.
         Exact second derivatives from the analytic tangent sweep (csrc/hvp.hip), all directions in one sweep; `eps` is, as in the
         reference, ignored by the analytic operator - it is the step of the finite-difference one (`hvp_method = "fd"`)."""
-        import torch
-
         if create_graph:
             raise NotImplementedError("create_graph=True needs autograd through the model; the native engine has none")
         if self._has_embedding(data):
@@ -870,10 +873,8 @@ class AIMNet2Calculator:
             self._validate_species_and_charge(data)
         self._maybe_warn_mult_ignored(data)
         d = self._single_structure(data, "hessian_vector_product")
-        v = torch.as_tensor(vectors, dtype=torch.float32, device=self.device)
         n = d["coord"].shape[0]
-        if v.shape[-2:] != (n, 3) or v.ndim not in (2, 3):
-            raise ValueError(f"vectors must have shape ({n}, 3) or (K, {n}, 3), got {tuple(v.shape)}")
+        v = self._directions(vectors, n)
         hv = self._hvp(d, v.reshape(-1, n, 3), eps)
         return hv.view_as(v)
 
@@ -888,16 +889,11 @@ class AIMNet2Calculator:
             self._validate_species_and_charge(data)
         self._maybe_warn_mult_ignored(data)
         d = self._single_structure(data, "charge_response")
-        v = torch.as_tensor(vectors, dtype=torch.float32, device=self.device)
         n = d["coord"].shape[0]
-        if v.shape[-2:] != (n, 3) or v.ndim not in (2, 3):
-            raise ValueError(f"vectors must have shape ({n}, 3) or (K, {n}, 3), got {tuple(v.shape)}")
-        pbc3 = (True, True, True)
-        if d.get("pbc") is not None:
-            pbc3 = tuple(bool(x) for x in d["pbc"].detach().cpu().numpy().astype(bool).reshape(-1)[:3])
+        v = self._directions(vectors, n)
         res = self.engine.charge_response(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
                                           self._engine_charge(d["charge"], d.get("mult")), v.reshape(-1, n, 3), cell=d.get("cell"),
-                                          pbc=pbc3)
+                                          pbc=self._normalize_pbc(d.get("pbc"), 1))
         lead = v.shape[:-2]
         out = {"charges": res["charges"], "dq": res["dq"].view(*lead, n)}
         if "dspin" in res:

@@ -293,6 +293,15 @@ class HipEngine(capacity.Capacities):
         inp.coord, inp.numbers, inp.mol_idx, inp.charge = (t[k].data_ptr() for k in ("coord", "numbers", "mol_idx", "charge"))
         return inp, t
 
+    def _directions(self, who: str, vectors, n: int) -> tuple:
+        """The tangent directions of `hvp` / `charge_response` (`who`, for the message): their number K and the [K, n, 3] device array."""
+        import torch
+
+        K = int(vectors.numel()) // (3 * n)
+        if K == 0:
+            raise ValueError(f"HipEngine.{who}: empty input")
+        return K, vectors.to(device=self.device, dtype=torch.float32).reshape(-1, n, 3).contiguous()
+
     def _caller_lists(self, inp, t, lists) -> tuple:
         """Check the caller-supplied matrices `lists` = ((name, matrix, shifts), ...) of `eval`, enter them into `inp` (and `t`, which
         keeps them alive) and return their widths (0: not given)."""
@@ -536,9 +545,7 @@ class HipEngine(capacity.Capacities):
 
         inp, t = self._inputs("hvp", coord, numbers, mol_idx, charge, cell, pbc)
         n, n_mol, dev = inp.n_atoms, inp.n_mol, self.device
-        K = int(vectors.numel()) // (3 * n)
-        if K == 0:
-            raise ValueError("HipEngine.hvp: empty input")
+        K, vectors = self._directions("hvp", vectors, n)
         est = 0.75e-6 * n * K if n > 2000 else 0.0  # (small systems are launch-bound: ~0.04 force evaluations per direction)
         if est > self.HVP_MAX_SECONDS and self.HVP_ON_LONG == "raise":
             raise ValueError(f"HipEngine.hvp: {K} directions on {n} atoms would take ~{est:.0f} s (HVP_ON_LONG = 'raise')")
@@ -547,7 +554,6 @@ class HipEngine(capacity.Capacities):
             warnings.warn(f"HipEngine.hvp: {K} directions on {n} atoms will take ~{est:.0f} s (~0.75 us per atom and direction on one "
                           f"MI355X, more with DFT-D3); a Krylov / Davidson solver needs tens of directions, not 3N "
                           f"(threshold: HipEngine.HVP_MAX_SECONDS = {self.HVP_MAX_SECONDS:.0f} s)", RuntimeWarning, stacklevel=2)
-        vectors = vectors.to(device=dev, dtype=torch.float32).reshape(-1, n, 3).contiguous()
         if coulomb == "pme":
             raise ValueError("HipEngine.hvp: the analytic tangent sweep does not carry particle-mesh Ewald; use coulomb='ewald' (the exact "
                              "sum) or differences of the forces (AIMNet2Calculator does: hvp_method 'fd' is taken automatically)")
@@ -618,10 +624,7 @@ class HipEngine(capacity.Capacities):
             raise ValueError("HipEngine.charge_response: the dipole moment of a periodic cell is not defined (want_dipole=True with a cell)")
         inp, t = self._inputs("charge_response", coord, numbers, mol_idx, charge, cell, pbc)
         n, n_mol, dev = inp.n_atoms, inp.n_mol, self.device
-        K = int(vectors.numel()) // (3 * n)
-        if K == 0:
-            raise ValueError("HipEngine.charge_response: empty input")
-        vectors = vectors.to(device=dev, dtype=torch.float32).reshape(-1, n, 3).contiguous()
+        K, vectors = self._directions("charge_response", vectors, n)
         rq = capacity.Request("hvp", n, n_mol, cell is not None, _lib.COULOMB_NONE, 0.0)  # the short-range rows are all it needs
         res = {"charges": torch.empty(n, dtype=torch.float32, device=dev), "dq": torch.empty(K, n, dtype=torch.float32, device=dev)}
         if self.nq == 2:

@@ -97,6 +97,30 @@ def test_pbc_auto_switch_and_explicit_dsf(calc):
         calc.set_lrcoulomb_method("simple")
 
 
+def test_hvp_of_a_cell_under_simple_takes_the_default_dsf_like_eval(calc):
+    """A cell under "simple" is evaluated with DSF at the setter's defaults (15 A, alpha 0.2) by every entry point: after
+    set_lrcoulomb_method("dsf", 8.0, 0.25) and back to "simple", hessian_vector_product equals HipEngine.hvp called directly with
+    15.0 / 0.2 on the same tensors bit for bit (the sweep is bitwise reproducible), and not the sweep at the left-over 8.0 / 0.25."""
+    g = golden("pbc96_dsf15")
+    data = {"coord": g["coord"], "numbers": g["numbers"], "charge": 0.0, "cell": g["cell"]}
+    v = torch.randn(2, 96, 3, generator=torch.Generator().manual_seed(7))
+    v = (v / v.flatten(1).norm(dim=1).view(2, 1, 1)).to(calc.device)
+    t = calc.to_input_tensors(data)
+    args = (t["coord"], t["numbers"], torch.zeros(96, dtype=torch.int32, device=calc.device), t["charge"], v)
+    calc.set_lrcoulomb_method("dsf", cutoff=8.0, dsf_alpha=0.25)
+    calc.set_lrcoulomb_method("simple")
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")  # only `eval` announces the switch
+            hv = calc.hessian_vector_product(data, v)
+    finally:
+        calc.set_lrcoulomb_method("simple")
+    want = calc.engine.hvp(*args, cell=t["cell"], coulomb="dsf", dsf_rc=15.0, dsf_alpha=0.2)["hv"]
+    stale = calc.engine.hvp(*args, cell=t["cell"], coulomb="dsf", dsf_rc=8.0, dsf_alpha=0.25)["hv"]
+    assert hv.shape == (2, 96, 3) and torch.equal(hv, want)
+    assert (hv - stale).abs().max().item() > 0.0  # the two surfaces differ: the comparison above can see a stale parameter
+
+
 def test_batched_cells(calc):
     g = golden("pbc2x96_dsf9")
     calc.set_lrcoulomb_method("dsf", cutoff=9.0)

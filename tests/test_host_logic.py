@@ -11,57 +11,16 @@ import torch
 
 from aimnetcentral_amd import calculator as calc_mod
 from aimnetcentral_amd import loader, workloads
+from fake_engine import WATER, FakeEngine, _as_tensor_cpu, fake_calculator
 
 import pathlib
 
 GOLDEN = pathlib.Path(__file__).parent / "golden"
 
 
-class FakeEngine:
-    """Records eval() calls and returns recognisable tensors; stands in for HipEngine."""
-
-    def __init__(self, spec, device):
-        self.spec, self.device, self.calls, self.d3_tables = spec, torch.device("cpu"), [], None
-        self.nq = int(getattr(spec, "num_charge_channels", 1))
-
-    def set_dftd3_tables(self, tables):
-        self.d3_tables = tables
-
-    def eval(self, coord, numbers, mol_idx, charge, cell=None, pbc=(True, True, True), forces=False, stress=False,
-             coulomb="simple", dsf_rc=15.0, dsf_alpha=0.2, ewald_accuracy=1e-6, sync=True, dftd3=None, host_out=False, **lists):
-        self.calls.append(dict(lists=lists, host_out=host_out, n=coord.shape[0], n_mol=charge.shape[0], coulomb=coulomb, dsf_rc=dsf_rc, dsf_alpha=dsf_alpha, dftd3=dftd3,
-                               ewald_accuracy=ewald_accuracy,
-                               pbc=pbc, cell=None if cell is None else tuple(cell.shape), mol_idx=mol_idx.clone(),
-                               numbers=numbers.clone(), charge=charge.clone()))
-        n = coord.shape[0]
-        out = {"energy": torch.arange(charge.shape[0], dtype=torch.float64), "charges": torch.arange(n, dtype=torch.float32) + 1}
-        if self.nq == 2:
-            assert charge.ndim == 2 and charge.shape[1] == 2
-            out["spin_charges"] = -(torch.arange(n, dtype=torch.float32) + 1)
-        if forces:
-            out["forces"] = torch.ones(n, 3) * (torch.arange(n, dtype=torch.float32) + 1).unsqueeze(-1)
-        if stress:
-            out["stress"] = torch.zeros(3, 3) if cell is not None and cell.ndim == 2 else torch.zeros(charge.shape[0], 3, 3)
-        return out
-
-
 @pytest.fixture()
 def calc(monkeypatch):
-    monkeypatch.setattr(calc_mod, "HipEngine", FakeEngine)
-    monkeypatch.setattr(torch, "as_tensor", _as_tensor_cpu(torch.as_tensor))
-    c = calc_mod.AIMNet2Calculator(loader.synthetic_spec(0), device="cuda")
-    c.device = "cpu"
-    return c
-
-
-def _as_tensor_cpu(orig):
-    def f(data, dtype=None, device=None):
-        return orig(data, dtype=dtype, device="cpu")
-
-    return f
-
-
-WATER = dict(coord=[[0.0, 0.0, 0.1173], [0.0, 0.7572, -0.4692], [0.0, -0.7572, -0.4692]], numbers=[8, 1, 1], charge=0.0)
+    return fake_calculator(monkeypatch)
 
 
 def test_cpu_device_is_refused():
@@ -317,10 +276,7 @@ class QuadraticEngine(FakeEngine):
 
 @pytest.fixture()
 def qcalc(monkeypatch):
-    monkeypatch.setattr(calc_mod, "HipEngine", QuadraticEngine)
-    monkeypatch.setattr(torch, "as_tensor", _as_tensor_cpu(torch.as_tensor))
-    c = calc_mod.AIMNet2Calculator(loader.synthetic_spec(0), device="cuda")
-    c.device = "cpu"
+    c = fake_calculator(monkeypatch, QuadraticEngine)
     g = torch.Generator().manual_seed(3)
     a = torch.randn(9, 9, generator=g, dtype=torch.float64)
     QuadraticEngine.A = a + a.T
@@ -422,11 +378,7 @@ def test_torchsim_adapter_maps_a_flat_multi_system_state(calc):
 # ---- open-shell NSE models: mult -> (alpha, beta) charges, spin_charges output (calculator.py:418-451,473-476) ------------------
 @pytest.fixture()
 def nse_calc(monkeypatch):
-    monkeypatch.setattr(calc_mod, "HipEngine", FakeEngine)
-    monkeypatch.setattr(torch, "as_tensor", _as_tensor_cpu(torch.as_tensor))
-    c = calc_mod.AIMNet2Calculator(loader.synthetic_spec(0, num_charge_channels=2), device="cuda")
-    c.device = "cpu"
-    return c
+    return fake_calculator(monkeypatch, spec=loader.synthetic_spec(0, num_charge_channels=2))
 
 
 def test_nse_calculator_channels_and_outputs(nse_calc, calc):
@@ -456,10 +408,7 @@ def test_nse_calculator_channels_and_outputs(nse_calc, calc):
 
 
 def test_nse_fd_hessian_carries_both_channels(monkeypatch):
-    monkeypatch.setattr(calc_mod, "HipEngine", QuadraticEngine)
-    monkeypatch.setattr(torch, "as_tensor", _as_tensor_cpu(torch.as_tensor))
-    c = calc_mod.AIMNet2Calculator(loader.synthetic_spec(0, num_charge_channels=2), device="cuda")
-    c.device = "cpu"
+    c = fake_calculator(monkeypatch, QuadraticEngine, loader.synthetic_spec(0, num_charge_channels=2))
     a = torch.randn(9, 9, generator=torch.Generator().manual_seed(3), dtype=torch.float64)
     QuadraticEngine.A = a + a.T
     out = c(dict(WATER, mult=3.0), hessian=True)  # analytic sweep: one molecule, both channels

@@ -9,9 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from aimnetcentral_amd import calculator as calc_mod
-from aimnetcentral_amd import loader
-from test_host_logic import FakeEngine, _as_tensor_cpu
+from fake_engine import FakeEngine, fake_calculator
 
 
 class RecordingHvpEngine(FakeEngine):
@@ -23,11 +21,7 @@ class RecordingHvpEngine(FakeEngine):
 
 @pytest.fixture()
 def calc(monkeypatch):
-    monkeypatch.setattr(calc_mod, "HipEngine", RecordingHvpEngine)
-    monkeypatch.setattr(torch, "as_tensor", _as_tensor_cpu(torch.as_tensor))
-    c = calc_mod.AIMNet2Calculator(loader.synthetic_spec(0), device="cuda")
-    c.device = "cpu"
-    return c
+    return fake_calculator(monkeypatch, RecordingHvpEngine)
 
 
 CELL = dict(coord=[[0.0, 0.0, 0.1173], [0.0, 0.7572, -0.4692], [0.0, -0.7572, -0.4692]], numbers=[8, 1, 1], charge=0.0,
