@@ -46,6 +46,11 @@ EXPORTED_SYMBOLS = (
     "aimnet_debug_gemm_h2",
     "aimnet_engine_debug_mlp_sweep",
     "aimnet_debug_pme_recip",
+    "aimnet_debug_conv_fwd",
+    "aimnet_debug_unconcat",
+    "aimnet_debug_conv_bwd",
+    "aimnet_debug_conv_bwd_p0",
+    "aimnet_debug_pair_force",
     "aimnet_engine_set_option",
     "aimnet_engine_get_option",
     "aimnet_engine_set_dftd3",
@@ -266,6 +271,20 @@ def load() -> C.CDLL:
                                                   C.POINTER(vp), C.POINTER(C.c_int), vp]
     lib.aimnet_debug_pme_recip.restype = C.c_int
     lib.aimnet_debug_pme_recip.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_double), vp]
+    # the conv kernels one launch at a time (tests/test_gpu_conv_kernels.py); `shifts` is a host pointer
+    ci, cf = C.c_int, C.c_float
+    lib.aimnet_debug_conv_fwd.restype = C.c_int
+    lib.aimnet_debug_conv_fwd.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, cf, cf, C.POINTER(cf), vp, ci, vp, vp, ci, vp, ci, ci, ci, vp]
+    lib.aimnet_debug_unconcat.restype = C.c_int
+    lib.aimnet_debug_unconcat.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp]
+    lib.aimnet_debug_conv_bwd.restype = C.c_int
+    lib.aimnet_debug_conv_bwd.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, cf, C.POINTER(cf), vp, ci, vp, vp, vp, vp, vp, vp,
+                                          ci, vp, vp, ci, ci, vp]
+    lib.aimnet_debug_conv_bwd_p0.restype = C.c_int
+    lib.aimnet_debug_conv_bwd_p0.argtypes = [ci, vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, cf, cf, C.POINTER(cf), vp, vp, vp, ci,
+                                             vp, vp, vp]
+    lib.aimnet_debug_pair_force.restype = C.c_int
+    lib.aimnet_debug_pair_force.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp]
     lib.aimnet_neighbor_list_workspace_bytes.restype = sz
     lib.aimnet_neighbor_list_workspace_bytes.argtypes = [i32, i32, i32]
     lib.aimnet_neighbor_list.restype = C.c_int

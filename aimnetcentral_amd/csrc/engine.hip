@@ -1539,6 +1539,80 @@ done:
   return rc;
 }
 
+// ---- the engine's conv kernels, one launch at a time on caller-made buffers (tests/test_gpu_conv_kernels.py) ----------------
+// row stride of x / xbar: the 704 (+ 29 per charge channel) columns in use, a multiple of 32, and at most the 64 pad columns the
+// forward kernel zeroes
+static bool debug_conv_ldx_ok(int nq, int ldx) { return ldx % 32 == 0 && ldx >= 704 + 29 * nq && ldx <= 768; }
+static bool debug_conv_basis(float rc, float eta, const float* shifts, aimnet::BasisParams* bp) {
+  if (!shifts || !(rc > 0.f) || !(eta > 0.f)) return false;
+  bp->rc = rc;
+  bp->eta = eta;
+  for (int g = 0; g < 16; ++g) bp->shifts[g] = shifts[g];
+  return true;
+}
+
+int aimnet_debug_conv_fwd(int nq, const float* a, const int32_t* row_of, const float* q, const int32_t* nb_idx,
+                          const int32_t* nb_cnt, const float* pg, int cap, const float* agh_a, const float* agh_q, float rc,
+                          float eta, const float* shifts, void* x, int ldx, float* Vsave, float* Vqsave, int n_atoms,
+                          const int32_t* order, int species_moments, int split_max, int x_split, void* hip_stream) {
+  aimnet::BasisParams bp;
+  if (nq < 0 || nq > 2 || !a || !nb_idx || !nb_cnt || !pg || cap <= 0 || !agh_a || !x || !Vsave || n_atoms <= 0 || x_split < 0 ||
+      x_split > 2 || !debug_conv_ldx_ok(nq, ldx) || !debug_conv_basis(rc, eta, shifts, &bp))
+    return AIMNET_E_INVALID;
+  if (nq > 0 && (!q || !agh_q || !Vqsave)) return AIMNET_E_INVALID;
+  if (species_moments && (!row_of || nq != 0)) return AIMNET_E_INVALID;
+  return launch_conv_fwd((hipStream_t)hip_stream, nq, a, row_of, q, nb_idx, nb_cnt, reinterpret_cast<const float4*>(pg), cap, agh_a,
+                         agh_q, bp, reinterpret_cast<float*>(x), ldx, Vsave, Vqsave, n_atoms, order, species_moments != 0, split_max,
+                         x_split);
+}
+
+int aimnet_debug_unconcat(int nq, const float* xbar, int ldx, const float* Vsave, const float* Vqsave, const float* agh_a,
+                          const float* agh_q, float* Sbar, float* Sqbar, int n_atoms, void* hip_stream) {
+  if (nq < 0 || nq > 2 || !xbar || !Vsave || !agh_a || !Sbar || n_atoms <= 0 || !debug_conv_ldx_ok(nq, ldx)) return AIMNET_E_INVALID;
+  if (nq > 0 && (!Vqsave || !agh_q || !Sqbar)) return AIMNET_E_INVALID;
+  return launch_unconcat((hipStream_t)hip_stream, nq, xbar, ldx, Vsave, Vqsave, agh_a, agh_q, Sbar, Sqbar, n_atoms);
+}
+
+int aimnet_debug_conv_bwd(int nq, int need_abar, int stress, const float* a, const int32_t* row_of, const float* q, const float* Sbar,
+                          const float* Sqbar, const int32_t* nb_idx, const int32_t* nb_cnt, const float* pg, int cap, float rc,
+                          float eta, const float* shifts, const float* xbar, int ldx, const float* abar_in, float* abar_out,
+                          const float* qbar_in, float* qbar_out, float* fgrad, float* virial_atom, int n_atoms, const int32_t* order,
+                          float* pairbuf, int pb_accum, int split_max, void* hip_stream) {
+  aimnet::BasisParams bp;
+  if (nq < 0 || nq > 2 || !a || !Sbar || !nb_idx || !nb_cnt || !pg || cap <= 0 || !xbar || !fgrad || n_atoms <= 0 ||
+      !debug_conv_ldx_ok(nq, ldx) || !debug_conv_basis(rc, eta, shifts, &bp))
+    return AIMNET_E_INVALID;
+  if (nq > 0 && (!q || !Sqbar || !qbar_in || !qbar_out)) return AIMNET_E_INVALID;
+  if ((need_abar && !abar_out) || (stress && !virial_atom)) return AIMNET_E_INVALID;
+  return launch_conv_bwd((hipStream_t)hip_stream, nq, need_abar != 0, stress != 0, a, row_of, q, Sbar, Sqbar, nb_idx, nb_cnt,
+                         reinterpret_cast<const float4*>(pg), cap, bp, xbar, ldx, abar_in, abar_out, qbar_in, qbar_out, fgrad,
+                         virial_atom, n_atoms, order, reinterpret_cast<float4*>(pairbuf), pb_accum != 0, split_max);
+}
+
+int aimnet_debug_conv_bwd_p0(int stress, const float* xbar, int ldx, const float* Vsave, const float* agh_a, const float* afv,
+                             const int32_t* z_of_slot, int nslots, const unsigned long long* present_part, int n_part,
+                             const int32_t* aslot, const int32_t* nb_idx, const int32_t* nb_cnt, const float* pg, int cap, float rc,
+                             float eta, const float* shifts, float* T, float* fgrad, float* virial_atom, int n_atoms,
+                             const int32_t* order, float* pairbuf, void* hip_stream) {
+  aimnet::BasisParams bp;
+  if (!xbar || !Vsave || !agh_a || !afv || !z_of_slot || nslots <= 0 || nslots > 64 || !present_part || n_part <= 0 || !aslot ||
+      !nb_idx || !nb_cnt || !pg || cap <= 0 || !T || !fgrad || n_atoms <= 0 || (stress && !virial_atom) ||
+      !debug_conv_ldx_ok(0, ldx) || !debug_conv_basis(rc, eta, shifts, &bp))
+    return AIMNET_E_INVALID;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int rc0 = launch_unconcat_p0(s, xbar, ldx, Vsave, agh_a, afv, z_of_slot, nslots, present_part, n_part, T, n_atoms);
+  if (rc0) return rc0;
+  return launch_conv_bwd_p0(s, stress != 0, T, nslots, aslot, nb_idx, nb_cnt, reinterpret_cast<const float4*>(pg), cap, bp, fgrad,
+                            virial_atom, n_atoms, order, reinterpret_cast<float4*>(pairbuf));
+}
+
+int aimnet_debug_pair_force(const int32_t* nb_idx, const int32_t* nb_cnt, const int32_t* rev, const float* pairbuf, int cap,
+                            int n_atoms, const float* fgrad, float* forces, void* hip_stream) {
+  if (!nb_idx || !nb_cnt || !rev || !pairbuf || cap <= 0 || n_atoms <= 0 || !fgrad || !forces) return AIMNET_E_INVALID;
+  return launch_pair_force((hipStream_t)hip_stream, nb_idx, nb_cnt, rev, reinterpret_cast<const float4*>(pairbuf), cap, n_atoms,
+                           fgrad, forces, nullptr);
+}
+
 int aimnet_conv_sv_2d_sp_fwd(const float* a, const int32_t* idx, const float* g, float* out, int32_t B, int32_t A,
                              int32_t G, int32_t M, void* hip_stream) {
   if (!a || !idx || !g || !out || B < 0 || A <= 0 || G <= 0 || M <= 0) return AIMNET_E_INVALID;

@@ -457,7 +457,45 @@ int aimnet_debug_pme_recip(const float* xw, const float* q, const int* order, co
                            int max_mesh, double* e_atom, float* qbar, float* fgrad, float* virial_atom, double* host_info,
                            void* hip_stream);
 
-/* Stand-alone neighbour list with the nvalchemiops contract.  nbmat [n_atoms, max_nb] int32 is
+/* Test hooks for the conv kernels that every evaluation runs (csrc/conv.hip): ONE launch each, on the given stream, on caller-allocated
+ * device buffers in the layouts csrc/kernels.h documents; nothing is allocated, copied or synchronised.  Common arguments: nq = charge
+ * channels (0, 1, 2); nb_idx [n][cap] / nb_cnt [n] / pg [n][cap][4] = (ux, uy, uz, d) per entry: a full, symmetric neighbour matrix;
+ * basis rc, eta and 16 shifts (HOST pointer); ldx = floats per row of x / xbar, a multiple of 32 with 704 + 29 nq <= ldx <= 768;
+ * order = processing order of the atoms (a permutation) or NULL; split_max = atoms up to which the four-waves-per-atom kernels run.
+ * aimnet_debug_conv_fwd: a [n][256], or the embedding table [64][256] with row_of = atomic numbers [n] (pass 0; species_moments != 0
+ *   then takes the element-moment kernel where the launcher allows it); q [nq][n]; agh_a [16][16][12], agh_q [nq][16][12]; writes the MLP
+ *   input row x [n][ldx] = [a | S_s | |V|^2 | q | S^q_s | |V^q|^2 | 0...] (x_split 1: bf3 form, 3 ldx bf16 per row; 2: h2 activation
+ *   form, 2 ldx fp16 per row), Vsave [n][3][192] and Vqsave [n][nq][12][3].
+ * aimnet_debug_unconcat: xbar [n][ldx], Vsave, Vqsave -> Sbar [n][4][64][4] (planes 1..3; plane 0 is not written), Sqbar [n][nq][64].
+ * aimnet_debug_conv_bwd: abar_out [n][256] = abar_in (or 0 when NULL) + xbar[:, :256] + conv term (need_abar != 0 only); qbar_out
+ *   [nq][n] = qbar_in + xbar q columns + conv term; fgrad [n][3] and virial_atom [n][9] are ACCUMULATED onto.  pairbuf [n][cap][4] !=
+ *   NULL above split_max: the reverse-pair form - fgrad untouched, F1 of every ordered pair written (pb_accum != 0: added) to pairbuf.
+ * aimnet_debug_conv_bwd_p0: the species-moment backward of pass 0, two launches: xbar, Vsave -> T [n][nslots][64] (scratch; only the
+ *   slots present are written), then fgrad / virial_atom accumulated, or with pairbuf != NULL its entries ADDED to pairbuf.  afv
+ *   [64][256]; z_of_slot [nslots] (slot -> row of afv), aslot [n] (atom -> slot), present_part [n_part] 64-bit masks whose OR is the
+ *   set of slots present.
+ * aimnet_debug_pair_force: forces [n][3] = -(fgrad + sum_m pairbuf[i][m] - pairbuf[j_m][rev[i][m]]), rev [n][cap] = position of the
+ *   mirror entry in the row of j_m (-1: none). */
+int aimnet_debug_conv_fwd(int nq, const float* a, const int32_t* row_of, const float* q, const int32_t* nb_idx,
+                          const int32_t* nb_cnt, const float* pg, int cap, const float* agh_a, const float* agh_q, float rc,
+                          float eta, const float* shifts, void* x, int ldx, float* Vsave, float* Vqsave, int n_atoms,
+                          const int32_t* order, int species_moments, int split_max, int x_split, void* hip_stream);
+int aimnet_debug_unconcat(int nq, const float* xbar, int ldx, const float* Vsave, const float* Vqsave, const float* agh_a,
+                          const float* agh_q, float* Sbar, float* Sqbar, int n_atoms, void* hip_stream);
+int aimnet_debug_conv_bwd(int nq, int need_abar, int stress, const float* a, const int32_t* row_of, const float* q, const float* Sbar,
+                          const float* Sqbar, const int32_t* nb_idx, const int32_t* nb_cnt, const float* pg, int cap, float rc,
+                          float eta, const float* shifts, const float* xbar, int ldx, const float* abar_in, float* abar_out,
+                          const float* qbar_in, float* qbar_out, float* fgrad, float* virial_atom, int n_atoms, const int32_t* order,
+                          float* pairbuf, int pb_accum, int split_max, void* hip_stream);
+int aimnet_debug_conv_bwd_p0(int stress, const float* xbar, int ldx, const float* Vsave, const float* agh_a, const float* afv,
+                             const int32_t* z_of_slot, int nslots, const unsigned long long* present_part, int n_part,
+                             const int32_t* aslot, const int32_t* nb_idx, const int32_t* nb_cnt, const float* pg, int cap, float rc,
+                             float eta, const float* shifts, float* T, float* fgrad, float* virial_atom, int n_atoms,
+                             const int32_t* order, float* pairbuf, void* hip_stream);
+int aimnet_debug_pair_force(const int32_t* nb_idx, const int32_t* nb_cnt, const int32_t* rev, const float* pairbuf, int cap,
+                            int n_atoms, const float* fgrad, float* forces, void* hip_stream);
+
+/* Stand-alone neighbour list with the nvalchemiops contract. nbmat [n_atoms, max_nb] int32 is
  * filled with `fill_value` beyond each row's count; shifts [n_atoms, max_nb, 3] int32 may be NULL
  * when cell == NULL; num_nb [n_atoms] int32; status [2] = {max count, overflow flag}. */
 int aimnet_neighbor_list(const float* coord, const int32_t* mol_idx, int32_t n_atoms, int32_t n_mol,

@@ -84,7 +84,11 @@ def evaluate(
     dsf_alpha: float = 0.2,
     stress: bool = False,
     mult=None,
+    trace: dict | None = None,
 ) -> dict[str, np.ndarray]:
+    """trace (optional, filled in place): the conv blocks' operands and results per pass as tensors - "fwd": [{a, q, x, V, Vq}],
+    "bwd": [{p, xb, abar_in, qbar_in, Sbar, Sqbar, abar_out, qbar_out, rbar_ij, rbar_ji}] in the order computed - for tests that pin a
+    single kernel's reference to this specification (tests/test_conv_cases.py)."""
     dt = model.dtype
     x = torch.as_tensor(np.asarray(coord_wrapped)).to(dt)
     n = x.shape[0]
@@ -132,6 +136,8 @@ def evaluate(
             Vq = torch.einsum("qgh,nqgk->nqhk", model.agh_q, Sq[..., 1:])
             xin += [q, Sq[..., 0].reshape(n, -1), Vq.pow(2).sum(-1).reshape(n, -1)]
         h = torch.cat(xin, dim=-1)
+        if trace is not None:
+            trace.setdefault("fwd", []).append({"a": a, "q": q, "x": h, "V": V, "Vq": Vq})
         zs = []
         layers = model.mlps[p]
         last_linear = p == 0  # aimnet2.py:58-85: only the first MLP ends linear
@@ -218,6 +224,7 @@ def evaluate(
             gcur = gcur @ layers[li][0]
         xb = gcur  # (N, 704|733)
         # kernel: unconcat -> abar, Sbar, (qbar, Sqbar)
+        abar_in, qbar_in = abar, qbar
         abar = abar + xb[:, : A * G].view(n, A, G)
         Sbar = torch.empty(n, A, G, 4, dtype=dt)
         Sbar[..., 0] = xb[:, A * G : 2 * A * G].view(n, A, G)
@@ -257,6 +264,10 @@ def evaluate(
         rbar_ij = (dbar_ij.unsqueeze(-1) * u + (ubar_ij - (ubar_ij * u).sum(-1, keepdim=True) * u) * dinv) * vm
         uji = -u
         rbar_ji = (dbar_ji.unsqueeze(-1) * uji + (ubar_ji - (ubar_ji * uji).sum(-1, keepdim=True) * uji) * dinv) * vm
+        if trace is not None:
+            trace.setdefault("bwd", []).append({"p": p, "xb": xb, "abar_in": abar_in, "qbar_in": qbar_in, "Sbar": Sbar,
+                                                "Sqbar": Sqbar if p > 0 else None, "abar_out": abar, "qbar_out": qbar,
+                                                "rbar_ij": rbar_ij, "rbar_ji": rbar_ji})
         xbar = xbar + (rbar_ji - rbar_ij).sum(1)
         if stress:
             virial = virial + msum(torch.einsum("nma,nmb->nab", r * vm, rbar_ij).double())
