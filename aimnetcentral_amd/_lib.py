@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_set_dd",
     "aimnet_embedding_scratch_bytes",
     "aimnet_engine_set_embedding",
+    "aimnet_embedding_tangent_scratch_bytes",
+    "aimnet_engine_set_embedding_tangent",
     "aimnet_neighbor_list",
     "aimnet_neighbor_list_workspace_bytes",
     "aimnet_conv_sv_2d_sp_fwd",
@@ -184,6 +186,18 @@ class Embedding(C.Structure):
     ]
 
 
+class EmbeddingTangent(C.Structure):
+    """aimnet_embedding_tangent: arms aimnet_engine_hvp for the embedding; device pointers, caller-owned scratch."""
+
+    _fields_ = [
+        ("potential_hess", C.c_void_p),
+        ("ext_hv", C.c_void_p),
+        ("field", C.c_void_p),
+        ("scratch", C.c_void_p),
+        ("scratch_bytes", C.c_size_t),
+    ]
+
+
 class Outputs(C.Structure):
     _fields_ = [
         ("energy", C.c_void_p),
@@ -249,6 +263,10 @@ def load() -> C.CDLL:
     lib.aimnet_embedding_scratch_bytes.argtypes = [i32, i32, i32]
     lib.aimnet_engine_set_embedding.restype = C.c_int
     lib.aimnet_engine_set_embedding.argtypes = [vp, C.POINTER(Embedding)]
+    lib.aimnet_embedding_tangent_scratch_bytes.restype = sz
+    lib.aimnet_embedding_tangent_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.aimnet_engine_set_embedding_tangent.restype = C.c_int
+    lib.aimnet_engine_set_embedding_tangent.argtypes = [vp, C.POINTER(EmbeddingTangent)]
     lib.aimnet_debug_gemm.restype = C.c_int
     lib.aimnet_debug_gemm.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.aimnet_debug_split_bf3.restype = C.c_int

@@ -185,9 +185,14 @@ class AIMNet2ASE(Calculator):
         if np.asarray(atoms.pbc).any():
             raise PropertyNotImplementedError("Hessian for periodic systems is not supported by AIMNet2ASE.get_hessian().")
         self._charge_from_info(atoms)
-        res = self.base_calc({"coord": np.asarray(atoms.positions, dtype=np.float32), "numbers": np.asarray(atoms.numbers),
-                              "charge": float(self.charge), "mult": float(self.mult)}, forces=True, hessian=True,
-                             validate_species=self.validate_species)
+        data = {"coord": np.asarray(atoms.positions, dtype=np.float32), "numbers": np.asarray(atoms.numbers),
+                "charge": float(self.charge), "mult": float(self.mult)}
+        pc = self._embed if self._embed is not None and self._embed.ready() else None
+        if pc is not None and self.base_calc._embedding_hessian_mode is not None:
+            # embed() is active and AIMNet2Calculator.set_embedding_hessian("fixed_sites") was called: the embedded Hessian, atoms
+            # moving in the clamped point charges (without the mode the sites are left out, as before)
+            data["ext_coord"], data["ext_charge"] = pc.positions.astype(np.float32), pc.charges.astype(np.float32)
+        res = self.base_calc(data, forces=True, hessian=True, validate_species=self.validate_species)
         H = res["hessian"].detach()
         n = H.shape[0]
         return H.reshape(n * 3, n * 3).cpu().numpy()

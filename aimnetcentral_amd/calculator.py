@@ -491,6 +491,58 @@ class AIMNet2Calculator:
     def _has_embedding(self, data: dict[str, Any]) -> bool:
         return any(data.get(k) is not None for k in self.EMBEDDING_KEYS)
 
+    # second derivatives with an embedding: None (refused) or "fixed_sites" (atoms move, sites are clamped); see set_embedding_hessian
+    _embedding_hessian_mode = None
+    _embedding_mixed_block = False
+
+    def set_embedding_hessian(self, mode: str | None = None, mixed_block: bool = False) -> None:
+        """Whether `eval(hessian=True)` and `hessian_vector_product` accept the embedding keys.  `None` (the default): they raise
+        NotImplementedError.  "fixed_sites": the analytic tangent sweep carries E_emb = sum_i q_i phi_i with the atoms moving and the
+        sites clamped (include/aimnet_hip.h, aimnet_embedding_tangent), the response of the charges to the displacement included;
+        beside `ext_potential` the key `ext_potential_hess` (N,3,3) or (N,6: xx, yy, zz, xy, xz, yz) in V/A^2 is then required (zeros
+        for a uniform field).  `mixed_block=True`: `eval(hessian=True)` with point charges also returns `ext_hessian` (M,3,N,3), the
+        mixed block d2E / dX_A dx_i.  Not carried: polarisation of the charges by the field, the site-site block, `hvp_method = "fd"`,
+        PME, stress and domain decomposition (these keep raising NotImplementedError)."""
+        if mode not in (None, "fixed_sites"):
+            raise ValueError(f"set_embedding_hessian: mode must be None or 'fixed_sites', got {mode!r}")
+        self._embedding_hessian_mode = mode
+        self._embedding_mixed_block = bool(mixed_block) and mode is not None
+
+    def _embedding_hessian_ok(self, data: dict[str, Any]) -> bool:
+        """Second derivatives of this embedded input run: the mode is set and the analytic sweep is what would carry them."""
+        return (self._embedding_hessian_mode == "fixed_sites" and self.hvp_method == "analytic" and self._dd is None and
+                self._long_range(data.get("cell")).method != "pme")
+
+    def _embedding_hvp(self, data: dict[str, Any], d: dict[str, Any], want_ext_hv: bool):
+        """For one structure `d` (_single_structure of `data`): its embedding keys in the flat layout, and the `embedding=` dict of
+        HipEngine.hvp built from them.  Every shape error is a ValueError raised before the engine is touched."""
+        import torch
+
+        keys = self.EMBEDDING_KEYS + ("ext_potential_hess",)
+        flat = {k: data[k] for k in keys if data.get(k) is not None}
+        if torch.as_tensor(data["coord"]).ndim == 3:  # a batch of one: the arrays carry its axis too
+            flat = {k: torch.as_tensor(v)[0] for k, v in flat.items()}
+        n = d["coord"].shape[0]
+        emb = self._embedding({**flat, "charge": d["charge"]}, d["coord"], None, d.get("cell"), True)
+        emb.pop("want_ext_forces", None)
+        ph = flat.get("ext_potential_hess")
+        if ph is not None and "potential" not in emb:
+            raise ValueError("ext_potential_hess given without ext_potential")
+        if "potential" in emb:
+            if ph is None:
+                raise ValueError("second derivatives with ext_potential need ext_potential_hess (N,3,3) or (N,6); zeros for a uniform field")
+            try:
+                ph = torch.as_tensor(ph, device=self.device).detach().to(torch.float32)
+            except Exception as exc:
+                raise ValueError(f"ext_potential_hess: not convertible to a real tensor ({exc})") from exc
+            if tuple(ph.shape) not in ((n, 3, 3), (n, 6)):
+                raise ValueError(f"ext_potential_hess must have shape ({n}, 3, 3) or ({n}, 6), got {tuple(ph.shape)}")
+            emb["potential_hess"] = ph
+        if want_ext_hv and "ext_coord" in emb:
+            emb["want_ext_hv"] = True
+        flat.pop("ext_potential_hess", None)
+        return flat, emb
+
     def _embedding(self, data: dict[str, Any], coord, pad_mask, cell, forces: bool) -> dict[str, Any]:
         """The `embedding=` dict of HipEngine.eval from the optional keys `ext_coord` (M,3) / `ext_charge` (M,) [/ `ext_mol_idx`
         (M,)], and `ext_potential` (N,) / `ext_potential_grad` (N,3) in V and V/A.  For (B,N,3) input: `ext_coord` (B,M,3) and
@@ -641,7 +693,7 @@ class AIMNet2Calculator:
             self._validate_species_and_charge(data)
         self._maybe_warn_mult_ignored(data)
         embedded = self._has_embedding(data)
-        if embedded and (hessian or stress or self._dd is not None):
+        if embedded and (stress or self._dd is not None or (hessian and not self._embedding_hessian_ok(data))):
             raise NotImplementedError("electrostatic embedding (ext_coord / ext_charge / ext_potential) is carried by energies and "
                                       "forces only: not with stress=True, hessian=True or domain decomposition")
         if hessian:
@@ -776,8 +828,10 @@ class AIMNet2Calculator:
     # their tangents in double); "pme" always takes the finite-difference operator.
     hvp_method = "analytic"
 
-    def _hvp(self, d: dict[str, Any], dirs, eps: float | None = None):
-        """H @ v for K directions (K,N,3) of one structure: analytic tangent sweep, or finite differences (see `hvp_method`)."""
+    def _hvp(self, d: dict[str, Any], dirs, eps: float | None = None, emb: dict[str, Any] | None = None, extra: dict | None = None):
+        """H @ v for K directions (K,N,3) of one structure: analytic tangent sweep, or finite differences (see `hvp_method`).
+        `emb`: the `embedding=` dict of HipEngine.hvp (analytic sweep only: the callers have checked, _embedding_hessian_ok);
+        `extra` then receives `ext_hv` where the dict asks for it."""
         import torch
 
         if self.hvp_method not in ("analytic", "fd"):
@@ -792,7 +846,10 @@ class AIMNet2Calculator:
             return self._fd_hvp(d, dirs, lr, pbc3, eps)
         n = d["coord"].shape[0]
         res = self.engine.hvp(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
-                              self._engine_charge(d["charge"], d.get("mult")), dirs, cell=cell, pbc=pbc3, **lr.kwargs())
+                              self._engine_charge(d["charge"], d.get("mult")), dirs, cell=cell, pbc=pbc3, **lr.kwargs(),
+                              **({"embedding": emb} if emb is not None else {}))
+        if extra is not None and "ext_hv" in res:
+            extra["ext_hv"] = res["ext_hv"]
         return res["hv"]
 
     def _split_structures(self, data: dict[str, Any]):
@@ -831,7 +888,10 @@ class AIMNet2Calculator:
     def _eval_hessian(self, data, *, forces: bool, stress: bool, validate_species: bool) -> dict[str, Any]:
         import torch
 
+        embedded = self._has_embedding(data)
         subs, stack = self._split_structures(data)
+        if subs is not None and embedded:
+            raise NotImplementedError("Hessian calculation with an electrostatic embedding supports a single structure only")
         if subs is not None:
             results = [self.eval(sub, forces=forces, stress=stress, hessian=True, validate_species=validate_species) for sub in subs]
             out: dict[str, Any] = {}
@@ -842,12 +902,18 @@ class AIMNet2Calculator:
             return out
         d = self._single_structure(data, "Hessian calculation")
         single = {k: v for k, v in d.items() if k in ("coord", "numbers", "charge", "cell", "pbc", "mult")}
+        emb, extra = None, {}
+        if embedded:  # (set_embedding_hessian("fixed_sites"): eval has checked) energy and forces take the term as the Hessian does
+            flat, emb = self._embedding_hvp(data, d, self._embedding_mixed_block)
+            single.update(flat)
         out = self.eval(single, forces=True, stress=stress, hessian=False, validate_species=False)
         n = d["coord"].shape[0]
         eye = torch.eye(3 * n, device=self.device, dtype=torch.float32).view(3 * n, n, 3)
-        hess = self._hvp(d, eye).view(3 * n, 3 * n)
+        hess = self._hvp(d, eye, emb=emb, extra=extra).view(3 * n, 3 * n)
         hess = 0.5 * (hess + hess.T)  # the Hessian is symmetric; the computed columns are to fp32 round-off (FD: to O(noise))
         out["hessian"] = hess.view(n, 3, n, 3)
+        if "ext_hv" in extra:  # [3N directions (i, c)][M][3] -> d2E / dX_A dx_i as (M, 3, N, 3)
+            out["ext_hessian"] = extra["ext_hv"].view(n, 3, -1, 3).permute(2, 3, 0, 1).contiguous()
         if not forces:
             out.pop("forces", None)
         return out
@@ -867,7 +933,8 @@ class AIMNet2Calculator:
         reference, ignored by the analytic operator - it is the step of the finite-difference one (`hvp_method = "fd"`)."""
         if create_graph:
             raise NotImplementedError("create_graph=True needs autograd through the model; the native engine has none")
-        if self._has_embedding(data):
+        embedded = self._has_embedding(data)
+        if embedded and not self._embedding_hessian_ok(data):  # (set_embedding_hessian("fixed_sites") switches the term on)
             raise NotImplementedError("hessian_vector_product: the electrostatic-embedding term is not carried by the tangent sweep")
         if validate_species:
             self._validate_species_and_charge(data)
@@ -875,7 +942,8 @@ class AIMNet2Calculator:
         d = self._single_structure(data, "hessian_vector_product")
         n = d["coord"].shape[0]
         v = self._directions(vectors, n)
-        hv = self._hvp(d, v.reshape(-1, n, 3), eps)
+        emb = self._embedding_hvp(data, d, False)[1] if embedded else None
+        hv = self._hvp(d, v.reshape(-1, n, 3), eps, emb=emb)
         return hv.view_as(v)
 
     def charge_response(self, data: dict[str, Any], vectors, *, validate_species: bool = True) -> dict[str, Any]:

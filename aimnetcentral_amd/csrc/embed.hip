@@ -5,7 +5,11 @@
 //   dE_emb/dx_i = q_i grad phi_i + sum_j phi_j dq_j/dx_i ,
 // whose second term is the backward sweep's own job - the seed pass adds phi_i to the adjoint dE/dq_i (qbar) that the Coulomb block
 // has seeded, exactly as the Ewald block does with its potential.
-// Pair terms in fp32, every sum in double; no atomics on results, fixed summation orders: bitwise repeatable.
+// The tangent sweep (aimnet_engine_set_embedding_tangent, hvp.hip) carries the term through the Hessian-vector product with the
+// atoms moving along v and the sites clamped: with g = grad phi, T = grad grad phi = k_e sum_A Q_A (3 r r^T / d^5 - 1 / d^3)
+//   t_qbar_i^k += g_i . v_i^k        t_xbar_i^k += t_q_i^k g_i + q_i T_i v_i^k        (embed_tseed_kernel)
+// and the backward sweep does the rest (sum_j phi_j d2q_j v, J t_phi).  The mixed atom-site block comes from embed_tsite_kernel.
+// Pair terms in fp32 (the tensor's in double), every sum in double; no atomics on results, fixed summation orders: bitwise repeatable.
 #include "common.h"
 #include "kernels.h"
 
@@ -45,22 +49,28 @@ __global__ __launch_bounds__(256) void embed_sites_kernel(const int* __restrict_
 
 // block = (atom i, slot s): lanes stride over the sites of the chunks s, s + n_slots, ... of the atom's molecule (consecutive lanes
 // read consecutive sites; the site stream is shared by every atom of the molecule and stays in L2).  One partial
-// (sum Q / d, -sum Q (x_i - X) / d^3) per block; it depends on the geometry alone.
+// (sum Q / d, -sum Q (x_i - X) / d^3) per block; it depends on the geometry alone.  TENSOR (the tangent sweep): six more sums, the
+// components xx, yy, zz, xy, xz, yz of sum Q (3 r r^T / d^5 - 1 / d^3), 10 partials per block, the tensor's pair terms in double (see
+// there).  With ten double accumulators and the double pair term the four-fold unrolled loop takes 101 VGPRs, four waves per SIMD
+// (the plain instantiation: 44, eight) - one pass per aimnet_engine_hvp call, bound by the site stream.  The flag being a template
+// parameter, the instantiation aimnet_engine_eval launches compiles to the instructions it had before the flag existed.
+template <bool TENSOR>
 __global__ __launch_bounds__(256) void embed_field_kernel(const float* __restrict__ x, const int* __restrict__ mol_c, int n_slots,
                                                           const float* __restrict__ ext_coord,
                                                           const float* __restrict__ ext_charge,
                                                           const int* __restrict__ ext_start, double* __restrict__ part) {
+  constexpr int NP = TENSOR ? EMBED_NP_TENSOR : 4;
   __shared__ double sh[4];
   const int i = blockIdx.x / n_slots, s = blockIdx.x % n_slots;
   const int m = mol_c[i];
   const int s0 = ext_start[m], cnt = max(0, ext_start[m + 1] - s0);
   const int n_chunk = (int)(((long long)cnt + EMBED_CHUNK - 1) / EMBED_CHUNK);
   if (s >= n_chunk) {  // (block-uniform) this slot has no chunk of the molecule: its partial is zero
-    if (threadIdx.x < 4) part[(size_t)blockIdx.x * 4 + threadIdx.x] = 0.0;
+    if (threadIdx.x < NP) part[(size_t)blockIdx.x * NP + threadIdx.x] = 0.0;
     return;
   }
   const float xi = x[3 * (size_t)i], yi = x[3 * (size_t)i + 1], zi = x[3 * (size_t)i + 2];
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  double acc[NP] = {};
   for (int k = s; k < n_chunk; k += n_slots) {
     const int lo = k * EMBED_CHUNK;  // (relative to s0: lo < cnt)
     const int hi = (int)min((long long)cnt, (long long)lo + EMBED_CHUNK);
@@ -76,12 +86,30 @@ __global__ __launch_bounds__(256) void embed_field_kernel(const float* __restric
       acc[1] -= (double)(t * dx);
       acc[2] -= (double)(t * dy);
       acc[3] -= (double)(t * dz);
+      if constexpr (TENSOR) {
+        // The tensor's pair term in double.  In fp32 a component reaches 2 |Q| / d^3 through some nineteen roundings (d^-5 takes
+        // the error of the reciprocal root five times), which the eight-rounding allowance of a field sum does not cover for a
+        // single site (measured: 12.9 * 2^-24 |Q| / d^3 at one site).  The fp32 reciprocal root is the seed of two Newton steps.
+        const double ex = (double)xi - (double)ext_coord[3 * a], ey = (double)yi - (double)ext_coord[3 * a + 1],
+                     ez = (double)zi - (double)ext_coord[3 * a + 2];
+        const double e2 = ex * ex + ey * ey + ez * ez;
+        double y = (double)rinv;
+        y = y * (1.5 - 0.5 * e2 * y * y);
+        y = y * (1.5 - 0.5 * e2 * y * y);
+        const double td = (double)ext_charge[a] * y * y * y, t5 = 3.0 * td * y * y;
+        acc[4] += t5 * ex * ex - td;
+        acc[5] += t5 * ey * ey - td;
+        acc[6] += t5 * ez * ez - td;
+        acc[7] += t5 * ex * ey;
+        acc[8] += t5 * ex * ez;
+        acc[9] += t5 * ey * ez;
+      }
     }
   }
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
+  for (int c = 0; c < NP; ++c) {
     const double v = embed_block_sum(acc[c], sh);
-    if (threadIdx.x == 0) part[(size_t)blockIdx.x * 4 + c] = v;
+    if (threadIdx.x == 0) part[(size_t)blockIdx.x * NP + c] = v;
   }
 }
 
@@ -179,9 +207,121 @@ __global__ __launch_bounds__(256) void embed_site_kernel(const float* __restrict
   }
 }
 
+// ---- the tangent sweep (hvp.hip, Tangent::embedding_seeds) ------------------------------------------------------------------------
+// thread = (atom i, direction k): the slot partials in slot order, times k_e, plus the caller's potential / grad / hess; then the
+// addends of the seeds in the layouts of hvp.hip's coul_store (qbar [nq][N], tqbar [K][nq][N], xbar [N][3], txbar [K][N][3]; the
+// Coulomb terms see alpha + beta: every channel takes the same seed).  The k = 0 threads add the primal seeds and write `field`.
+// Every thread forms the same ten sums in the same order: what an atom adds does not depend on how many directions ride along.
+__global__ __launch_bounds__(256) void embed_tseed_kernel(const float* __restrict__ q, const float* __restrict__ tq, int nq,
+                                                          const float* __restrict__ tv, int n_atoms, int n_slots,
+                                                          const double* __restrict__ part, const float* __restrict__ potential,
+                                                          const float* __restrict__ potential_grad,
+                                                          const float* __restrict__ potential_hess, float* __restrict__ qbar,
+                                                          float* __restrict__ tqbar, float* __restrict__ xbar,
+                                                          float* __restrict__ txbar, double* __restrict__ field) {
+  constexpr int NP = EMBED_NP_TENSOR;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+  if (i >= n_atoms) return;
+  const size_t N = (size_t)n_atoms;
+  double f[NP] = {};
+  for (int s = 0; s < n_slots; ++s)
+#pragma unroll
+    for (int c = 0; c < NP; ++c) f[c] += part[((size_t)i * n_slots + s) * NP + c];
+#pragma unroll
+  for (int c = 0; c < NP; ++c) f[c] *= KE;
+  if (potential) f[0] += (double)potential[i];
+  if (potential_grad)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) f[1 + c] += (double)potential_grad[3 * (size_t)i + c];
+  if (potential_hess)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) f[4 + c] += (double)potential_hess[6 * (size_t)i + c];
+  float qf = q[i], tqf = tq[((size_t)k * nq) * N + i];  // total charge and its tangent (hvp.hip, q_total)
+  if (nq == 2) {
+    qf += q[N + i];
+    tqf += tq[((size_t)k * nq + 1) * N + i];
+  }
+  const double qi = (double)qf, tqi = (double)tqf;
+  const size_t te = ((size_t)k * N + i) * 3;
+  const double vx = (double)tv[te], vy = (double)tv[te + 1], vz = (double)tv[te + 2];
+  const double gv = f[1] * vx + f[2] * vy + f[3] * vz;
+  const double Tv[3] = {f[4] * vx + f[7] * vy + f[8] * vz, f[7] * vx + f[5] * vy + f[9] * vz, f[8] * vx + f[9] * vy + f[6] * vz};
+  for (int ch = 0; ch < nq; ++ch) {
+    if (k == 0) qbar[(size_t)ch * N + i] += (float)f[0];
+    tqbar[((size_t)k * nq + ch) * N + i] += (float)gv;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (k == 0) xbar[3 * (size_t)i + c] += (float)(qi * f[1 + c]);
+    txbar[te + c] += (float)(tqi * f[1 + c] + qi * Tv[c]);
+  }
+  if (k == 0 && field)
+#pragma unroll
+    for (int c = 0; c < NP; ++c) field[(size_t)i * NP + c] = f[c];
+}
+
+// mixed atom-site block: ext_hv[k][A] = d/d eps of dE_emb/dX_A along v^k, the charge response included,
+//   -k_e Q_A sum_i [ t_q_i s / |s|^3 + q_i (-v_i / |s|^3 + 3 (s . v_i) s / |s|^5) ] ,  s = X_A - x_i .
+// block = (256 consecutive sites, direction k), thread = site - embed_site_kernel's mapping: the atoms (x, q, v^k, t_q^k) of every
+// molecule the block's sites belong to pass through LDS in tiles of 256, and a thread sums over its molecule's atoms in atom order.
+__global__ __launch_bounds__(256) void embed_tsite_kernel(const float* __restrict__ x, const float* __restrict__ q,
+                                                          const float* __restrict__ tq, int nq, const float* __restrict__ tv,
+                                                          int n_atoms, const int* __restrict__ mol_start,
+                                                          const float* __restrict__ ext_coord, const float* __restrict__ ext_charge,
+                                                          const int* __restrict__ ext_mol_c, int n_ext, float* __restrict__ ext_hv) {
+  __shared__ float4 tile_x[256], tile_v[256];  // (x, q) and (v, t_q)
+  const int a0 = blockIdx.x * 256, a = a0 + (int)threadIdx.x, k = blockIdx.y;
+  const size_t N = (size_t)n_atoms;
+  const bool live = a < n_ext;
+  const int a_last = min(n_ext, a0 + 256) - 1;
+  const int mf = ext_mol_c[a0], ml = ext_mol_c[a_last];  // (block-uniform; a sorted list: the block's molecules lie between them)
+  const int m_lo = min(mf, ml), m_hi = max(mf, ml);
+  const int mine = live ? ext_mol_c[a] : -1;
+  float X = 0.f, Y = 0.f, Z = 0.f;
+  if (live) { X = ext_coord[3 * (size_t)a]; Y = ext_coord[3 * (size_t)a + 1]; Z = ext_coord[3 * (size_t)a + 2]; }
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int m = m_lo; m <= m_hi; ++m) {
+    const int i0 = mol_start[m], i1 = mol_start[m + 1];
+    for (int t0 = i0; t0 < i1; t0 += 256) {
+      const int nt = min(256, i1 - t0);
+      __syncthreads();
+      if ((int)threadIdx.x < nt) {
+        const size_t i = (size_t)t0 + threadIdx.x, te = ((size_t)k * N + i) * 3;
+        float qf = q[i], tqf = tq[((size_t)k * nq) * N + i];
+        if (nq == 2) {
+          qf += q[N + i];
+          tqf += tq[((size_t)k * nq + 1) * N + i];
+        }
+        tile_x[threadIdx.x] = make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], qf);
+        tile_v[threadIdx.x] = make_float4(tv[te], tv[te + 1], tv[te + 2], tqf);
+      }
+      __syncthreads();
+      if (mine == m) {
+        for (int j = 0; j < nt; ++j) {
+          const float4 at = tile_x[j], av = tile_v[j];
+          const float sx = X - at.x, sy = Y - at.y, sz = Z - at.z;
+          const float d2 = fmaf(sz, sz, fmaf(sy, sy, sx * sx));
+          const float rinv = rsqrtf(d2);
+          const float r3 = rinv * rinv * rinv;
+          const float sv = fmaf(sz, av.z, fmaf(sy, av.y, sx * av.x));
+          const float cs = r3 * (av.w + 3.0f * at.w * sv * rinv * rinv);  // coefficient of s
+          const float cv = at.w * r3;                                     // coefficient of -v
+          acc[0] += (double)(cs * sx - cv * av.x);
+          acc[1] += (double)(cs * sy - cv * av.y);
+          acc[2] += (double)(cs * sz - cv * av.z);
+        }
+      }
+    }
+  }
+  if (!live) return;
+  const double kq = -KE * (double)ext_charge[a];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) ext_hv[((size_t)k * n_ext + a) * 3 + c] = (float)(kq * acc[c]);
+}
+
 }  // namespace
 
-void embed_carve(EmbedBuffers& b, char* base, int n_atoms, int n_mol, int n_ext) {
+void embed_carve(EmbedBuffers& b, char* base, int n_atoms, int n_mol, int n_ext, bool tensor) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* r = base ? base + off : nullptr;
@@ -191,8 +331,8 @@ void embed_carve(EmbedBuffers& b, char* base, int n_atoms, int n_mol, int n_ext)
   const size_t n = (size_t)n_atoms, ns = (size_t)embed_slots(n_ext, n_mol);
   b.ext_start = (int*)take(((size_t)n_mol + 1) * sizeof(int));
   b.ext_mol_c = (int*)take((size_t)n_ext * sizeof(int));
-  b.part = (double*)take(n * ns * 4 * sizeof(double));
-  b.e_atom = (double*)take(n * sizeof(double));
+  b.part = (double*)take(n * ns * (tensor ? EMBED_NP_TENSOR : 4) * sizeof(double));
+  b.e_atom = (double*)take(tensor ? 0 : n * sizeof(double));  // (the tangent sweep forms no energy)
   b.total = off;
 }
 
@@ -205,15 +345,18 @@ int launch_embed_sites(hipStream_t s, const int* ext_mol_idx, int n_ext, int n_m
 }
 
 int launch_embed_field(hipStream_t s, const float* x, const int* mol_c, int n_atoms, int n_mol, const float* ext_coord,
-                       const float* ext_charge, int n_ext, const EmbedBuffers& b) {
+                       const float* ext_charge, int n_ext, const EmbedBuffers& b, bool tensor) {
   const int ns = embed_slots(n_ext, n_mol);
-  if (ns == 0) return 0;
+  if (ns == 0 || n_atoms <= 0) return 0;
   if ((long long)n_atoms * ns > (long long)INT32_MAX) {
     set_last_error("embedding: n_atoms * slots exceeds the grid limit");
     return -1;
   }
-  hipLaunchKernelGGL(embed_field_kernel, dim3((unsigned)(n_atoms * ns)), dim3(256), 0, s, x, mol_c, ns, ext_coord, ext_charge,
-                     b.ext_start, b.part);
+  const dim3 grid((unsigned)(n_atoms * ns)), block(256);
+  if (tensor)
+    hipLaunchKernelGGL((embed_field_kernel<true>), grid, block, 0, s, x, mol_c, ns, ext_coord, ext_charge, b.ext_start, b.part);
+  else
+    hipLaunchKernelGGL((embed_field_kernel<false>), grid, block, 0, s, x, mol_c, ns, ext_coord, ext_charge, b.ext_start, b.part);
   AIMNET_LAUNCH_CHECK();
   return 0;
 }
@@ -242,6 +385,26 @@ int launch_embed_site_pass(hipStream_t s, const float* x, const float* q, const 
   if (n_ext <= 0 || (!ext_forces && !ext_potential)) return 0;
   hipLaunchKernelGGL(embed_site_kernel, dim3(ceil_div(n_ext, 256)), dim3(256), 0, s, x, q, mol_start, n_mol, ext_coord, ext_charge,
                      b.ext_mol_c, n_ext, ext_forces, ext_potential);
+  AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_embed_tseed(hipStream_t s, const float* q, const float* tq, int nq, const float* vectors, int n_atoms, int n_vec, int n_ext,
+                       int n_mol, const float* potential, const float* potential_grad, const float* potential_hess,
+                       const EmbedBuffers& b, float* qbar, float* tqbar, float* xbar, float* txbar, double* field) {
+  if (n_atoms <= 0 || n_vec <= 0) return 0;
+  hipLaunchKernelGGL(embed_tseed_kernel, dim3(ceil_div(n_atoms, 256), n_vec), dim3(256), 0, s, q, tq, nq, vectors, n_atoms,
+                     embed_slots(n_ext, n_mol), b.part, potential, potential_grad, potential_hess, qbar, tqbar, xbar, txbar, field);
+  AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_embed_tsite(hipStream_t s, const float* x, const float* q, const float* tq, int nq, const float* vectors, int n_atoms,
+                       int n_vec, const int* mol_start, const float* ext_coord, const float* ext_charge, int n_ext,
+                       const EmbedBuffers& b, float* ext_hv) {
+  if (n_ext <= 0 || n_vec <= 0 || !ext_hv) return 0;
+  hipLaunchKernelGGL(embed_tsite_kernel, dim3(ceil_div(n_ext, 256), n_vec), dim3(256), 0, s, x, q, tq, nq, vectors, n_atoms, mol_start,
+                     ext_coord, ext_charge, b.ext_mol_c, n_ext, ext_hv);
   AIMNET_LAUNCH_CHECK();
   return 0;
 }

@@ -172,6 +172,9 @@ struct aimnet_engine {
   // aimnet_engine_set_embedding: electrostatic embedding of the charges (csrc/embed.hip), a copy of the caller's struct
   bool emb_on = false;
   aimnet_embedding emb{};
+  // aimnet_engine_set_embedding_tangent: aimnet_engine_hvp carries the embedding (hvp.hip, Tangent::embedding_seeds); off with emb_on
+  bool emb_tangent_on = false;
+  aimnet_embedding_tangent emb_tangent{};
   float* unit_cell = nullptr;  // 3 x 3 identity (device): "cell" of the virial sums of a decomposed evaluation
   double* sae;
   // species slots of the pass-0 moment backward: slot = rank of the atomic number among the embedding rows that

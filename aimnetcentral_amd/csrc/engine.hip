@@ -1217,6 +1217,8 @@ size_t aimnet_embedding_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_
 
 int aimnet_engine_set_embedding(aimnet_engine* e, const aimnet_embedding* emb) {
   if (!e) return AIMNET_E_INVALID;
+  e->emb_tangent_on = false;  // a new embedding, or none, starts unarmed (aimnet_engine_set_embedding_tangent)
+  e->emb_tangent = aimnet_embedding_tangent{};
   if (!emb) {
     e->emb_on = false;
     e->emb = aimnet_embedding{};
@@ -1232,6 +1234,33 @@ int aimnet_engine_set_embedding(aimnet_engine* e, const aimnet_embedding* emb) {
   }
   e->emb = *emb;  // (checked against the problem size by every evaluation, eval_plan.h)
   e->emb_on = true;
+  return AIMNET_OK;
+}
+
+size_t aimnet_embedding_tangent_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext) {
+  if (n_atoms <= 0 || n_mol <= 0 || n_ext < 0) return 0;
+  aimnet::EmbedBuffers b;
+  aimnet::embed_carve(b, nullptr, n_atoms, n_mol, n_ext, true);
+  return b.total;
+}
+
+int aimnet_engine_set_embedding_tangent(aimnet_engine* e, const aimnet_embedding_tangent* t) {
+  if (!e) return AIMNET_E_INVALID;
+  if (!t) {
+    e->emb_tangent_on = false;
+    e->emb_tangent = aimnet_embedding_tangent{};
+    return AIMNET_OK;
+  }
+  if (!e->emb_on) {
+    set_last_error("set_embedding_tangent: no embedding is set (aimnet_engine_set_embedding first)");
+    return AIMNET_E_INVALID;
+  }
+  if (!t->scratch) {
+    set_last_error("set_embedding_tangent: scratch is required (aimnet_embedding_tangent_scratch_bytes)");
+    return AIMNET_E_INVALID;
+  }
+  e->emb_tangent = *t;  // (checked against the problem size by every aimnet_engine_hvp call, tangent_plan.h)
+  e->emb_tangent_on = true;
   return AIMNET_OK;
 }
 

@@ -1015,7 +1015,8 @@ struct Tangent {
   int open(const TangentRequest& rq, void* workspace, size_t workspace_bytes);
   int mlp_forward(const std::vector<Layer>& Ls, int n_layers, bool last_linear, const float* hin, float* const* z, float* y);
   int mlp_backward(const std::vector<Layer>& Ls, int n_layers, bool last_linear, const float* g_ext, float* const* z);
-  int lists(), forward(), coulomb_seeds(), backward(), d3_block(bool want_forces);
+  int lists(), forward(), coulomb_seeds(), embedding_seeds(), backward(), embedding_sites(), d3_block(bool want_forces);
+  EmbedBuffers emb{};  // carved from aimnet_embedding_tangent.scratch by embedding_seeds()
   int head_forward() { return mlp_forward(e->head, (int)e->head.size() - 1, false, W.y[np - 1], W.hz, nullptr); }
   int write_hvp(float* hv, float* forces), write_charge_response(float* charges, float* dq, float* dspin, float* dmu);
 };
@@ -1203,6 +1204,28 @@ int Tangent::coulomb_seeds() {
   return 0;
 }
 
+// electrostatic embedding (embed.hip; plan: armed by aimnet_engine_set_embedding_tangent): one more addend of the Coulomb seeds and
+// of their tangents, after every Coulomb term and in front of the backward sweep that reads them.  The field pass (phi, grad phi and
+// the field-gradient tensor of the point charges) depends on the geometry alone: once per call, whatever K is.
+int Tangent::embedding_seeds() {
+  const aimnet_embedding& m = e->emb;
+  const aimnet_embedding_tangent& mt = e->emb_tangent;
+  embed_carve(emb, (char*)mt.scratch, N, n_mol, m.n_ext, true);
+  if (m.n_ext > 0) {
+    RC(launch_embed_sites(s, m.ext_mol_idx, m.n_ext, n_mol, emb, status + 6));
+    RC(launch_embed_field(s, in->coord, mol_c, N, n_mol, m.ext_coord, m.ext_charge, m.n_ext, emb, true));
+  }
+  return launch_embed_tseed(s, W.q[np - 2], W.tq[np - 2], nq, vectors, N, K, m.n_ext, n_mol, m.potential, m.potential_grad,
+                            mt.potential_hess, emb, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar, mt.field);
+}
+
+// the mixed atom-site block of the embedding, from the final charges and their tangents (untouched by the backward sweep)
+int Tangent::embedding_sites() {
+  const aimnet_embedding& m = e->emb;
+  return launch_embed_tsite(s, in->coord, W.q[np - 2], W.tq[np - 2], nq, vectors, N, K, W.nl.mol_start, m.ext_coord, m.ext_charge,
+                            m.n_ext, emb, e->emb_tangent.ext_hv);
+}
+
 // backward + tangent: the energy head, then the passes from the last to the first
 int Tangent::backward() {
   const dim3 gik(N, K), gmk(n_mol, K), b256(256);
@@ -1306,6 +1329,15 @@ TangentRequest tangent_request(TangentEntry entry, const aimnet_engine* e, int N
   r.coulomb = opt->coulomb; r.dftd3 = opt->dftd3; r.dsf_rc_set = opt->dsf_rc > 0.0f;
   r.max_nb = opt->max_nb; r.max_nb_lr = opt->max_nb_lr; r.max_nb_d3 = opt->max_nb_d3; r.ewald_max_k = opt->ewald_max_k;
   r.ewald_kb = EWALD_KB; r.d3_tables = e->d3.ns != 0; r.emb_on = e->emb_on; r.bbox_ok = bbox_applies(N, n_mol);
+  if (entry == TangentEntry::Hvp && e->emb_on && e->emb_tangent_on) {
+    const aimnet_embedding& m = e->emb;
+    const aimnet_embedding_tangent& mt = e->emb_tangent;
+    r.emb_tangent = true;
+    r.emb_n_ext = m.n_ext;
+    r.emb_potential = m.potential != nullptr; r.emb_potential_grad = m.potential_grad != nullptr;
+    r.emb_potential_hess = mt.potential_hess != nullptr; r.emb_mol_idx = m.ext_mol_idx != nullptr;
+    r.emb_scratch_ok = mt.scratch && m.n_ext >= 0 && mt.scratch_bytes >= aimnet_embedding_tangent_scratch_bytes(N, n_mol, m.n_ext);
+  }
   if (!in) return r;
   r.pbc = in->cell != nullptr; r.n_cell = in->n_cell;
   r.ewald_args = entry == TangentEntry::Hvp && opt->coulomb == AIMNET_COULOMB_EWALD ? ewald_args_check(in, opt) : 0;
@@ -1365,7 +1397,9 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
   RC(t.forward());
   RC(t.head_forward());
   RC(t.coulomb_seeds());
+  if (t.P.embedding) RC(t.embedding_seeds());
   RC(t.backward());
+  if (t.P.embedding) RC(t.embedding_sites());
   if (t.P.d3_block) RC(t.d3_block(forces != nullptr));
   return t.write_hvp(hv, forces);
 }

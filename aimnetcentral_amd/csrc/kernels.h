@@ -463,6 +463,7 @@ int launch_copy_f32(hipStream_t s, const float* src, float* dst, size_t n);
 // device or on the data (mirrored in _lib.py); a molecule that owns more than its share of the sites runs more chunks per slot.
 constexpr int EMBED_CHUNK = 1024;
 constexpr int EMBED_MAX_SLOTS = 64;
+constexpr int EMBED_NP_TENSOR = 10;  // partials per block of the tangent sweep's field pass: phi, grad phi, grad grad phi (xx yy zz xy xz yz)
 constexpr int STATUS_EXT_MOL_IDX = 128;  // bit of status[6]: ext_mol_idx holds an entry outside [0, n_mol) or is not sorted
 static inline int embed_slots(int n_ext, int n_mol) {
   const long long per_mol = ((long long)n_ext + n_mol - 1) / (n_mol > 0 ? n_mol : 1);
@@ -472,16 +473,17 @@ static inline int embed_slots(int n_ext, int n_mol) {
 struct EmbedBuffers {  // carved from the caller's scratch (embed_carve; base == NULL: sizes only)
   int* ext_start;   // [n_mol + 1] first site of every molecule
   int* ext_mol_c;   // [n_ext] ext_mol_idx clamped to [0, n_mol)
-  double* part;     // [n_atoms][n_slots][4] partial (phi, grad phi) of the field pass
-  double* e_atom;   // [n_atoms] q_i phi_i
+  double* part;     // [n_atoms][n_slots][4] partial (phi, grad phi) of the field pass; tensor: [..][EMBED_NP_TENSOR]
+  double* e_atom;   // [n_atoms] q_i phi_i (tensor: not carved)
   size_t total;
 };
-void embed_carve(EmbedBuffers& b, char* base, int n_atoms, int n_mol, int n_ext);
+// tensor: the buffers of the tangent sweep (aimnet_embedding_tangent.scratch) - the same lists, the wider partials
+void embed_carve(EmbedBuffers& b, char* base, int n_atoms, int n_mol, int n_ext, bool tensor = false);
 // ext_start / ext_mol_c from ext_mol_idx (NULL: every site belongs to molecule 0); raises STATUS_EXT_MOL_IDX in *status6
 int launch_embed_sites(hipStream_t s, const int* ext_mol_idx, int n_ext, int n_mol, const EmbedBuffers& b, int* status6);
-// field pass: one block per (atom, slot); x: the coordinates as the caller gave them
+// field pass: one block per (atom, slot); x: the coordinates as the caller gave them; tensor: with the field-gradient tensor
 int launch_embed_field(hipStream_t s, const float* x, const int* mol_c, int n_atoms, int n_mol, const float* ext_coord,
-                       const float* ext_charge, int n_ext, const EmbedBuffers& b);
+                       const float* ext_charge, int n_ext, const EmbedBuffers& b, bool tensor = false);
 // seed pass: ecoul += q phi; grad: qbar += phi, fgrad += q grad phi; then the molecule sums of q phi into energy (may be NULL)
 int launch_embed_seed(hipStream_t s, bool grad, const float* q, int n_atoms, int n_ext, const float* potential,
                       const float* potential_grad, const EmbedBuffers& b, double* ecoul, float* qbar, float* fgrad,
@@ -489,5 +491,15 @@ int launch_embed_seed(hipStream_t s, bool grad, const float* q, int n_atoms, int
 // site pass: ext_forces[A] = -dE_emb/dX_A, ext_potential[A] = k_e sum_i q_i / |x_i - X_A| (either may be NULL)
 int launch_embed_site_pass(hipStream_t s, const float* x, const float* q, const int* mol_start, int n_mol, const float* ext_coord,
                            const float* ext_charge, int n_ext, const EmbedBuffers& b, float* ext_forces, float* ext_potential);
+
+// tangent sweep (hvp.hip): the embedding's addends onto qbar / xbar (k = 0) and tqbar / txbar in coul_store's layouts, from the
+// partials of a tensor field pass; field [n_atoms][EMBED_NP_TENSOR] (may be NULL) receives phi, grad phi, grad grad phi as used
+int launch_embed_tseed(hipStream_t s, const float* q, const float* tq, int nq, const float* vectors, int n_atoms, int n_vec, int n_ext,
+                       int n_mol, const float* potential, const float* potential_grad, const float* potential_hess,
+                       const EmbedBuffers& b, float* qbar, float* tqbar, float* xbar, float* txbar, double* field);
+// mixed atom-site block ext_hv [n_vec][n_ext][3] (NULL: nothing runs)
+int launch_embed_tsite(hipStream_t s, const float* x, const float* q, const float* tq, int nq, const float* vectors, int n_atoms,
+                       int n_vec, const int* mol_start, const float* ext_coord, const float* ext_charge, int n_ext,
+                       const EmbedBuffers& b, float* ext_hv);
 
 }  // namespace aimnet

@@ -22,6 +22,11 @@ struct TangentRequest {
   bool bbox_ok, arrays;      // bbox_applies(N, n_mol); coord, numbers, mol_idx and charge are all given
   bool nbmat, nbmat_lr, nbmat_d3;            // caller-supplied matrices
   bool hv, forces, dq, dspin, dmu, charges;  // outputs given: of Hvp (hv, forces), of ChargeResponse (the other four)
+  // aimnet_engine_set_embedding_tangent armed the sweep for the embedding (read with emb_on and Hvp only); then, of the two structs:
+  bool emb_tangent;
+  int emb_n_ext;                                                // point charges
+  bool emb_potential, emb_potential_grad, emb_potential_hess;  // which per-atom arrays are given
+  bool emb_mol_idx, emb_scratch_ok;  // ext_mol_idx given; scratch given and at least aimnet_embedding_tangent_scratch_bytes
 };
 
 // ---- argument checks: 0, or AIMNET_E_INVALID with the message in msg.  Nothing has been launched when they run --------------------
@@ -31,8 +36,25 @@ inline int tangent_validate(const TangentRequest& r, char* msg, size_t n) {
   const bool d3 = hvp && r.dftd3 != 0;
   if (!hvp && !r.dq) return plan_reject(msg, n, "charge_response: dq is required");
   if (r.N <= 0 || r.n_mol <= 0 || !r.arrays) return plan_reject(msg, n, "%s: null or empty input", who);
-  if (hvp && r.emb_on)
+  if (hvp && r.emb_on && !r.emb_tangent)
     return plan_reject(msg, n, "hvp: the embedding term is not carried by the tangent sweep (aimnet_engine_set_embedding(e, NULL) first)");
+  if (hvp && r.emb_on) {  // armed (aimnet_engine_set_embedding_tangent)
+    if (r.emb_n_ext > 0 && r.pbc)
+      return plan_reject(msg, n, "hvp: embedding point charges take non-periodic input (no images of the sites): pass a per-atom "
+                                 "potential with its gradient and Hessian");
+    if (r.emb_potential && !r.emb_potential_grad)
+      return plan_reject(msg, n, "hvp: embedding: the tangent sweep needs potential_grad beside potential");
+    if (r.emb_potential && !r.emb_potential_hess)
+      return plan_reject(msg, n, "hvp: embedding: the tangent sweep needs potential_hess beside potential (zeros for a uniform field)");
+    if (!r.emb_potential && (r.emb_potential_grad || r.emb_potential_hess))
+      return plan_reject(msg, n, "hvp: embedding: potential_grad / potential_hess without potential");
+    if (r.emb_n_ext > 0 && !r.emb_mol_idx && r.n_mol > 1)
+      return plan_reject(msg, n, "hvp: embedding: ext_mol_idx == NULL is allowed with one molecule only (n_mol = %d)", r.n_mol);
+    if (r.coulomb == AIMNET_COULOMB_PME)
+      return plan_reject(msg, n, "hvp: embedding: the analytic tangent sweep does not cover particle-mesh Ewald");
+    if (!r.emb_scratch_ok)
+      return plan_reject(msg, n, "hvp: embedding: scratch missing or smaller than aimnet_embedding_tangent_scratch_bytes");
+  }
   if (r.nbmat || r.nbmat_lr || r.nbmat_d3)
     return plan_reject(msg, n, "%s: caller-supplied neighbour matrices are not read by the tangent sweep (it builds its own %s)", who,
                        hvp ? "lists" : "list");
@@ -93,6 +115,7 @@ struct TangentPlan {
   bool d3_block;            // the external DFT-D3 block (central difference of its gradient over all directions)
   bool want_species;        // species slots + present masks are formed (DFT-D3)
   bool bbox;                // non-periodic: bounding-box cell grid
+  bool embedding;           // the embedding's seeds join the Coulomb seeds (armed), and after the backward its site pass
 };
 
 inline TangentPlan tangent_plan(const TangentRequest& r) {
@@ -114,6 +137,7 @@ inline TangentPlan tangent_plan(const TangentRequest& r) {
   P.ewald_qtot = P.ewald && r.nq == 2;
   P.want_species = P.d3_block;
   P.bbox = !r.pbc && r.bbox_ok;
+  P.embedding = hvp && r.emb_on && r.emb_tangent;
   return P;
 }
 

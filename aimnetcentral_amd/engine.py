@@ -452,64 +452,84 @@ class HipEngine(capacity.Capacities):
         return res
 
     EMBEDDING_KEYS = ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "want_ext_forces", "want_ext_potential")
+    EMBEDDING_KEYS_HVP = EMBEDDING_KEYS + ("potential_hess", "want_ext_hv", "want_field")
+
+    def _embedding_arrays(self, who: str, emb: dict[str, Any], keys, n: int, n_mol: int, periodic: bool) -> dict[str, Any]:
+        """The checks `eval` and `hvp` share on an `embedding` dict: known keys, shapes, what goes with what.  Returns the device
+        arrays `ext_coord`, `ext_charge`, `ext_mol_idx`, `potential`, `potential_grad` (None where not given) and `m`, the number of
+        sites."""
+        import torch
+
+        who = f"HipEngine.{who}"
+        unknown = set(emb) - set(keys)
+        if unknown:
+            raise ValueError(f"{who}: unknown embedding keys {sorted(unknown)}")
+        dev, f32 = self.device, torch.float32
+        xc, qc, mi = emb.get("ext_coord"), emb.get("ext_charge"), emb.get("ext_mol_idx")
+        if (xc is None) != (qc is None):
+            raise ValueError(f"{who}: embedding point charges need both ext_coord and ext_charge")
+        m = 0
+        if xc is not None:
+            xc = torch.as_tensor(xc).to(device=dev, dtype=f32).contiguous()
+            qc = torch.as_tensor(qc).to(device=dev, dtype=f32).contiguous()
+            if xc.ndim != 2 or xc.shape[1] != 3 or tuple(qc.shape) != (xc.shape[0],):
+                raise ValueError(f"{who}: ext_coord must be [M, 3] and ext_charge [M], got {tuple(xc.shape)}, {tuple(qc.shape)}")
+            m = int(xc.shape[0])
+            if m and periodic:
+                raise ValueError(f"{who}: embedding point charges take non-periodic input; pass a per-atom potential with a cell")
+            if mi is not None:
+                mi = torch.as_tensor(mi).to(device=dev, dtype=torch.int32).contiguous()
+                if tuple(mi.shape) != (m,):
+                    raise ValueError(f"{who}: ext_mol_idx must have shape ({m},), got {tuple(mi.shape)}")
+            elif n_mol > 1 and m:
+                raise ValueError(f"{who}: embedding point charges of more than one molecule need ext_mol_idx")
+        elif mi is not None:
+            raise ValueError(f"{who}: ext_mol_idx given without ext_coord")
+        pot, pg = emb.get("potential"), emb.get("potential_grad")
+        if pot is not None:
+            pot = torch.as_tensor(pot).to(device=dev, dtype=f32).contiguous()
+            if tuple(pot.shape) != (n,):
+                raise ValueError(f"{who}: embedding potential must have shape ({n},), got {tuple(pot.shape)}")
+        if pg is not None:
+            if pot is None:
+                raise ValueError(f"{who}: embedding potential_grad given without potential")
+            pg = torch.as_tensor(pg).to(device=dev, dtype=f32).contiguous()
+            if tuple(pg.shape) != (n, 3):
+                raise ValueError(f"{who}: embedding potential_grad must have shape ({n}, 3), got {tuple(pg.shape)}")
+        return {"ext_coord": xc, "ext_charge": qc, "ext_mol_idx": mi, "potential": pot, "potential_grad": pg, "m": m}
+
+    def _embedding_scratch(self, attr: str, nbytes: int):
+        """One buffer per kind (`attr`), grown on demand, ordered like the workspace (_workspace)."""
+        import torch
+
+        scratch = getattr(self, attr, None)
+        if scratch is None or scratch.numel() < nbytes:
+            if scratch is not None and self._ws_stream is not None:
+                scratch.record_stream(self._ws_stream)
+            scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            setattr(self, attr, scratch)
+        return scratch
 
     def _eval_embedded(self, emb: dict[str, Any], kw: dict[str, Any]) -> dict[str, Any]:
         """`eval` with an embedding: check it, allocate its scratch and outputs, set it (aimnet_engine_set_embedding), evaluate,
         and switch it off again whatever happens."""
         import torch
 
-        unknown = set(emb) - set(self.EMBEDDING_KEYS)
-        if unknown:
-            raise ValueError(f"HipEngine.eval: unknown embedding keys {sorted(unknown)}")
-        if kw["stress"]:
+        if set(emb) <= set(self.EMBEDDING_KEYS) and kw["stress"]:  # (an unknown key is reported first, by the shared checks)
             raise ValueError("HipEngine.eval: the embedding term has no stress")
         dev, f32 = self.device, torch.float32
         n = int(kw["coord"].shape[0])
         n_mol = int(kw["charge"].shape[0]) if self.nq == 2 else int(kw["charge"].numel())
-        xc, qc, mi = emb.get("ext_coord"), emb.get("ext_charge"), emb.get("ext_mol_idx")
-        if (xc is None) != (qc is None):
-            raise ValueError("HipEngine.eval: embedding point charges need both ext_coord and ext_charge")
-        m = 0
-        if xc is not None:
-            xc = torch.as_tensor(xc).to(device=dev, dtype=f32).contiguous()
-            qc = torch.as_tensor(qc).to(device=dev, dtype=f32).contiguous()
-            if xc.ndim != 2 or xc.shape[1] != 3 or tuple(qc.shape) != (xc.shape[0],):
-                raise ValueError(f"HipEngine.eval: ext_coord must be [M, 3] and ext_charge [M], got {tuple(xc.shape)}, {tuple(qc.shape)}")
-            m = int(xc.shape[0])
-            if m and kw["cell"] is not None:
-                raise ValueError("HipEngine.eval: embedding point charges take non-periodic input; pass a per-atom potential with a cell")
-            if mi is not None:
-                mi = torch.as_tensor(mi).to(device=dev, dtype=torch.int32).contiguous()
-                if tuple(mi.shape) != (m,):
-                    raise ValueError(f"HipEngine.eval: ext_mol_idx must have shape ({m},), got {tuple(mi.shape)}")
-            elif n_mol > 1 and m:
-                raise ValueError("HipEngine.eval: embedding point charges of more than one molecule need ext_mol_idx")
-        elif mi is not None:
-            raise ValueError("HipEngine.eval: ext_mol_idx given without ext_coord")
-        pot, pg = emb.get("potential"), emb.get("potential_grad")
-        if pot is not None:
-            pot = torch.as_tensor(pot).to(device=dev, dtype=f32).contiguous()
-            if tuple(pot.shape) != (n,):
-                raise ValueError(f"HipEngine.eval: embedding potential must have shape ({n},), got {tuple(pot.shape)}")
-        if pg is not None:
-            if pot is None:
-                raise ValueError("HipEngine.eval: embedding potential_grad given without potential")
-            pg = torch.as_tensor(pg).to(device=dev, dtype=f32).contiguous()
-            if tuple(pg.shape) != (n, 3):
-                raise ValueError(f"HipEngine.eval: embedding potential_grad must have shape ({n}, 3), got {tuple(pg.shape)}")
-        elif pot is not None and kw["forces"]:
+        arr = self._embedding_arrays("eval", emb, self.EMBEDDING_KEYS, n, n_mol, kw["cell"] is not None)
+        xc, qc, mi, pot, pg, m = (arr[k] for k in ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "m"))
+        if pot is not None and pg is None and kw["forces"]:
             raise ValueError("HipEngine.eval: forces with an embedding potential need potential_grad")
         outs = {"embedding_energy": torch.empty(n_mol, dtype=torch.float64, device=dev)}
         if emb.get("want_ext_forces") and xc is not None:
             outs["ext_forces"] = torch.empty(m, 3, dtype=f32, device=dev)
         if emb.get("want_ext_potential") and xc is not None:
             outs["ext_potential"] = torch.empty(m, dtype=f32, device=dev)
-        nbytes = int(self.lib.aimnet_embedding_scratch_bytes(n, n_mol, m))
-        scratch = getattr(self, "_emb_scratch", None)  # one buffer, grown on demand, ordered like the workspace (_workspace)
-        if scratch is None or scratch.numel() < nbytes:
-            if scratch is not None and self._ws_stream is not None:
-                scratch.record_stream(self._ws_stream)
-            self._emb_scratch = scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        scratch = self._embedding_scratch("_emb_scratch", int(self.lib.aimnet_embedding_scratch_bytes(n, n_mol, m)))
         ptr = lambda v: v.data_ptr() if v is not None and v.numel() else None  # noqa: E731
         s = _lib.Embedding(n_ext=m, ext_coord=ptr(xc), ext_charge=ptr(qc), ext_mol_idx=ptr(mi), potential=ptr(pot), potential_grad=ptr(pg),
                            ext_forces=ptr(outs.get("ext_forces")), ext_potential=ptr(outs.get("ext_potential")),
@@ -534,13 +554,19 @@ class HipEngine(capacity.Capacities):
 
     def hvp(self, coord, numbers, mol_idx, charge, vectors, cell=None, pbc=(True, True, True), coulomb: str = "simple",
             dsf_rc: float = 15.0, dsf_alpha: float = 0.2, want_forces: bool = False,
-            dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6) -> dict[str, Any]:
+            dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6,
+            embedding: dict[str, Any] | None = None) -> dict[str, Any]:
         """Analytic Hessian-vector products (csrc/hvp.hip, aimnet_engine_hvp): vectors [K, N, 3] -> hv [K, N, 3] on the device
         (+ the forces of the same sweep with `want_forces`).  Inputs as `eval` (`pbc`: three flags or per-system [n_cell, 3]);
         with `dftd3` the dispersion block is added as a central difference of the D3 gradient inside the same call.  The K
         directions are processed in as many sweeps as the workspace budget asks for.  `coulomb`: "none", "simple", "dsf" or "ewald" (the exact structure-factor sum at
         `ewald_accuracy`, periodic cells only; `dsf_rc` / `dsf_alpha` are not read with it); "pme" raises - its tangent is not
-        carried, AIMNet2Calculator takes differences of forces there."""
+        carried, AIMNet2Calculator takes differences of forces there.
+        `embedding`: the dict of `eval`, carried through the sweep with the atoms moving and the sites clamped
+        (include/aimnet_hip.h, aimnet_embedding_tangent): a `potential` needs `potential_grad` and `potential_hess` [N,6] (xx, yy,
+        zz, xy, xz, yz) or [N,3,3] beside it (zeros for a uniform field).  hv and the forces then include the term; `want_ext_hv`
+        adds `ext_hv` [K, M, 3], the mixed atom-site block applied to the directions, `want_field` adds `ext_field` [N, 10] (phi,
+        grad phi, grad grad phi as the sweep used them, float64)."""
         import torch
 
         inp, t = self._inputs("hvp", coord, numbers, mol_idx, charge, cell, pbc)
@@ -575,12 +601,64 @@ class HipEngine(capacity.Capacities):
         hv = torch.empty_like(vectors)
         f_out = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_forces else None
 
+        arm, outs = (lambda k0, kc: None), {}
+        if embedding is not None:
+            arm, outs = self._hvp_embedding(embedding, n, n_mol, K, cell is not None)
+
         def call(opt, k0, kc, *tail):
+            arm(k0, kc)  # (the embedding's tangent struct names this sweep's slice of ext_hv)
             return self.lib.aimnet_engine_hvp(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
                                               hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None, *tail)
         kmax = self.HVP_MAX_DIRECTIONS // (4 if dftd3 is not None else 1)  # grid.y limit of the tangent kernels
-        self._tangent_sweeps("hvp", self.lib.aimnet_engine_hvp_workspace_bytes, rq, K, kmax, call)
-        return {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}
+        try:
+            self._tangent_sweeps("hvp", self.lib.aimnet_engine_hvp_workspace_bytes, rq, K, kmax, call)
+        finally:
+            if embedding is not None:
+                self.lib.aimnet_engine_set_embedding(self._h, None)  # (disarms the tangent too)
+        res = {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}
+        res.update(outs)
+        return res
+
+    def _hvp_embedding(self, emb: dict[str, Any], n: int, n_mol: int, K: int, periodic: bool):
+        """`hvp` with an embedding: the checks of `eval` (_embedding_arrays) and those of the tangent, the scratches and outputs; sets
+        the embedding and returns (`arm`, outputs) - `arm(k0, kc)` arms the sweep of the directions [k0, k0 + kc)
+        (aimnet_engine_set_embedding_tangent).  The caller switches the embedding off again."""
+        import torch
+
+        dev, f32 = self.device, torch.float32
+        arr = self._embedding_arrays("hvp", emb, self.EMBEDDING_KEYS_HVP, n, n_mol, periodic)
+        xc, qc, mi, pot, pg, m = (arr[k] for k in ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "m"))
+        ph = emb.get("potential_hess")
+        if pot is not None and (pg is None or ph is None):
+            raise ValueError("HipEngine.hvp: an embedding potential needs potential_grad and potential_hess (zeros for a uniform field)")
+        if ph is not None:
+            if pot is None:
+                raise ValueError("HipEngine.hvp: embedding potential_hess given without potential")
+            ph = torch.as_tensor(ph).to(device=dev, dtype=f32)
+            if tuple(ph.shape) == (n, 3, 3):
+                ph = torch.stack([ph[:, 0, 0], ph[:, 1, 1], ph[:, 2, 2], ph[:, 0, 1], ph[:, 0, 2], ph[:, 1, 2]], dim=1)
+            if tuple(ph.shape) != (n, 6):
+                raise ValueError(f"HipEngine.hvp: embedding potential_hess must have shape ({n}, 6) or ({n}, 3, 3), got {tuple(ph.shape)}")
+            ph = ph.contiguous()
+        outs = {}
+        if emb.get("want_ext_hv") and xc is not None:
+            outs["ext_hv"] = torch.empty(K, m, 3, dtype=f32, device=dev)
+        if emb.get("want_field"):
+            outs["ext_field"] = torch.empty(n, 10, dtype=torch.float64, device=dev)
+        scratch = self._embedding_scratch("_emb_scratch", int(self.lib.aimnet_embedding_scratch_bytes(n, n_mol, m)))
+        tscratch = self._embedding_scratch("_emb_tangent_scratch", int(self.lib.aimnet_embedding_tangent_scratch_bytes(n, n_mol, m)))
+        ptr = lambda v: v.data_ptr() if v is not None and v.numel() else None  # noqa: E731
+        s = _lib.Embedding(n_ext=m, ext_coord=ptr(xc), ext_charge=ptr(qc), ext_mol_idx=ptr(mi), potential=ptr(pot), potential_grad=ptr(pg),
+                           scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
+        keep = (xc, qc, mi, pot, pg, ph)  # (the arrays the structs point into live as long as `arm` does)
+        _lib.check(self.lib.aimnet_engine_set_embedding(self._h, C.byref(s)), "aimnet_engine_set_embedding")
+
+        def arm(k0: int, kc: int, keep=keep) -> None:
+            ext_hv = outs.get("ext_hv")
+            ts = _lib.EmbeddingTangent(potential_hess=ptr(ph), ext_hv=ptr(ext_hv[k0 : k0 + kc]) if ext_hv is not None else None,
+                                       field=ptr(outs.get("ext_field")), scratch=tscratch.data_ptr(), scratch_bytes=tscratch.numel())
+            _lib.check(self.lib.aimnet_engine_set_embedding_tangent(self._h, C.byref(ts)), "aimnet_engine_set_embedding_tangent")
+        return arm, outs
 
     def _tangent_sweeps(self, name: str, ws_bytes_fn, rq: capacity.Request, K: int, kmax: int, call) -> None:
         """The K directions of `hvp` / `charge_response` (`name`) in sweeps of at most `kmax`, and of as many as HVP_BYTES_BUDGET

@@ -256,7 +256,8 @@ int aimnet_engine_set_dd(aimnet_engine* e, const float* owned, aimnet_dd_exchang
  * workspace.  Pair terms are fp32, all sums fp64 in a fixed order without atomics: results are bitwise repeatable.
  * The struct is copied; every pointer must stay valid while evaluations run.  emb == NULL switches the mode off, and with it off
  * aimnet_engine_eval launches exactly what it launched before.  While it is on: AIMNET_STRESS, domain decomposition and
- * aimnet_engine_hvp are rejected (the term is carried by neither), aimnet_engine_charge_response ignores it (the charges do not
+ * aimnet_engine_hvp are rejected (the term is carried by neither; aimnet_engine_hvp carries it once
+ * aimnet_engine_set_embedding_tangent has armed it, below), aimnet_engine_charge_response ignores it (the charges do not
  * see the field).  status[6] bit 7 (128): ext_mol_idx holds an entry outside [0, n_mol) or is not sorted (the kernels index
  * through clamped copies; the results are meaningless). */
 typedef struct aimnet_embedding {
@@ -274,6 +275,38 @@ typedef struct aimnet_embedding {
 } aimnet_embedding;
 size_t aimnet_embedding_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext);
 int aimnet_engine_set_embedding(aimnet_engine* e, const aimnet_embedding* emb);
+
+/* The embedding in the analytic Hessian sweep (atoms move along v, sites are clamped).  Arming is explicit: with only
+ * aimnet_engine_set_embedding called, aimnet_engine_hvp refuses as before; after aimnet_engine_set_embedding_tangent it carries the
+ * term.  With g = grad phi and T = grad grad phi = k_e sum_A Q_A (3 r r^T / d^5 - 1 / d^3) + potential_hess (r = x_i - X_A), the
+ * sweep's seeds take   qbar_i += phi_i, xbar_i += q_i g_i   (as aimnet_engine_eval) and, per direction k,
+ *   t_qbar_i += g_i . v_i        t_xbar_i += t_q_i g_i + q_i T_i v_i ,
+ * q / t_q the total charge and its tangent; the backward sweep does the rest.  hv and the sweep's forces then include the term.
+ * Stages inside aimnet_engine_hvp: site lists (n_ext > 0), ONE field pass with T per call whatever n_vec is, the seed kernel, and
+ * after the backward sweep the site pass for ext_hv.
+ *   potential_hess [n_atoms][6] in V / A^2, components xx, yy, zz, xy, xz, yz: required beside aimnet_embedding.potential (zeros
+ *                  for a uniform field), as is potential_grad; NULL without a potential.
+ *   ext_hv         [n_vec][n_ext][3] or NULL: the mixed block, ext_hv[k][A] = sum_i (d2 E_emb / dX_A dx_i) v_i^k in eV / A^2, the
+ *                  directional derivative of -ext_forces with the charge response included (by symmetry also the block that gives
+ *                  the atom forces under site displacements).  A caller that splits its directions over several calls arms again
+ *                  with the slice of each call.
+ *   field          [n_atoms][10] doubles or NULL: phi, g (3), T (6) as the sweep used them (k_e and the caller's arrays included).
+ *   scratch        device memory of at least aimnet_embedding_tangent_scratch_bytes(n_atoms, n_mol, n_ext) bytes; the scratch of
+ *                  aimnet_embedding is not touched by the sweep.
+ * Rejected by aimnet_engine_hvp while armed: point charges with a cell, a potential without potential_grad or potential_hess,
+ * AIMNET_COULOMB_PME, a missing or short scratch.  Not carried: polarisation of the charges by the field, the site-site block,
+ * periodic images of sites.  aimnet_engine_eval and aimnet_engine_charge_response do not read this struct.  Pair terms fp32 (those of T in
+ * double: a component of 3 r r^T / d^5 - 1 / d^3 collects too many fp32 roundings), sums fp64 in fixed orders, no atomics: hv and ext_hv are bitwise repeatable and independent of how the directions are split into calls.
+ * t == NULL disarms; aimnet_engine_set_embedding (with a struct or with NULL) disarms too.  The struct is copied. */
+typedef struct aimnet_embedding_tangent {
+  const float* potential_hess;
+  float* ext_hv;
+  double* field;
+  void* scratch;
+  size_t scratch_bytes;
+} aimnet_embedding_tangent;
+size_t aimnet_embedding_tangent_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext);
+int aimnet_engine_set_embedding_tangent(aimnet_engine* e, const aimnet_embedding_tangent* t);
 
 /* Bytes of scratch `aimnet_engine_eval` needs for the given problem size. */
 size_t aimnet_engine_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_cell,
