@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "aimnet_debug_gemm_h2",
     "aimnet_engine_debug_mlp_sweep",
     "aimnet_debug_pme_recip",
+    "aimnet_debug_pme_tangent",
     "aimnet_debug_conv_fwd",
     "aimnet_debug_unconcat",
     "aimnet_debug_conv_bwd",
@@ -59,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_set_embedding",
     "aimnet_embedding_tangent_scratch_bytes",
     "aimnet_engine_set_embedding_tangent",
+    "aimnet_engine_set_pme_tangent",
     "aimnet_neighbor_list",
     "aimnet_neighbor_list_workspace_bytes",
     "aimnet_conv_sv_2d_sp_fwd",
@@ -289,6 +291,11 @@ def load() -> C.CDLL:
                                                   C.POINTER(vp), C.POINTER(C.c_int), vp]
     lib.aimnet_debug_pme_recip.restype = C.c_int
     lib.aimnet_debug_pme_recip.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_double), vp]
+    lib.aimnet_debug_pme_tangent.restype = C.c_int
+    lib.aimnet_debug_pme_tangent.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp,
+                                             C.POINTER(C.c_double), vp]
+    lib.aimnet_engine_set_pme_tangent.restype = C.c_int
+    lib.aimnet_engine_set_pme_tangent.argtypes = [vp, C.c_int32]
     # the conv kernels one launch at a time (tests/test_gpu_conv_kernels.py); `shifts` is a host pointer
     ci, cf = C.c_int, C.c_float
     lib.aimnet_debug_conv_fwd.restype = C.c_int

@@ -20,7 +20,8 @@ Deliberate deviations, all loud:
   * hessian=True and hessian_vector_product run the analytic tangent sweep of csrc/hvp.hip (forward-mode through the
     forward and backward sweep, all directions at once; `hvp_method`), not autograd double backward: exact second derivatives
     at fp32 round-off (the external DFT-D3 block: a central difference of the D3 gradient alone, inside the same call), for
-    every Coulomb method but "pme" - the exact Ewald sum is carried by the sweep, the mesh takes differences of forces.  The
+    every Coulomb method but "pme" - the exact Ewald sum is carried by the sweep, the mesh takes differences of forces unless
+    set_pme_hessian("analytic") arms its tangent.  The
     finite-difference operator over the analytic forces (`_fd_hvp`, `hvp_method = "fd"`) is kept as the cross-check;
     create_graph=True raises (there is no autograd graph);
   * `charge_response` and `dipole_derivatives` (d q / d x and d mu / d x from the forward half of that sweep) have no reference
@@ -825,8 +826,19 @@ class AIMNet2Calculator:
     # with an external DFT-D3 term its block is a central difference of the D3 gradient alone inside the same call (smooth, ~1 % of
     # the curvature: ~1e-6 eV/A^2);  "fd": the central-difference operator over the analytic forces (`_fd_hvp`), the independent
     # cross-check.  The sweep carries "simple", DSF and the exact Ewald sum ("ewald": real space on a list, structure factors and
-    # their tangents in double); "pme" always takes the finite-difference operator.
+    # their tangents in double); "pme" takes the finite-difference operator unless set_pme_hessian("analytic") armed the mesh tangent
+    # of csrc/pme.hip (opt-in: its workspace grows by 40 bytes per mesh point and direction).
     hvp_method = "analytic"
+    _pme_hessian = None
+
+    def set_pme_hessian(self, mode: str | None = None) -> None:
+        """How second derivatives are taken with set_lrcoulomb_method("pme"): None (default) - differences of the analytic forces,
+        four force evaluations per direction; "analytic" - the tangent sweep carries the mesh (HipEngine.hvp(..., pme_tangent=True)),
+        as it carries the exact Ewald sum.  Read by hessian_vector_product, eval(hessian=True) and AIMNet2ASE.get_hessian() while
+        `hvp_method` is "analytic"; an electrostatic embedding together with "pme" keeps raising NotImplementedError."""
+        if mode not in (None, "analytic"):
+            raise ValueError(f"set_pme_hessian: mode must be None or 'analytic', got {mode!r}")
+        self._pme_hessian = mode
 
     def _hvp(self, d: dict[str, Any], dirs, eps: float | None = None, emb: dict[str, Any] | None = None, extra: dict | None = None):
         """H @ v for K directions (K,N,3) of one structure: analytic tangent sweep, or finite differences (see `hvp_method`).
@@ -840,14 +852,16 @@ class AIMNet2Calculator:
         lr = self._long_range(cell)
         lr.require_cell()
         pbc3 = self._normalize_pbc(d.get("pbc"), 1)
-        if self.hvp_method == "fd" or lr.method == "pme":
+        mesh_sweep = lr.method == "pme" and self._pme_hessian == "analytic"
+        if self.hvp_method == "fd" or (lr.method == "pme" and not mesh_sweep):
             # particle-mesh Ewald: differences of the analytic forces (what the reference does for its PME block, lr.py:903-926);
-            # the tangent sweep of csrc/hvp.hip carries the pair-wise Coulomb methods and the exact Ewald sum, not the mesh
+            # the tangent sweep of csrc/hvp.hip carries the pair-wise Coulomb methods and the exact Ewald sum, and the mesh only
+            # when set_pme_hessian("analytic") armed it
             return self._fd_hvp(d, dirs, lr, pbc3, eps)
         n = d["coord"].shape[0]
         res = self.engine.hvp(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
                               self._engine_charge(d["charge"], d.get("mult")), dirs, cell=cell, pbc=pbc3, **lr.kwargs(),
-                              **({"embedding": emb} if emb is not None else {}))
+                              **({"embedding": emb} if emb is not None else {}), **({"pme_tangent": True} if mesh_sweep else {}))
         if extra is not None and "ext_hv" in res:
             extra["ext_hv"] = res["ext_hv"]
         return res["hv"]

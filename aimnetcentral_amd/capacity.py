@@ -13,6 +13,7 @@ from . import _lib
 
 EWALD_METHODS = (_lib.COULOMB_EWALD, _lib.COULOMB_PME)
 PME_START_MESH = 8192  # starting capacity of one system's PME mesh (points)
+PME_RC_MAX = 10.0  # Angstrom: cap of the mesh method's real-space cutoff (csrc/pme.hip)
 
 
 def round16(n: int) -> int:
@@ -137,6 +138,8 @@ class Capacities:
                 # r_c changes with every cell, atom count and accuracy: ONE capacity of its own (as _ewald_max_k for the k entries),
                 # not a key per cutoff in _max_nb_lr; it only grows (an overflow repeats the sweep)
                 self._ewald_nb_lr = opt.max_nb_lr = max(self._ewald_nb_lr, start_capacity(rq.lr_rc))
+                if rq.method == _lib.COULOMB_PME:  # the armed mesh tangent: every (direction, system) slice has this many points
+                    opt.pme_max_mesh = self._pme_max_mesh
             else:
                 # the mesh workspace is n_mol slices of the LARGEST system's mesh this engine has seen (40 B per point): after one big
                 # cell, a batch of many small ones would ask for n_mol x that.  Shrink to the starting capacity once per call (status[7]
@@ -169,7 +172,7 @@ class Capacities:
         call has to be repeated)."""
         if st[2]:
             self.max_nb = grown(self.max_nb, st[0])
-        if st[3] and rq.kind == "hvp" and rq.method == _lib.COULOMB_EWALD:
+        if st[3] and rq.kind == "hvp" and rq.method in EWALD_METHODS:
             self._ewald_nb_lr = grown(opt.max_nb_lr, st[1])
         elif st[3]:
             self._max_nb_lr[rq.lr_rc] = grown(opt.max_nb_lr, st[1])

@@ -175,6 +175,8 @@ struct aimnet_engine {
   // aimnet_engine_set_embedding_tangent: aimnet_engine_hvp carries the embedding (hvp.hip, Tangent::embedding_seeds); off with emb_on
   bool emb_tangent_on = false;
   aimnet_embedding_tangent emb_tangent{};
+  // aimnet_engine_set_pme_tangent: aimnet_engine_hvp carries AIMNET_COULOMB_PME (tangent_plan.h: pme); off: it refuses, as it always has
+  bool pme_tangent_on = false;
   float* unit_cell = nullptr;  // 3 x 3 identity (device): "cell" of the virial sums of a decomposed evaluation
   double* sae;
   // species slots of the pass-0 moment backward: slot = rank of the atomic number among the embedding rows that

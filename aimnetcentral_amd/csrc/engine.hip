@@ -1264,6 +1264,12 @@ int aimnet_engine_set_embedding_tangent(aimnet_engine* e, const aimnet_embedding
   return AIMNET_OK;
 }
 
+int aimnet_engine_set_pme_tangent(aimnet_engine* e, int32_t on) {
+  if (!e) return AIMNET_E_INVALID;
+  e->pme_tangent_on = on != 0;
+  return AIMNET_OK;
+}
+
 int aimnet_engine_set_dftd3(aimnet_engine* e, const aimnet_dftd3_tables* t) {
   if (!e || !t || t->n_z <= 0 || !t->c6ab || !t->cn_ref || !t->rcov || !t->r4r2) {
     set_last_error("set_dftd3: null argument");
@@ -1565,6 +1571,77 @@ done:
   (void)hipStreamSynchronize(st);
   (void)hipFree(b.sys); (void)hipFree(b.frac); (void)hipFree(b.meshq); (void)hipFree(b.ma); (void)hipFree(b.mb); (void)hipFree(b.bmod);
   (void)hipFree(b.vpart); (void)hipFree(mol_idx); (void)hipFree(mol_start); (void)hipFree(status); (void)hipFree(charge);
+  return rc;
+}
+
+int aimnet_debug_pme_tangent(const float* xw, const float* q, const float* tq, const float* v, const int* order, const float* cell,
+                             float total_charge, int n_atoms, int n_dir, float accuracy, int max_mesh, double* field, double* tphi,
+                             double* tg, double* host_info, void* hip_stream) {
+  using namespace aimnet;
+  if (!xw || !q || !tq || !v || !cell || !field || !tphi || !tg || !host_info || n_atoms <= 0 || n_atoms >= (1 << 21) || n_dir <= 0 ||
+      n_dir > 65535 || max_mesh < 512)
+    return AIMNET_E_INVALID;
+  hipStream_t st = (hipStream_t)hip_stream;
+  EwaldBuffers b{};
+  PmeTangentBuffers t{};
+  b.max_mesh = max_mesh;
+  b.max_parts = ceil_div(max_mesh, PME_PART);
+  const size_t mm = (size_t)max_mesh, tm = mm * (size_t)n_dir;
+  int *mol_idx = nullptr, *mol_start = nullptr, *status = nullptr;
+  float* charge = nullptr;
+  const int ms[2] = {0, n_atoms};
+  std::vector<double> scales((size_t)n_dir);
+  int rc = 0;
+#define PME_DBG(x)            \
+  if ((x) != hipSuccess) {    \
+    rc = AIMNET_E_HIP;        \
+    goto done;                \
+  }
+  PME_DBG(hipMalloc(&b.sys, sizeof(EwaldSystem)));
+  PME_DBG(hipMalloc(&b.meshq, sizeof(long long) * mm));
+  PME_DBG(hipMalloc(&b.ma, sizeof(double) * 2 * mm));
+  PME_DBG(hipMalloc(&b.mb, sizeof(double) * 2 * mm));
+  PME_DBG(hipMalloc(&b.bmod, sizeof(double) * 3 * PME_MAX_AXIS));
+  PME_DBG(hipMalloc(&b.vpart, sizeof(double) * 8 * (size_t)b.max_parts));
+  PME_DBG(hipMalloc(&t.tmeshq, sizeof(long long) * tm));
+  PME_DBG(hipMalloc(&t.tma, sizeof(double) * 2 * tm));
+  PME_DBG(hipMalloc(&t.tmb, sizeof(double) * 2 * tm));
+  PME_DBG(hipMalloc(&t.sys_rep, sizeof(EwaldSystem) * (size_t)n_dir));
+  PME_DBG(hipMalloc(&t.tscale, sizeof(double) * (size_t)n_dir));
+  PME_DBG(hipMalloc(&mol_idx, sizeof(int) * n_atoms));
+  PME_DBG(hipMalloc(&mol_start, sizeof(int) * 2));
+  PME_DBG(hipMalloc(&status, sizeof(int)));
+  PME_DBG(hipMalloc(&charge, sizeof(float)));
+  t.field = field;
+  PME_DBG(hipMemsetAsync(mol_idx, 0, sizeof(int) * n_atoms, st));
+  PME_DBG(hipMemsetAsync(tphi, 0, sizeof(double) * (size_t)n_dir * n_atoms, st));
+  PME_DBG(hipMemsetAsync(tg, 0, sizeof(double) * 3 * (size_t)n_dir * n_atoms, st));
+  PME_DBG(hipMemcpyAsync(mol_start, ms, sizeof(ms), hipMemcpyHostToDevice, st));
+  PME_DBG(hipMemcpyAsync(charge, &total_charge, sizeof(float), hipMemcpyHostToDevice, st));
+  rc = launch_pme_setup(st, cell, 1, mol_start, charge, 1, 1, accuracy, b, status);
+  if (!rc) rc = launch_pme_potential(st, xw, q, mol_idx, order, n_atoms, 1, b);
+  if (!rc) rc = launch_pme_field(st, xw, mol_idx, n_atoms, b, field);
+  if (!rc)
+    rc = launch_pme_tangent(st, xw, q, tq, 1, v, mol_idx, order, n_atoms, 1, n_dir, b, t, 1.0f, nullptr, nullptr, nullptr, nullptr, tphi,
+                            tg);
+  if (!rc) {
+    EwaldSystem E;
+    int need = 0;
+    PME_DBG(hipMemcpyAsync(&E, b.sys, sizeof(E), hipMemcpyDeviceToHost, st));
+    PME_DBG(hipMemcpyAsync(&need, status, sizeof(int), hipMemcpyDeviceToHost, st));
+    PME_DBG(hipMemcpyAsync(scales.data(), t.tscale, sizeof(double) * (size_t)n_dir, hipMemcpyDeviceToHost, st));
+    PME_DBG(hipStreamSynchronize(st));
+    double smax = scales[0];
+    for (double sk : scales) smax = sk > smax ? sk : smax;
+    host_info[0] = E.alpha; host_info[1] = E.rc; host_info[2] = E.mesh[0]; host_info[3] = E.mesh[1]; host_info[4] = E.mesh[2];
+    host_info[5] = need; host_info[6] = E.phi_bg; host_info[7] = 1099511627776.0 / smax;
+  }
+done:
+#undef PME_DBG
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(b.sys); (void)hipFree(b.meshq); (void)hipFree(b.ma); (void)hipFree(b.mb); (void)hipFree(b.bmod); (void)hipFree(b.vpart);
+  (void)hipFree(t.tmeshq); (void)hipFree(t.tma); (void)hipFree(t.tmb); (void)hipFree(t.sys_rep); (void)hipFree(t.tscale);
+  (void)hipFree(mol_idx); (void)hipFree(mol_start); (void)hipFree(status); (void)hipFree(charge);
   return rc;
 }
 

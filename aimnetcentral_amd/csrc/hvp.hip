@@ -877,6 +877,7 @@ struct HvpWs {
   EwaldBuffers ew;  // Ewald summation: per-system parameters, fractional coordinates, k entries (ewald.hip)
   double* ew_tk;    // [K][max_k][2] tangent structure factors (t_P, t_Q)
   float* qsum;      // [N] alpha + beta of every atom: for the structure factors of a two-channel model, and for crs_dipole_kernel
+  PmeTangentBuffers pt;  // particle-mesh Ewald (plan: pme): the per-direction meshes and the field rows (pme.hip); W.ew holds the primal's
   // external DFT-D3 block (4 K displaced copies as one batch)
   int *d3_idx, *d3_shift, *d3_cnt, *aslot, *d3c_idx, *d3c_shift, *d3c_cnt, *d3c_mol, *d3c_aslot;
   unsigned long long* present_part;
@@ -967,6 +968,21 @@ void tangent_layout(const aimnet_engine* e, int N, int n_mol, int K, const Tange
     W.ew.k = c.take<EwaldK>((size_t)P.ewald_max_k);
     W.ew_tk = c.take<double>(2 * (size_t)K * P.ewald_max_k);
     W.qsum = c.take<float>(P.ewald_qtot ? n : 0);
+    if (P.pme) {  // the mesh buffers of aimnet_engine_eval + per direction and system 40 bytes per mesh point, and the field rows
+      const size_t mm = (size_t)P.pme_max_mesh, mesh_all = mm * (size_t)n_mol, tmesh_all = mesh_all * (size_t)K;
+      W.ew.max_mesh = P.pme_max_mesh, W.ew.max_parts = P.pme_max_parts;
+      W.ew.sys = c.take<EwaldSystem>((size_t)n_mol);
+      W.ew.meshq = c.take<long long>(mesh_all);
+      W.ew.ma = c.take<double>(2 * mesh_all), W.ew.mb = c.take<double>(2 * mesh_all);
+      W.ew.bmod = c.take<double>((size_t)n_mol * 3 * PME_MAX_AXIS);
+      W.ew.vpart = c.take<double>((size_t)n_mol * P.pme_max_parts * 8);
+      W.pt.tmeshq = c.take<long long>(tmesh_all);
+      W.pt.tma = c.take<double>(2 * tmesh_all), W.pt.tmb = c.take<double>(2 * tmesh_all);
+      W.pt.sys_rep = c.take<EwaldSystem>((size_t)K * n_mol);
+      W.pt.tscale = c.take<double>((size_t)K);
+      W.pt.field = c.take<double>(n * 10);
+      if (P.pme_qtot) W.qsum = c.take<float>(n);
+    }
     if (P.d3_block) {
       const size_t cn = 4 * kn, cap_d3 = (size_t)P.cap_d3;
       W.d3_idx = c.take<int>(n * cap_d3), W.d3_shift = c.take<int>(n * cap_d3), W.d3_cnt = c.take<int>(n);
@@ -1163,6 +1179,8 @@ int Tangent::lists() {
   if (P.bbox) RC(launch_bbox(s, n_mol, W.nl));
   RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, rc, rc, P.cap, N, 0, W.nl, W.nb_idx, W.nb_shift, W.nb_cnt,
                   status + 0, status + 2, W.pg));
+  if (P.pme)  // per-system (alpha, rc, mesh) from the cell, the primal charge mesh zeroed, the spline moduli; status[7] = mesh points needed
+    RC(launch_pme_setup(s, in->cell, n_cell, W.nl.mol_start, in->charge, nq, n_mol, opt->ewald_accuracy, W.ew, status + 7));
   if (P.lr_list)
     RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->dsf_rc, -1.0f, P.cap_lr, N, 0, W.nl, W.lr_idx, W.lr_shift,
                     W.lr_cnt, status + 1, status + 3));
@@ -1200,6 +1218,21 @@ int Tangent::coulomb_seeds() {
     RC(launch_ewald_sfac(s, q_tot, W.nl.mol_start, n_mol, W.ew));
     RC(launch_ewald_tangent(s, q_tot, tq_fin, nq, vectors, mol_c, W.nl.mol_start, N, n_mol, K, W.ew, W.ew_tk, cp.factor, W.qbar[qb],
                             W.tqbar[qb], W.xbar, W.txbar));
+  }
+  if (P.pme) {  // the same real-space term with the (alpha, rc) pme_setup filled, then the mesh and its tangents (pme.hip)
+    cp.ewald = W.ew.sys;
+    long_range(std::integral_constant<LrMode, LrMode::Ewald>{});
+    AIMNET_LAUNCH_CHECK();
+    const float* q_tot = q_fin;
+    if (P.pme_qtot) {  // the mesh sees alpha + beta
+      hipLaunchKernelGGL(hvp_qtot_kernel, grid1((size_t)N), b256, 0, s, q_fin, N, W.qsum);
+      AIMNET_LAUNCH_CHECK();
+      q_tot = W.qsum;
+    }
+    RC(launch_pme_potential(s, W.nl.xw, q_tot, mol_c, nullptr, N, n_mol, W.ew));
+    RC(launch_pme_field(s, W.nl.xw, mol_c, N, W.ew, W.pt.field));  // once per call, whatever K is
+    RC(launch_pme_tangent(s, W.nl.xw, q_tot, tq_fin, nq, vectors, mol_c, nullptr, N, n_mol, K, W.ew, W.pt, cp.factor, W.qbar[qb],
+                          W.tqbar[qb], W.xbar, W.txbar, nullptr, nullptr));
   }
   return 0;
 }
@@ -1338,9 +1371,12 @@ TangentRequest tangent_request(TangentEntry entry, const aimnet_engine* e, int N
     r.emb_potential_hess = mt.potential_hess != nullptr; r.emb_mol_idx = m.ext_mol_idx != nullptr;
     r.emb_scratch_ok = mt.scratch && m.n_ext >= 0 && mt.scratch_bytes >= aimnet_embedding_tangent_scratch_bytes(N, n_mol, m.n_ext);
   }
+  r.pme_tangent = entry == TangentEntry::Hvp && e->pme_tangent_on;
+  r.pme_max_mesh = opt->pme_max_mesh; r.pme_part = PME_PART;
   if (!in) return r;
   r.pbc = in->cell != nullptr; r.n_cell = in->n_cell;
-  r.ewald_args = entry == TangentEntry::Hvp && opt->coulomb == AIMNET_COULOMB_EWALD ? ewald_args_check(in, opt) : 0;
+  const bool mesh_armed = opt->coulomb == AIMNET_COULOMB_PME && r.pme_tangent;
+  r.ewald_args = entry == TangentEntry::Hvp && (opt->coulomb == AIMNET_COULOMB_EWALD || mesh_armed) ? ewald_args_check(in, opt) : 0;
   r.arrays = in->coord && in->numbers && in->mol_idx && in->charge;
   r.nbmat = in->nbmat != nullptr; r.nbmat_lr = in->nbmat_lr != nullptr; r.nbmat_d3 = in->nbmat_d3 != nullptr;
   return r;

@@ -347,6 +347,25 @@ int launch_pme_setup(hipStream_t s, const float* cell, int n_cell, const int* mo
 // order: the engine's bin order of the atoms (a permutation of 0 .. n_atoms-1) or NULL - the charge assignment groups atoms by it
 int launch_pme_recip(hipStream_t s, bool grad, bool stress, const float* xw, const float* q, const int* mol_idx, const int* mol_start,
                      const int* order, int n_atoms, int n_mol, const EwaldBuffers& b, float factor, double* ecoul, float* qbar, float* fgrad, float* virial_atom);
+// ---- pme.hip: the mesh in the tangent sweep (hvp.hip; armed by aimnet_engine_set_pme_tangent) ------------------------------
+struct PmeTangentBuffers {  // 40 bytes per mesh point, direction and system + the per-atom field rows
+  long long* tmeshq;   // [n_dir][n_mol][max_mesh] tangent charge meshes (2^-40 fixed point of the normalised direction), later tpot
+  double* tma;         // [n_dir][n_mol][max_mesh][2] work meshes of the transforms
+  double* tmb;
+  EwaldSystem* sys_rep;  // [n_dir][n_mol] the systems' parameters once per direction: pme_dft_kernel's slice index is grid.y
+  double* tscale;      // [n_dir] s_k: the power of two a direction is normalised by
+  double* field;       // [n_atoms][10] phi, g, T (xx yy zz xy xz yz) of the primal potential mesh, without the background
+};
+// the first nine launches of launch_pme_recip: the potential mesh in b.meshq; then phi, g, T of every atom from it, once per call
+int launch_pme_potential(hipStream_t s, const float* xw, const float* q, const int* mol_idx, const int* order, int n_atoms, int n_mol,
+                         const EwaldBuffers& b);
+int launch_pme_field(hipStream_t s, const float* xw, const int* mol_idx, int n_atoms, const EwaldBuffers& b, double* field);
+// after the two: the mesh tangents of n_dir directions, ADDED onto the seeds in launch_ewald_tangent's layouts and conventions
+// (q [n_atoms]: total charges).  No atomics on results.  dbg_tphi / dbg_tg != NULL: [n_dir][n_atoms] / [n_dir][n_atoms][3] doubles
+// instead of the seeds (aimnet_debug_pme_tangent).  n_dir n_mol <= 65 535.
+int launch_pme_tangent(hipStream_t s, const float* xw, const float* q, const float* tq, int nq, const float* tv, const int* mol_idx,
+                       const int* order, int n_atoms, int n_mol, int n_dir, const EwaldBuffers& b, const PmeTangentBuffers& t,
+                       float factor, float* qbar, float* tqbar, float* xbar, float* txbar, double* dbg_tphi, double* dbg_tg);
 // reciprocal-space sum + neutralising background, ACCUMULATED onto the per-atom energies / adjoints the pair kernels have stored
 int launch_ewald_recip(hipStream_t s, bool grad, bool stress, const float* q, const int* mol_idx, const int* mol_start, int n_atoms,
                        int n_mol, const EwaldBuffers& b, float factor, double* ecoul, float* qbar, float* fgrad, float* virial_atom);

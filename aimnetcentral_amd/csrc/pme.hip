@@ -15,6 +15,10 @@
 // below accuracy x the rms reciprocal force (tests/tools/pme_calibrate.py).  Everything is decided on the device from the cell (no
 // host round trip, NPT-safe); the host only provides the mesh capacity and grows it when status[7] says so.
 //
+// Second derivatives: the tangent stages at the end of this file carry the mesh through the Hessian-vector sweep of hvp.hip when
+// aimnet_engine_set_pme_tangent armed it (off by default: the sweep then refuses the method and the calculator takes differences of
+// forces, as before).  They add kernels; the ones aimnet_engine_eval launches are untouched.
+//
 // Launches per evaluation: setup (+ mesh clear + spline moduli) in front of the walk; assignment, 3 + 3 axis transforms around the
 // influence function, interpolation behind it: 10.
 //
@@ -491,6 +495,379 @@ __global__ __launch_bounds__(256) void pme_gather_kernel(const float* __restrict
   }
 }
 
+// ---- tangents for the Hessian-vector sweep (hvp.hip; armed by aimnet_engine_set_pme_tangent) ---------------------------------------
+// The cell is fixed; the atoms move along v^k, the total charges along t_q^k.  With theta_i the spline product of atom i and G the
+// linear, cell-only map charge mesh -> potential mesh (the three forward axis transforms, the influence function, the three inverse):
+//   primal    Q = sum_i q_i theta_i            pot = G Q          phi_i = sum_m theta_i pot         g_i = sum_m grad theta_i pot
+//   tangent   tQ = sum_i [t_q_i theta_i + q_i (grad theta_i . v_i)]                                 tpot = G tQ
+//             tphi_i = sum_m theta_i tpot + g_i . v_i       t_g_i = sum_m grad theta_i tpot + T_i v_i,   T_i = sum_m grad grad theta_i pot
+// (the twin: tests/pme_tangent_yardstick.py).  The neutralising background is a constant of the evaluation (sum t_q = 0 under the
+// NSE normalisation, as in ewald_tatom_kernel).  Stages: the primal potential mesh and ONE field pass (phi, g, T per atom, in
+// double) per call whatever K is; per direction a charge assignment, the axis transforms (pme_dft_kernel itself, over a
+// (direction, system) slice index: `sys_rep` repeats the systems' parameters K times), the influence multiply and one wave per
+// (atom, direction) that adds onto the seeds of the sweep.
+//
+// Fixed point of the tangent assignment.  A direction is normalised by s_k = the power of two above
+//   c_max = max_i c_i,   c_i = |t_q_i| + |q_i| sum_a |du_a/dt|,   du_a/dt = K_a (v_i . inv_a)      (pme_tscale_kernel),
+// the bound of what one atom adds to one mesh point: every weight and |dM8/du| (a difference of two order-7 weights in [0, 1]) is at
+// most 1.  The normalised values go to the mesh as integers in units of 2^-40, so a point holds at most N 2^40 in magnitude: below
+// 2^61 for the N < 2^21 atoms tangent_validate admits, whatever |v| is (a large |v| only raises s_k).  The operator is linear: the
+// influence step multiplies s_k back in (and the 2^44 / 2^40 between pme_dft_kernel<0>'s unit and this one) - powers of two, exact.
+constexpr double PME_TFIX = 1099511627776.0;  // 2^40
+constexpr int PME_TTILE = 5120;               // tile points of the tangent assignment (40 KiB beside 13 KiB of spline tables)
+
+// bspline8 with the second derivative: d2w[j] = w6[j - 2] - 2 w6[j - 1] + w6[j] from the order-6 weights of the recursion (the rule
+// dw[j] = w7[j - 1] - w7[j] applied twice; continuous: M8 is C^6)
+__device__ __forceinline__ void bspline8_d2(double d, double w[PME_P], double dw[PME_P], double d2w[PME_P]) {
+#pragma unroll
+  for (int j = 0; j < PME_P; ++j) w[j] = 0.0;
+  w[0] = 1.0 - d;
+  w[1] = d;
+#pragma unroll
+  for (int k = 3; k <= PME_P; ++k) {
+    if (k == PME_P - 1) {  // (w holds the order-6 weights in 0 .. 5, zeros behind them)
+      d2w[0] = w[0];
+      d2w[1] = w[1] - 2.0 * w[0];
+#pragma unroll
+      for (int j = 2; j < PME_P; ++j) d2w[j] = w[j - 2] - 2.0 * w[j - 1] + w[j];
+    }
+    if (k == PME_P) {
+      dw[0] = -w[0];
+#pragma unroll
+      for (int j = 1; j < PME_P; ++j) dw[j] = w[j - 1] - w[j];
+    }
+    const double div = 1.0 / (double)(k - 1);
+    w[k - 1] = div * d * w[k - 2];
+#pragma unroll
+    for (int j = 1; j < k - 1; ++j) w[k - 1 - j] = div * ((d + (double)j) * w[k - 2 - j] + ((double)(k - j) - d) * w[k - 1 - j]);
+    w[0] = div * (1.0 - d) * w[0];
+  }
+}
+
+// velocity of the scaled coordinate along axis a: K_a (v . inv_a)
+__device__ __forceinline__ double pme_du(const float* __restrict__ v, const EwaldSystem& E, int ax) {
+  return (double)E.mesh[ax] * fma((double)v[2], E.inv[6 + ax], fma((double)v[1], E.inv[3 + ax], (double)v[0] * E.inv[ax]));
+}
+
+__device__ __forceinline__ double pme_total_tq(const float* __restrict__ tq, int nq, int n_atoms, int k, int i) {
+  double t = (double)tq[((size_t)k * nq) * n_atoms + i];
+  if (nq == 2) t += (double)tq[((size_t)k * nq + 1) * n_atoms + i];
+  return t;
+}
+
+// s_k of every direction (grid = directions): the maximum is independent of the order it is taken in
+__global__ __launch_bounds__(256) void pme_tscale_kernel(const float* __restrict__ q, const float* __restrict__ tq, int nq,
+                                                        const float* __restrict__ tv, const int* __restrict__ mol_idx, int n_atoms,
+                                                        const EwaldSystem* __restrict__ es, double* __restrict__ tscale) {
+  const int k = blockIdx.x;
+  double m = 0.0;
+  for (int i = threadIdx.x; i < n_atoms; i += 256) {
+    const EwaldSystem& E = es[mol_idx[i]];
+    if (E.mesh_pts == 0) continue;
+    const float* v = tv + ((size_t)k * n_atoms + i) * 3;
+    const double c = fabs(pme_total_tq(tq, nq, n_atoms, k, i)) +
+                     fabs((double)q[i]) * (fabs(pme_du(v, E, 0)) + fabs(pme_du(v, E, 1)) + fabs(pme_du(v, E, 2)));
+    m = fmax(m, c);  // (a NaN is dropped here; the sweep's outputs carry it through the seeds)
+  }
+  __shared__ double sh[256];
+  sh[threadIdx.x] = m;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double c = sh[0];
+    tscale[k] = (c > 0.0 && c < 1e300) ? ldexp(1.0, ilogb(c) + 1) : 1.0;
+  }
+}
+
+__global__ void pme_trep_kernel(const EwaldSystem* __restrict__ es, int n_mol, int n_slices, EwaldSystem* __restrict__ rep) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n_slices) rep[t] = es[t % n_mol];
+}
+
+// the integer one atom adds to mesh point (j0, lane): ONE expression for the tile and the direct form (explicit fma: nothing is left
+// to contraction, both forms add the same integers)
+__device__ __forceinline__ unsigned long long pme_tval(double w0, double dw0, double c0, double c1) {
+  return (unsigned long long)__double2ll_rn(fma(dw0, c1, w0 * c0) * PME_TFIX);
+}
+// per lane (j1, j2) of atom a:  value(j0) = w0[j0] c0 + dw0[j0] c1,  c0 = t_q w1 w2 + q (u1 dw1 w2 + u2 w1 dw2),  c1 = q u0 w1 w2
+// (sc = {t_q, q u0, q u1, q u2} / s_k)
+__device__ __forceinline__ void pme_tcoef(const double* __restrict__ w1, const double* __restrict__ w2, int j1, int j2,
+                                          const double* __restrict__ sc, double& c0, double& c1) {
+  const double w12 = w1[j1] * w2[j2];
+  c1 = sc[1] * w12;
+  c0 = fma(sc[0], w12, fma(sc[2], w1[8 + j1] * w2[j2], sc[3] * (w1[j1] * w2[8 + j2])));
+}
+
+// Tangent charge assignment over (atoms of a block, direction): pme_spread_kernel's two forms with signed values (two's complement:
+// the unsigned adds wrap to the signed sum).  grid (blocks of PME_SG atoms, directions); mesh slice (k n_mol + system).
+__global__ __launch_bounds__(256) void pme_tspread_kernel(const float* __restrict__ xw, const float* __restrict__ q,
+                                                         const float* __restrict__ tq, int nq, const float* __restrict__ tv,
+                                                         const int* __restrict__ mol_idx, const int* __restrict__ order, int n_atoms,
+                                                         int n_mol, const EwaldSystem* __restrict__ es,
+                                                         const double* __restrict__ tscale, long long* __restrict__ tmeshq,
+                                                         size_t max_mesh) {
+  __shared__ unsigned long long tile[PME_TTILE];
+  __shared__ double sw[PME_SG][3][2 * PME_P];  // [0..7] weights, [8..15] derivatives
+  __shared__ double sc[PME_SG][4];
+  __shared__ int sfl[PME_SG][3], srel[PME_SG][3];
+  __shared__ int smin[3], smax[3], satom[PME_SG], s_mixed;
+  const int a0 = blockIdx.x * PME_SG, na = min(PME_SG, n_atoms - a0), k = blockIdx.y;
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  if (tid < 3) smin[tid] = INT_MAX, smax[tid] = INT_MIN;
+  if (tid == 0) s_mixed = 0;
+  if (tid < na) satom[tid] = order ? order[a0 + tid] : a0 + tid;
+  __syncthreads();
+  const int s = mol_idx[satom[0]];
+  const double inv_s = 1.0 / tscale[k];  // (a power of two: exact)
+  if (tid < 3 * na) {
+    const int a = tid / 3, ax = tid - 3 * a, ai = satom[a];
+    const EwaldSystem& Ea = es[mol_idx[ai]];
+    if (mol_idx[ai] != s) s_mixed = 1;
+    int fl = 0;
+    double d = 0.0, w[PME_P], dw[PME_P];
+    pme_scaled(xw, ai, ax, Ea, max(1, Ea.mesh[ax]), fl, d);
+    bspline8(d, w, dw);
+#pragma unroll
+    for (int j = 0; j < PME_P; ++j) sw[a][ax][j] = w[j], sw[a][ax][8 + j] = dw[j];
+    sfl[a][ax] = fl;
+    const double qi = (double)q[ai];
+    sc[a][1 + ax] = qi * pme_du(tv + ((size_t)k * n_atoms + ai) * 3, Ea, ax) * inv_s;
+    if (ax == 0) sc[a][0] = pme_total_tq(tq, nq, n_atoms, k, ai) * inv_s;
+  }
+  __syncthreads();
+  const EwaldSystem& E = es[s];
+  const int K0 = E.mesh[0], K1 = E.mesh[1], K2 = E.mesh[2];
+  const bool one_system = s_mixed == 0;
+  if (one_system && E.mesh_pts != 0 && tid < 3 * na) {
+    const int a = tid / 3, ax = tid - 3 * a, K = E.mesh[ax];
+    int rel = sfl[a][ax] - sfl[0][ax];
+    if (2 * rel > K) rel -= K;
+    if (2 * rel < -K) rel += K;
+    srel[a][ax] = rel;
+    atomicMin(&smin[ax], rel);
+    atomicMax(&smax[ax], rel);
+  }
+  __syncthreads();
+  unsigned long long* mq = reinterpret_cast<unsigned long long*>(tmeshq) + (size_t)k * (size_t)n_mol * max_mesh;
+  const int j1 = lane >> 3, j2 = lane & 7;
+  const bool spans = one_system && E.mesh_pts != 0;
+  const int e0 = spans ? smax[0] - smin[0] + PME_P : 0, e1 = spans ? smax[1] - smin[1] + PME_P : 0, e2 = spans ? smax[2] - smin[2] + PME_P : 0;
+  const bool tiled = spans && (long)e0 * e1 * e2 <= (long)PME_TTILE;
+  if (!tiled) {  // direct form, one wave per atom in turn
+    for (int a = wv; a < na; a += 4) {
+      const int sa = mol_idx[satom[a]];
+      const EwaldSystem& Ea = es[sa];
+      if (Ea.mesh_pts == 0) continue;
+      const int A1 = Ea.mesh[1], A2 = Ea.mesh[2];
+      double c0, c1;
+      pme_tcoef(sw[a][1], sw[a][2], j1, j2, sc[a], c0, c1);
+      const size_t off12 = (size_t)pme_wrap(sfl[a][1] - (PME_P - 1) + j1, A1) * A2 + pme_wrap(sfl[a][2] - (PME_P - 1) + j2, A2);
+      unsigned long long* m = mq + (size_t)sa * max_mesh;
+#pragma unroll
+      for (int j0 = 0; j0 < PME_P; ++j0) {
+        const size_t at = (size_t)pme_wrap(sfl[a][0] - (PME_P - 1) + j0, Ea.mesh[0]) * A1 * A2 + off12;
+        atomicAdd(m + at, pme_tval(sw[a][0][j0], sw[a][0][8 + j0], c0, c1));
+      }
+    }
+    return;
+  }
+  const int np = e0 * e1 * e2;
+  for (int t = tid; t < np; t += 256) tile[t] = 0ull;
+  __syncthreads();
+  for (int a = wv; a < na; a += 4) {
+    double c0, c1;
+    pme_tcoef(sw[a][1], sw[a][2], j1, j2, sc[a], c0, c1);
+    const int base = ((srel[a][0] - smin[0]) * e1 + (srel[a][1] - smin[1] + j1)) * e2 + (srel[a][2] - smin[2] + j2);
+#pragma unroll
+    for (int j0 = 0; j0 < PME_P; ++j0) atomicAdd(&tile[base + j0 * e1 * e2], pme_tval(sw[a][0][j0], sw[a][0][8 + j0], c0, c1));
+  }
+  __syncthreads();
+  int o0 = (sfl[0][0] + smin[0] - (PME_P - 1)) % K0, o1 = (sfl[0][1] + smin[1] - (PME_P - 1)) % K1,
+      o2 = (sfl[0][2] + smin[2] - (PME_P - 1)) % K2;
+  o0 += o0 < 0 ? K0 : 0;
+  o1 += o1 < 0 ? K1 : 0;
+  o2 += o2 < 0 ? K2 : 0;
+  unsigned long long* m = mq + (size_t)s * max_mesh;
+  for (int t = tid; t < np; t += 256) {
+    const unsigned long long v = tile[t];
+    if (v == 0ull) continue;
+    const int t0 = t / (e1 * e2), r = t - t0 * (e1 * e2), t1 = r / e2, t2 = r - t1 * e2;
+    atomicAdd(m + ((size_t)((o0 + t0) % K0) * K1 + (o1 + t1) % K1) * K2 + (o2 + t2) % K2, v);
+  }
+}
+
+// tQ^ <- theta tQ^ s_k 2^44 / 2^40 on the half spectrum of slice (k, s): pme_influence_kernel's theta, the multiply alone
+__global__ __launch_bounds__(256) void pme_tinfluence_kernel(const EwaldSystem* __restrict__ es, int n_mol, double* __restrict__ mesh,
+                                                            const double* __restrict__ bmod, const double* __restrict__ tscale,
+                                                            size_t max_mesh) {
+  const int slice = blockIdx.y, s = slice % n_mol, k = slice / n_mol;
+  const EwaldSystem& E = es[s];
+  const int K0 = E.mesh[0], K1 = E.mesh[1], K2 = E.mesh[2], H = K2 / 2 + 1;
+  const int half_pts = K0 * K1 * H;
+  if (E.mesh_pts == 0 || (size_t)blockIdx.x * PME_PART >= (size_t)half_pts) return;
+  const double* b0 = bmod + ((size_t)s * 3 + 0) * PME_MAX_AXIS;
+  const double* b1 = bmod + ((size_t)s * 3 + 1) * PME_MAX_AXIS;
+  const double* b2 = bmod + ((size_t)s * 3 + 2) * PME_MAX_AXIS;
+  double2* A = reinterpret_cast<double2*>(mesh) + (size_t)slice * max_mesh;
+  const double back = tscale[k] * (PME_FIX / PME_TFIX);
+  for (int r = 0; r < PME_PART / 256; ++r) {
+    const int e = blockIdx.x * PME_PART + r * 256 + threadIdx.x;
+    if (e >= half_pts) break;
+    const int i0 = e / (K1 * H), rem = e - i0 * (K1 * H), i1 = rem / H, i2 = rem - i1 * H;
+    const int m0 = i0 <= K0 / 2 ? i0 : i0 - K0, m1 = i1 <= K1 / 2 ? i1 : i1 - K1, m2 = i2;
+    double k2 = 0.0;
+    for (int c = 0; c < 3; ++c) {
+      const double kx = (double)m0 * E.b[c] + (double)m1 * E.b[3 + c] + (double)m2 * E.b[6 + c];
+      k2 += kx * kx;
+    }
+    double theta = 0.0;
+    if (e != 0) theta = 0.5 * E.pref * exp(-k2 * (double)E.inv4a2) / k2 * b0[i0] * b1[i1] * b2[i2];
+    theta *= back;
+    const double2 v = A[e];
+    A[e] = double2{theta * v.x, theta * v.y};
+  }
+}
+
+// Primal field pass, one wave per atom (pme_gather_kernel's lane mapping): field[i] = {phi, g[3], T xx yy zz xy xz yz} in double, without
+// the background.  grad = inv applied to K_a d/du_a, twice for T.
+struct PmeSplines2 {
+  double w[3][24];  // [axis][0..7 weights, 8..15 first, 16..23 second derivatives]
+  int fl[3];
+  int pad;
+};
+__global__ __launch_bounds__(256) void pme_field_kernel(const float* __restrict__ xw, const int* __restrict__ mol_idx, int n_atoms,
+                                                       const EwaldSystem* __restrict__ es, const double* __restrict__ pot_,
+                                                       size_t max_mesh, double* __restrict__ field) {
+  __shared__ PmeSplines2 sp[4];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + wv;
+  const int s = i < n_atoms ? mol_idx[i] : 0;
+  const EwaldSystem& E = es[s];
+  const bool live = i < n_atoms && E.mesh_pts != 0;
+  if (live && lane < 3) {
+    int fl;
+    double d, w[PME_P], dw[PME_P], d2w[PME_P];
+    pme_scaled(xw, i, lane, E, E.mesh[lane], fl, d);
+    bspline8_d2(d, w, dw, d2w);
+#pragma unroll
+    for (int j = 0; j < PME_P; ++j) sp[wv].w[lane][j] = w[j], sp[wv].w[lane][8 + j] = dw[j], sp[wv].w[lane][16 + j] = d2w[j];
+    sp[wv].fl[lane] = fl;
+  }
+  __syncthreads();
+  if (i < n_atoms && !live && lane < 10) field[(size_t)i * 10 + lane] = 0.0;
+  if (!live) return;
+  const PmeSplines2& S = sp[wv];
+  const int K0 = E.mesh[0], K1 = E.mesh[1], K2 = E.mesh[2];
+  const int j1 = lane >> 3, j2 = lane & 7;
+  const double a1 = S.w[1][j1], a2 = S.w[2][j2], da1 = S.w[1][8 + j1], da2 = S.w[2][8 + j2], dda1 = S.w[1][16 + j1], dda2 = S.w[2][16 + j2];
+  const size_t off12 = (size_t)pme_wrap(S.fl[1] - (PME_P - 1) + j1, K1) * K2 + pme_wrap(S.fl[2] - (PME_P - 1) + j2, K2);
+  const double* pot = pot_ + (size_t)s * max_mesh;
+  double s0 = 0.0, sd = 0.0, sdd = 0.0;
+#pragma unroll
+  for (int j0 = 0; j0 < PME_P; ++j0) {
+    const double p = pot[(size_t)pme_wrap(S.fl[0] - (PME_P - 1) + j0, K0) * K1 * K2 + off12];
+    s0 = fma(S.w[0][j0], p, s0);
+    sd = fma(S.w[0][8 + j0], p, sd);
+    sdd = fma(S.w[0][16 + j0], p, sdd);
+  }
+  const double k0 = (double)K0, k1 = (double)K1, k2 = (double)K2;
+  const double phi = wave_sum(s0 * a1 * a2);
+  double gu[3], Tu[6];  // scaled-coordinate derivatives: Tu = 00 11 22 01 02 12
+  gu[0] = wave_sum(sd * a1 * a2) * k0;
+  gu[1] = wave_sum(s0 * da1 * a2) * k1;
+  gu[2] = wave_sum(s0 * a1 * da2) * k2;
+  Tu[0] = wave_sum(sdd * a1 * a2) * k0 * k0;
+  Tu[1] = wave_sum(s0 * dda1 * a2) * k1 * k1;
+  Tu[2] = wave_sum(s0 * a1 * dda2) * k2 * k2;
+  Tu[3] = wave_sum(sd * da1 * a2) * k0 * k1;
+  Tu[4] = wave_sum(sd * a1 * da2) * k0 * k2;
+  Tu[5] = wave_sum(s0 * da1 * da2) * k1 * k2;
+  if (lane != 0) return;
+  double* f = field + (size_t)i * 10;
+  f[0] = phi;
+  double M[3][3];  // M[c][b] = sum_a inv[c][a] Tu[a][b]
+  const double TU[3][3] = {{Tu[0], Tu[3], Tu[4]}, {Tu[3], Tu[1], Tu[5]}, {Tu[4], Tu[5], Tu[2]}};
+  for (int c = 0; c < 3; ++c) {
+    f[1 + c] = E.inv[c * 3] * gu[0] + E.inv[c * 3 + 1] * gu[1] + E.inv[c * 3 + 2] * gu[2];
+    for (int b = 0; b < 3; ++b) M[c][b] = E.inv[c * 3] * TU[0][b] + E.inv[c * 3 + 1] * TU[1][b] + E.inv[c * 3 + 2] * TU[2][b];
+  }
+  const int pc[6] = {0, 1, 2, 0, 0, 1}, pd[6] = {0, 1, 2, 1, 2, 2};
+  for (int t = 0; t < 6; ++t) {
+    const int c = pc[t], d = pd[t];
+    f[4 + t] = M[c][0] * E.inv[d * 3] + M[c][1] * E.inv[d * 3 + 1] + M[c][2] * E.inv[d * 3 + 2];
+  }
+}
+
+// Tangent interpolation: one wave per (atom, direction) in pme_gather_kernel's lane mapping, sums in double in fixed orders, no
+// atomics: the wave owns its elements.  ADDS onto the seeds in coul_store's layouts, as ewald_tatom_kernel does:
+//   qbar_i += 2 f (phi_i + phi_bg)   tqbar_i^k += 2 f tphi_i^k   (every channel)      xbar_i += 2 f q_i g_i   (k = 0 only)
+//   txbar_i^k += 2 f (t_q_i^k g_i + q_i t_g_i^k)
+// dbg_tphi != NULL (aimnet_debug_pme_tangent): tphi [K][n] and t_g [K][n][3] go out in double instead, before they meet fp32 seeds.
+__global__ __launch_bounds__(256) void pme_tgather_kernel(const float* __restrict__ xw, const float* __restrict__ q,
+                                                         const float* __restrict__ tq, int nq, const float* __restrict__ tv,
+                                                         const int* __restrict__ mol_idx, int n_atoms, int n_mol,
+                                                         const EwaldSystem* __restrict__ es, const double* __restrict__ tpot_,
+                                                         const double* __restrict__ field, size_t max_mesh, float factor,
+                                                         float* __restrict__ qbar, float* __restrict__ tqbar, float* __restrict__ xbar,
+                                                         float* __restrict__ txbar, double* __restrict__ dbg_tphi,
+                                                         double* __restrict__ dbg_tg) {
+  __shared__ PmeSplines sp[4];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, k = blockIdx.y;
+  const int i = blockIdx.x * 4 + wv;
+  const int s = i < n_atoms ? mol_idx[i] : 0;
+  const EwaldSystem& E = es[s];
+  const bool live = i < n_atoms && E.mesh_pts != 0;
+  pme_wave_splines(xw, i, live, E, lane, sp[wv]);
+  __syncthreads();
+  if (!live) return;
+  const PmeSplines& S = sp[wv];
+  const int K0 = E.mesh[0], K1 = E.mesh[1], K2 = E.mesh[2];
+  const int j1 = lane >> 3, j2 = lane & 7;
+  const double a1 = S.w[1][j1], a2 = S.w[2][j2], da1 = S.w[1][8 + j1], da2 = S.w[2][8 + j2];
+  const size_t off12 = (size_t)pme_wrap(S.fl[1] - (PME_P - 1) + j1, K1) * K2 + pme_wrap(S.fl[2] - (PME_P - 1) + j2, K2);
+  const double* tpot = tpot_ + ((size_t)k * n_mol + s) * max_mesh;
+  double s0 = 0.0, sd = 0.0;
+#pragma unroll
+  for (int j0 = 0; j0 < PME_P; ++j0) {
+    const double p = tpot[(size_t)pme_wrap(S.fl[0] - (PME_P - 1) + j0, K0) * K1 * K2 + off12];
+    s0 = fma(S.w[0][j0], p, s0);
+    sd = fma(S.w[0][8 + j0], p, sd);
+  }
+  const double tphi_m = wave_sum(s0 * a1 * a2);
+  const double u0 = wave_sum(sd * a1 * a2) * (double)K0, u1 = wave_sum(s0 * da1 * a2) * (double)K1,
+               u2 = wave_sum(s0 * a1 * da2) * (double)K2;
+  if (lane != 0) return;
+  const double* f = field + (size_t)i * 10;
+  const float* vp = tv + ((size_t)k * n_atoms + i) * 3;
+  const double v0 = vp[0], v1 = vp[1], v2 = vp[2];
+  const double g[3] = {f[1], f[2], f[3]};
+  const double tphi = tphi_m + fma(g[2], v2, fma(g[1], v1, g[0] * v0));
+  const double Tv[3] = {fma(f[8], v2, fma(f[7], v1, f[4] * v0)), fma(f[9], v2, fma(f[5], v1, f[7] * v0)),
+                        fma(f[6], v2, fma(f[9], v1, f[8] * v0))};
+  double tg[3];
+  for (int c = 0; c < 3; ++c) tg[c] = fma(E.inv[c * 3 + 2], u2, fma(E.inv[c * 3 + 1], u1, E.inv[c * 3] * u0)) + Tv[c];
+  if (dbg_tphi) {
+    dbg_tphi[(size_t)k * n_atoms + i] = tphi;
+    for (int c = 0; c < 3; ++c) dbg_tg[((size_t)k * n_atoms + i) * 3 + c] = tg[c];
+    return;
+  }
+  const double qi = q[i], f2x = 2.0 * (double)factor, tqi = pme_total_tq(tq, nq, n_atoms, k, i);
+  const float qv = (float)(f2x * (f[0] + (double)E.phi_bg)), tqv = (float)(f2x * tphi);
+  for (int ch = 0; ch < nq; ++ch) {
+    const size_t pe = (size_t)ch * n_atoms + i, te = ((size_t)k * nq + ch) * n_atoms + i;
+    if (k == 0) qbar[pe] += qv;
+    tqbar[te] += tqv;
+  }
+  for (int c = 0; c < 3; ++c) {
+    const size_t pe = (size_t)i * 3 + c, te = ((size_t)k * n_atoms + i) * 3 + c;
+    if (k == 0) xbar[pe] += (float)(f2x * qi * g[c]);
+    txbar[te] += (float)(f2x * fma(tqi, g[c], qi * tg[c]));
+  }
+}
+
 }  // namespace
 
 int launch_pme_setup(hipStream_t s, const float* cell, int n_cell, const int* mol_start, const float* charge, int nq, int n_mol,
@@ -501,8 +878,9 @@ int launch_pme_setup(hipStream_t s, const float* cell, int n_cell, const int* mo
   return 0;
 }
 
-int launch_pme_recip(hipStream_t s, bool grad, bool stress, const float* xw, const float* q, const int* mol_idx, const int* mol_start,
-                     const int* order, int n_atoms, int n_mol, const EwaldBuffers& b, float factor, double* ecoul, float* qbar, float* fgrad, float* virial_atom) {
+// charge assignment, the 3 + 3 axis transforms around the influence function: the potential mesh in b.meshq (as doubles)
+int launch_pme_potential(hipStream_t s, const float* xw, const float* q, const int* mol_idx, const int* order, int n_atoms, int n_mol,
+                         const EwaldBuffers& b) {
   const size_t mm = (size_t)b.max_mesh;
   const dim3 blk(256);
   hipLaunchKernelGGL(pme_spread_kernel, dim3(ceil_div(n_atoms, PME_SG)), blk, 0, s, xw, q, mol_idx, order, n_atoms, b.sys, b.meshq,
@@ -524,6 +902,57 @@ int launch_pme_recip(hipStream_t s, bool grad, bool stress, const float* xw, con
   AIMNET_LAUNCH_CHECK();
   hipLaunchKernelGGL((pme_dft_kernel<3>), gdft, blk, 0, s, b.sys, 2, b.ma, b.meshq, mm);
   AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_pme_field(hipStream_t s, const float* xw, const int* mol_idx, int n_atoms, const EwaldBuffers& b, double* field) {
+  hipLaunchKernelGGL(pme_field_kernel, dim3(ceil_div(n_atoms, 4)), dim3(256), 0, s, xw, mol_idx, n_atoms, b.sys,
+                     reinterpret_cast<const double*>(b.meshq), (size_t)b.max_mesh, field);
+  AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_pme_tangent(hipStream_t s, const float* xw, const float* q, const float* tq, int nq, const float* tv, const int* mol_idx,
+                       const int* order, int n_atoms, int n_mol, int n_dir, const EwaldBuffers& b, const PmeTangentBuffers& t,
+                       float factor, float* qbar, float* tqbar, float* xbar, float* txbar, double* dbg_tphi, double* dbg_tg) {
+  const size_t mm = (size_t)b.max_mesh;
+  const int n_slices = n_dir * n_mol;  // (<= 65 535: tangent_validate)
+  const dim3 blk(256);
+  AIMNET_HIP_CHECK(hipMemsetAsync(t.tmeshq, 0, (size_t)n_slices * mm * sizeof(long long), s));
+  hipLaunchKernelGGL(pme_tscale_kernel, dim3(n_dir), blk, 0, s, q, tq, nq, tv, mol_idx, n_atoms, b.sys, t.tscale);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pme_trep_kernel, dim3(ceil_div(n_slices, 256)), blk, 0, s, b.sys, n_mol, n_slices, t.sys_rep);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pme_tspread_kernel, dim3(ceil_div(n_atoms, PME_SG), n_dir), blk, 0, s, xw, q, tq, nq, tv, mol_idx, order, n_atoms,
+                     n_mol, b.sys, t.tscale, t.tmeshq, mm);
+  AIMNET_LAUNCH_CHECK();
+  // the transforms of the evaluation, one (direction, system) slice per grid.y: sys_rep[k n_mol + s] = sys[s]
+  const dim3 gdft(b.max_mesh / 256 + 2, n_slices);
+  hipLaunchKernelGGL((pme_dft_kernel<0>), gdft, blk, 0, s, t.sys_rep, 2, t.tmeshq, t.tma, mm);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL((pme_dft_kernel<1>), gdft, blk, 0, s, t.sys_rep, 1, t.tma, t.tmb, mm);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL((pme_dft_kernel<1>), gdft, blk, 0, s, t.sys_rep, 0, t.tmb, t.tma, mm);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pme_tinfluence_kernel, dim3(b.max_parts, n_slices), blk, 0, s, b.sys, n_mol, t.tma, b.bmod, t.tscale, mm);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL((pme_dft_kernel<2>), gdft, blk, 0, s, t.sys_rep, 0, t.tma, t.tmb, mm);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL((pme_dft_kernel<2>), gdft, blk, 0, s, t.sys_rep, 1, t.tmb, t.tma, mm);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL((pme_dft_kernel<3>), gdft, blk, 0, s, t.sys_rep, 2, t.tma, t.tmeshq, mm);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pme_tgather_kernel, dim3(ceil_div(n_atoms, 4), n_dir), blk, 0, s, xw, q, tq, nq, tv, mol_idx, n_atoms, n_mol, b.sys,
+                     reinterpret_cast<const double*>(t.tmeshq), t.field, mm, factor, qbar, tqbar, xbar, txbar, dbg_tphi, dbg_tg);
+  AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_pme_recip(hipStream_t s, bool grad, bool stress, const float* xw, const float* q, const int* mol_idx, const int* mol_start,
+                     const int* order, int n_atoms, int n_mol, const EwaldBuffers& b, float factor, double* ecoul, float* qbar, float* fgrad, float* virial_atom) {
+  if (const int rc = launch_pme_potential(s, xw, q, mol_idx, order, n_atoms, n_mol, b)) return rc;
+  const size_t mm = (size_t)b.max_mesh;
+  const dim3 blk(256);
   const dim3 grid(ceil_div(n_atoms, 4));
   const double* pot = reinterpret_cast<const double*>(b.meshq);
   if (grad && stress)

@@ -27,6 +27,10 @@ struct TangentRequest {
   int emb_n_ext;                                                // point charges
   bool emb_potential, emb_potential_grad, emb_potential_hess;  // which per-atom arrays are given
   bool emb_mol_idx, emb_scratch_ok;  // ext_mol_idx given; scratch given and at least aimnet_embedding_tangent_scratch_bytes
+  // aimnet_engine_set_pme_tangent armed the sweep for particle-mesh Ewald (read with coulomb == PME and Hvp only); then ewald_args
+  // holds ewald_args_check of the inputs as for Ewald, and of the options:
+  bool pme_tangent;
+  int pme_max_mesh, pme_part;  // options.pme_max_mesh; PME_PART (kernels.h)
 };
 
 // ---- argument checks: 0, or AIMNET_E_INVALID with the message in msg.  Nothing has been launched when they run --------------------
@@ -69,10 +73,25 @@ inline int tangent_validate(const TangentRequest& r, char* msg, size_t n) {
     if (r.coulomb == AIMNET_COULOMB_DSF && r.max_nb_lr <= 0)
       return plan_reject(msg, n,
                          "hvp: DSF Coulomb needs max_nb_lr > 0 (the tangent sweep runs on the neighbour list, also for periodic input)");
-    if (r.coulomb == AIMNET_COULOMB_PME)
+    if (r.coulomb == AIMNET_COULOMB_PME && !r.pme_tangent)
       return plan_reject(msg, n,
                          "hvp: the analytic tangent sweep does not cover particle-mesh Ewald (use the exact Ewald sum or DSF, or "
                          "differences of forces as the reference does for its PME block, lr.py:903-926)");
+    if (r.coulomb == AIMNET_COULOMB_PME) {  // armed (aimnet_engine_set_pme_tangent)
+      if (r.ewald_args == 1)
+        return plan_reject(msg, n, "hvp: particle-mesh Ewald needs a cell that is periodic along all three axes (lr.py:655-657)");
+      if (r.ewald_args || r.pme_max_mesh < 512)
+        return plan_reject(msg, n, "hvp: particle-mesh Ewald needs 0 < ewald_accuracy < 1 and pme_max_mesh >= 512");
+      if (r.max_nb_lr <= 0 || !r.dsf_rc_set)
+        return plan_reject(msg, n,
+                           "hvp: particle-mesh Ewald runs its real-space term on the neighbour list: dsf_rc (the list cutoff, at least "
+                           "every system's real-space cutoff) and max_nb_lr must be > 0");
+      // the tangent charge meshes hold at most n_atoms 2^40 per point (pme.hip); a (direction, system) slice is a grid.y index
+      if (r.N >= (1 << 21)) return plan_reject(msg, n, "hvp: the particle-mesh Ewald tangent takes fewer than %d atoms", 1 << 21);
+      if ((size_t)r.n_vec * (size_t)r.n_mol > 65535)
+        return plan_reject(msg, n, "hvp: particle-mesh Ewald: at most 65535 directions x systems per sweep (%d x %d given): split the "
+                                   "directions over several calls", r.n_vec, r.n_mol);
+    }
     if (r.coulomb == AIMNET_COULOMB_EWALD) {
       if (r.ewald_args == 1)
         return plan_reject(msg, n, "hvp: Ewald summation needs a cell that is periodic along all three axes (lr.py:655-657)");
@@ -116,6 +135,10 @@ struct TangentPlan {
   bool want_species;        // species slots + present masks are formed (DFT-D3)
   bool bbox;                // non-periodic: bounding-box cell grid
   bool embedding;           // the embedding's seeds join the Coulomb seeds (armed), and after the backward its site pass
+  // particle-mesh Ewald (armed): pme_setup in front of the list, the real-space term over the list with the systems' own (alpha, rc),
+  // the primal potential mesh + field pass and the mesh tangents of every direction (pme.hip)
+  bool pme, pme_qtot;       // pme_qtot: a two-channel model - the mesh sees alpha + beta, formed in a buffer of its own
+  int pme_max_mesh, pme_max_parts;  // mesh points of one system's slice, blocks of its influence kernel (0: branch not taken)
 };
 
 inline TangentPlan tangent_plan(const TangentRequest& r) {
@@ -132,7 +155,11 @@ inline TangentPlan tangent_plan(const TangentRequest& r) {
   P.d3_block = hvp && r.dftd3 != 0;
   P.cap_d3 = P.d3_block ? std::max(1, r.max_nb_d3) : 0;
   P.ewald = hvp && r.coulomb == AIMNET_COULOMB_EWALD;
-  P.lr_list = hvp && (r.coulomb == AIMNET_COULOMB_DSF || P.ewald);
+  P.pme = hvp && r.coulomb == AIMNET_COULOMB_PME && r.pme_tangent;
+  P.lr_list = hvp && (r.coulomb == AIMNET_COULOMB_DSF || P.ewald || P.pme);
+  P.pme_qtot = P.pme && r.nq == 2;
+  P.pme_max_mesh = P.pme ? std::max(512, r.pme_max_mesh) : 0;
+  P.pme_max_parts = P.pme && r.pme_part > 0 ? (P.pme_max_mesh + r.pme_part - 1) / r.pme_part : 0;
   P.ewald_max_k = P.ewald ? std::max(r.ewald_kb, r.ewald_max_k / r.ewald_kb * r.ewald_kb) : 0;
   P.ewald_qtot = P.ewald && r.nq == 2;
   P.want_species = P.d3_block;

@@ -555,13 +555,16 @@ class HipEngine(capacity.Capacities):
     def hvp(self, coord, numbers, mol_idx, charge, vectors, cell=None, pbc=(True, True, True), coulomb: str = "simple",
             dsf_rc: float = 15.0, dsf_alpha: float = 0.2, want_forces: bool = False,
             dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6,
-            embedding: dict[str, Any] | None = None) -> dict[str, Any]:
+            embedding: dict[str, Any] | None = None, pme_tangent: bool = False) -> dict[str, Any]:
         """Analytic Hessian-vector products (csrc/hvp.hip, aimnet_engine_hvp): vectors [K, N, 3] -> hv [K, N, 3] on the device
         (+ the forces of the same sweep with `want_forces`).  Inputs as `eval` (`pbc`: three flags or per-system [n_cell, 3]);
         with `dftd3` the dispersion block is added as a central difference of the D3 gradient inside the same call.  The K
         directions are processed in as many sweeps as the workspace budget asks for.  `coulomb`: "none", "simple", "dsf" or "ewald" (the exact structure-factor sum at
         `ewald_accuracy`, periodic cells only; `dsf_rc` / `dsf_alpha` are not read with it); "pme" raises - its tangent is not
-        carried, AIMNet2Calculator takes differences of forces there.
+        carried, AIMNet2Calculator takes differences of forces there - unless `pme_tangent=True` arms the mesh tangent
+        (aimnet_engine_set_pme_tangent, csrc/pme.hip): the real-space term on a list of cutoff r_c <= 10 A, the mesh tangents of
+        every direction at 40 bytes per mesh point, direction and system (they enter the split by HVP_BYTES_BUDGET); status[7]
+        grows the mesh capacity and the sweep repeats, as in `eval`.  The engine's switch is on for the sweeps of such a call only.
         `embedding`: the dict of `eval`, carried through the sweep with the atoms moving and the sites clamped
         (include/aimnet_hip.h, aimnet_embedding_tangent): a `potential` needs `potential_grad` and `potential_hess` [N,6] (xx, yy,
         zz, xy, xz, yz) or [N,3,3] beside it (zeros for a uniform field).  hv and the forces then include the term; `want_ext_hv`
@@ -580,14 +583,14 @@ class HipEngine(capacity.Capacities):
             warnings.warn(f"HipEngine.hvp: {K} directions on {n} atoms will take ~{est:.0f} s (~0.75 us per atom and direction on one "
                           f"MI355X, more with DFT-D3); a Krylov / Davidson solver needs tens of directions, not 3N "
                           f"(threshold: HipEngine.HVP_MAX_SECONDS = {self.HVP_MAX_SECONDS:.0f} s)", RuntimeWarning, stacklevel=2)
-        if coulomb == "pme":
+        if coulomb == "pme" and not pme_tangent:
             raise ValueError("HipEngine.hvp: the analytic tangent sweep does not carry particle-mesh Ewald; use coulomb='ewald' (the exact "
                              "sum) or differences of the forces (AIMNet2Calculator does: hvp_method 'fd' is taken automatically)")
         method = _METHODS[coulomb]
         lr_rc = float(dsf_rc)  # cutoff of the long-range list
-        if method == _lib.COULOMB_EWALD:
+        if method in capacity.EWALD_METHODS:
             if cell is None:
-                raise ValueError("HipEngine.hvp: coulomb='ewald' needs a periodic cell")
+                raise ValueError(f"HipEngine.hvp: coulomb='{coulomb}' needs a periodic cell")
             if not (0.0 < float(ewald_accuracy) < 1.0):
                 raise ValueError("HipEngine.hvp: ewald_accuracy must lie in (0, 1)")
             # the real-space term runs on a list: its cutoff is the largest r_c of the batch
@@ -597,6 +600,8 @@ class HipEngine(capacity.Capacities):
             if vols.shape[0] != n_mol:
                 raise ValueError("HipEngine.hvp: cell must be [3, 3] or [n_mol, 3, 3]")
             lr_rc = capacity.ewald_list_cutoff(vols, counts, float(ewald_accuracy))
+            if method == _lib.COULOMB_PME:  # the mesh method caps r_c (csrc/pme.hip, PME_RC_MAX)
+                lr_rc = min(lr_rc, capacity.PME_RC_MAX * (1.0 + 1e-5))
         rq = capacity.Request("hvp", n, n_mol, cell is not None, method, lr_rc, float(dsf_alpha), float(ewald_accuracy), dftd3)
         hv = torch.empty_like(vectors)
         f_out = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_forces else None
@@ -610,9 +615,16 @@ class HipEngine(capacity.Capacities):
             return self.lib.aimnet_engine_hvp(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
                                               hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None, *tail)
         kmax = self.HVP_MAX_DIRECTIONS // (4 if dftd3 is not None else 1)  # grid.y limit of the tangent kernels
+        if method == _lib.COULOMB_PME:  # a (direction, system) slice of the mesh transforms is a grid.y index
+            kmax = max(1, min(kmax, self.HVP_MAX_DIRECTIONS // n_mol))
+        mesh = method == _lib.COULOMB_PME  # (armed: unarmed requests were refused above)
         try:
+            if mesh:  # the engine's switch is on for the sweeps of this call only: no state leaks from one call into the next
+                _lib.check(self.lib.aimnet_engine_set_pme_tangent(self._h, 1), "aimnet_engine_set_pme_tangent")
             self._tangent_sweeps("hvp", self.lib.aimnet_engine_hvp_workspace_bytes, rq, K, kmax, call)
         finally:
+            if mesh:
+                self.lib.aimnet_engine_set_pme_tangent(self._h, 0)
             if embedding is not None:
                 self.lib.aimnet_engine_set_embedding(self._h, None)  # (disarms the tangent too)
         res = {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}

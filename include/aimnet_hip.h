@@ -308,6 +308,26 @@ typedef struct aimnet_embedding_tangent {
 size_t aimnet_embedding_tangent_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext);
 int aimnet_engine_set_embedding_tangent(aimnet_engine* e, const aimnet_embedding_tangent* t);
 
+/* Particle-mesh Ewald in the analytic Hessian sweep.  Arming is explicit, as for the embedding: by default (and after on = 0)
+ * aimnet_engine_hvp refuses AIMNET_COULOMB_PME with the message it always had; after aimnet_engine_set_pme_tangent(e, 1) it carries the
+ * method: pme_setup in front of the long-range list, the real-space term erfc(alpha d) / d and the self term over that list with the
+ * systems' own (alpha, r_c) (options.dsf_rc: the list cutoff, at least every system's r_c <= 10 A; verified on the device, status[6]
+ * bit 6), then on the mesh (csrc/pme.hip; the cell is fixed, atoms move along v^k, the total charges along t_q^k, theta_i the order-8
+ * spline product, G the linear cell-only map charge mesh -> potential mesh):
+ *   once per call    Q = sum_i q_i theta_i,  pot = G Q,  phi_i, g_i = grad phi_i, T_i = sum_m grad grad theta_i pot   (double)
+ *   per direction    tQ = sum_i [t_q_i theta_i + q_i (grad theta_i . v_i)],  tpot = G tQ,
+ *                    tphi_i = sum_m theta_i tpot + g_i . v_i,    t_g_i = sum_m grad theta_i tpot + T_i v_i
+ *   seeds            qbar_i += 2 f (phi_i + phi_bg), xbar_i += 2 f q_i g_i, tqbar_i += 2 f tphi_i, txbar_i += 2 f (t_q_i g_i + q_i t_g_i)
+ * The tangent charge assignment is in integers (2^-40 of the direction normalised by a power of two above max_i (|t_q_i| + |q_i|
+ * sum_a K_a |v_i . inv_a|): no |v| overflows it), sums are double in fixed orders, no atomics on results: hv is bitwise repeatable
+ * and independent of how the directions are split into calls.  Workspace: 40 bytes per mesh point, direction and system
+ * (aimnet_engine_hvp_workspace_bytes counts them while armed); status[7] = mesh points the largest system needs (> pme_max_mesh:
+ * nothing of the mesh was computed - grow and repeat).  Armed requests need a cell periodic along all three axes, 0 <
+ * ewald_accuracy < 1, pme_max_mesh >= 512, dsf_rc > 0, max_nb_lr > 0, n_atoms < 2^21, n_vec n_mol <= 65535, no caller-supplied
+ * matrices; the embedding together with PME stays refused.  Not carried: strain tangents, domain decomposition, meshes beyond 512
+ * points per axis.  aimnet_engine_eval and aimnet_engine_charge_response do not read the switch. */
+int aimnet_engine_set_pme_tangent(aimnet_engine* e, int32_t on);
+
 /* Bytes of scratch `aimnet_engine_eval` needs for the given problem size. */
 size_t aimnet_engine_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_cell,
                                      const aimnet_eval_options* opt);
@@ -489,6 +509,15 @@ int aimnet_debug_pme_recip(const float* xw, const float* q, const int* order, co
                            float accuracy,
                            int max_mesh, double* e_atom, float* qbar, float* fgrad, float* virial_atom, double* host_info,
                            void* hip_stream);
+/* aimnet_debug_pme_tangent (csrc/pme.hip): the mesh tangent stage of the armed sweep alone, for ONE system, in double, before the
+ * results meet fp32 seeds and WITHOUT the background: device xw [n][3], q [n], tq [n_dir][n] (tangents of the total charges), v
+ * [n_dir][n][3], order [n] or NULL (as above: the tile and the direct form of the assignment add the same integers), cell [9];
+ * writes device field [n][10] (phi, g x y z, T xx yy zz xy xz yz), tphi [n_dir][n], tg [n_dir][n][3].  host_info[8]: alpha, rc,
+ * mesh[3], mesh points needed (> max_mesh: nothing was computed, the outputs are zero), phi_bg, and the tangent fixed-point scale:
+ * the smallest 2^40 / s_k over the directions, i.e. the coarsest step of the charge assignment in the caller's units. */
+int aimnet_debug_pme_tangent(const float* xw, const float* q, const float* tq, const float* v, const int* order, const float* cell,
+                             float total_charge, int n_atoms, int n_dir, float accuracy, int max_mesh, double* field, double* tphi,
+                             double* tg, double* host_info, void* hip_stream);
 
 /* Test hooks for the conv kernels that every evaluation runs (csrc/conv.hip): ONE launch each, on the given stream, on caller-allocated
  * device buffers in the layouts csrc/kernels.h documents; nothing is allocated, copied or synchronised.  Common arguments: nq = charge
