@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_debug_mlp_sweep",
     "aimnet_debug_pme_recip",
     "aimnet_debug_pme_tangent",
+    "aimnet_debug_dftd3_tangent",
     "aimnet_debug_conv_fwd",
     "aimnet_debug_unconcat",
     "aimnet_debug_conv_bwd",
@@ -61,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "aimnet_embedding_tangent_scratch_bytes",
     "aimnet_engine_set_embedding_tangent",
     "aimnet_engine_set_pme_tangent",
+    "aimnet_engine_set_dftd3_tangent",
     "aimnet_neighbor_list",
     "aimnet_neighbor_list_workspace_bytes",
     "aimnet_conv_sv_2d_sp_fwd",
@@ -245,6 +247,8 @@ def load() -> C.CDLL:
     lib.aimnet_engine_hvp_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(EvalOptions)]
     lib.aimnet_engine_hvp.restype = C.c_int
     lib.aimnet_engine_hvp.argtypes = [vp, C.POINTER(Inputs), C.POINTER(EvalOptions), vp, i32, vp, vp, vp, vp, sz, vp]
+    lib.aimnet_debug_dftd3_tangent.restype = C.c_int
+    lib.aimnet_debug_dftd3_tangent.argtypes = lib.aimnet_engine_hvp.argtypes
     lib.aimnet_engine_charge_response_workspace_bytes.restype = sz
     lib.aimnet_engine_charge_response_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(EvalOptions)]
     lib.aimnet_engine_charge_response.restype = C.c_int
@@ -296,6 +300,8 @@ def load() -> C.CDLL:
                                              C.POINTER(C.c_double), vp]
     lib.aimnet_engine_set_pme_tangent.restype = C.c_int
     lib.aimnet_engine_set_pme_tangent.argtypes = [vp, C.c_int32]
+    lib.aimnet_engine_set_dftd3_tangent.restype = C.c_int
+    lib.aimnet_engine_set_dftd3_tangent.argtypes = [vp, C.c_int32]
     # the conv kernels one launch at a time (tests/test_gpu_conv_kernels.py); `shifts` is a host pointer
     ci, cf = C.c_int, C.c_float
     lib.aimnet_debug_conv_fwd.restype = C.c_int

@@ -19,7 +19,8 @@ Deliberate deviations, all loud:
   * (per-system `pbc` flags of shape (B, 3) are supported: the engine takes them as a device array);
   * hessian=True and hessian_vector_product run the analytic tangent sweep of csrc/hvp.hip (forward-mode through the
     forward and backward sweep, all directions at once; `hvp_method`), not autograd double backward: exact second derivatives
-    at fp32 round-off (the external DFT-D3 block: a central difference of the D3 gradient alone, inside the same call), for
+    at fp32 round-off (the external DFT-D3 block: a central difference of the D3 gradient alone, inside the same call, or its
+    analytic tangent after set_dftd3_hessian("analytic")), for
     every Coulomb method but "pme" - the exact Ewald sum is carried by the sweep, the mesh takes differences of forces unless
     set_pme_hessian("analytic") arms its tangent.  The
     finite-difference operator over the analytic forces (`_fd_hvp`, `hvp_method = "fd"`) is kept as the cross-check;
@@ -840,6 +841,19 @@ class AIMNet2Calculator:
             raise ValueError(f"set_pme_hessian: mode must be None or 'analytic', got {mode!r}")
         self._pme_hessian = mode
 
+    _dftd3_hessian = None
+
+    def set_dftd3_hessian(self, mode: str | None = None) -> None:
+        """How the external DFT-D3 term enters second derivatives taken by the tangent sweep: None (default) - a 4-point central
+        difference of the D3 gradient inside the same call (about 5e-5 eV/A^2, four displaced copies of the D3 list per direction);
+        "analytic" - the tangent of the term's gradient on the one list (HipEngine.hvp(..., d3_tangent=True), csrc/d3.hip) at fp32
+        round-off, 32 bytes per direction and atom.  Read by hessian_vector_product, eval(hessian=True) and
+        AIMNet2ASE.get_hessian() while `hvp_method` is "analytic"; combinable with set_pme_hessian and set_embedding_hessian;
+        `hvp_method = "fd"` (and "pme" without its own arming) differences the forces and does not read it."""
+        if mode not in (None, "analytic"):
+            raise ValueError(f"set_dftd3_hessian: mode must be None or 'analytic', got {mode!r}")
+        self._dftd3_hessian = mode
+
     def _hvp(self, d: dict[str, Any], dirs, eps: float | None = None, emb: dict[str, Any] | None = None, extra: dict | None = None):
         """H @ v for K directions (K,N,3) of one structure: analytic tangent sweep, or finite differences (see `hvp_method`).
         `emb`: the `embedding=` dict of HipEngine.hvp (analytic sweep only: the callers have checked, _embedding_hessian_ok);
@@ -861,7 +875,8 @@ class AIMNet2Calculator:
         n = d["coord"].shape[0]
         res = self.engine.hvp(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
                               self._engine_charge(d["charge"], d.get("mult")), dirs, cell=cell, pbc=pbc3, **lr.kwargs(),
-                              **({"embedding": emb} if emb is not None else {}), **({"pme_tangent": True} if mesh_sweep else {}))
+                              **({"embedding": emb} if emb is not None else {}), **({"pme_tangent": True} if mesh_sweep else {}),
+                              **({"d3_tangent": True} if lr.dftd3 is not None and self._dftd3_hessian == "analytic" else {}))
         if extra is not None and "ext_hv" in res:
             extra["ext_hv"] = res["ext_hv"]
         return res["hv"]

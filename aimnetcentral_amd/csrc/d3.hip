@@ -477,4 +477,363 @@ int launch_dftd3(hipStream_t s, bool grad, bool stress, const float* xw, const i
   return 0;
 }
 
+// ================================================================================================
+// The tangent of the term's gradient along K directions v^k [K][N][3] (the cell is fixed): H_d3 v^k, ADDED onto txbar [K][N][3].
+// The analytic dispersion block of the Hessian sweep (hvp.hip, armed by aimnet_engine_set_dftd3_tangent); the formulas are restated in
+// include/aimnet_hip.h and, in numpy float64, in tests/d3_tangent_yardstick.py::closed_form.  launch_dftd3(grad = true) has run at x
+// on the same list: xs4, d3w (shifted exponents, weights, cn) and dEdcn (G) are its outputs.
+//
+// Three passes mirror the primal ones - a wave per atom, lanes over list slots, the loads of two list slots issued before the
+// arithmetic, the cell in registers, wave_sum, no atomics - with the two all-atom dependencies between them:
+//   d3_tcn_kernel       t_cn_i = sum_j sigma' t_d                                   -> tcn4 [K][N] = (v_i, t_cn_i)
+//   d3_tpair_kernel     C6 and its derivatives A_i A_j B_ii B_ij (centred moments), P P' P'' once per pair; per direction the direct pair term onto txbar and
+//                       t_G_i                                                       -> tg4 [K][N] = (v_i, t_G_i)
+//   d3_tcnforce_kernel  (t_G_i + t_G_j) sigma' u + (G_i + G_j)(sigma'' t_d u + sigma' t_u) onto txbar
+// (the direction rides in the float4 of the quantity the NEXT pass gathers per neighbour: one 16-byte gather per neighbour and direction).
+// A wave holds D3_KG directions (grid.y = groups of D3_KG): geometry, sigma and P with their derivatives and the C6 sums are formed
+// once per pair and group.  Every direction owns its accumulators and runs the same instruction sequence whatever slot of a group it
+// sits in - ONE instantiation, no contraction in the bodies, every fused multiply-add written out - so H v^k is bitwise repeatable and
+// does not depend on how the directions are grouped or split into sweeps.  All sums are fp32 (a lane adds ~10 terms, wave_sum is a tree).
+constexpr int D3_KG = 4;
+
+struct D3Dirs {  // the directions of this wave's group, clamped to the first one beyond K (computed, never stored)
+  int k[D3_KG];
+  bool ok[D3_KG];
+  __device__ __forceinline__ D3Dirs(int group, int K) {
+#pragma unroll
+    for (int q = 0; q < D3_KG; ++q) {
+      ok[q] = group * D3_KG + q < K;
+      k[q] = ok[q] ? group * D3_KG + q : group * D3_KG;
+    }
+  }
+};
+
+__global__ __launch_bounds__(256) void d3_tcn_kernel(const float4* __restrict__ xs4, const int* __restrict__ mol_idx,
+                                                    const float* __restrict__ cell, int n_cell, const int* __restrict__ nb_idx,
+                                                    const int* __restrict__ nb_shift, const int* __restrict__ nb_cnt, int cap,
+                                                    D3Tables T, float cutoff, int n_atoms, const float* __restrict__ tv, int K,
+                                                    float4* __restrict__ tcn4) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_atoms) return;
+  const int lane = threadIdx.x & 63;
+  const D3Dirs G(blockIdx.y, K);
+  const float* c = cell ? cell + (n_cell == 1 ? 0 : (size_t)mol_idx[i] * 9) : nullptr;
+  const float4 x4 = xs4[i];
+  const float xi = x4.x, yi = x4.y, zi = x4.z;
+  const float rci = T.rcov[__float_as_int(x4.w)];
+  const int cnt = nb_cnt[i];
+  float vi[D3_KG][3], acc[D3_KG];
+#pragma unroll
+  for (int q = 0; q < D3_KG; ++q) {
+    const float* v = tv + ((size_t)G.k[q] * n_atoms + i) * 3;
+    vi[q][0] = v[0], vi[q][1] = v[1], vi[q][2] = v[2];
+    acc[q] = 0.0f;
+  }
+  const D3Cell C(c);
+  const size_t row = (size_t)i * cap;
+  auto term = [&](const D3Pair& P, float rcj, const float (&vj)[D3_KG][3]) {
+#pragma clang fp contract(off)
+    const float R = rci + rcj;
+    const float idb = frcp(fmaxf(P.d * BOHR_INV_F, 1e-12f));
+    const float sg = frcp(1.0f + fexp(-16.0f * (R * idb - 1.0f)));
+    const float dsg = P.ok ? sg * (1.0f - sg) * (-16.0f * R * idb * idb) * BOHR_INV_F : 0.0f;  // d sigma / d d_ij per Angstrom
+#pragma unroll
+    for (int q = 0; q < D3_KG; ++q) {
+      const float td = fmaf(P.ux, vj[q][0] - vi[q][0], fmaf(P.uy, vj[q][1] - vi[q][1], P.uz * (vj[q][2] - vi[q][2])));
+      acc[q] = fmaf(dsg, td, acc[q]);
+    }
+  };
+  for (int m = lane; m < cnt; m += 128) {  // two list slots per trip, all of their loads issued before the arithmetic
+    const bool v1 = m + 64 < cnt;
+    const int m1 = v1 ? m + 64 : m;
+    const int j0 = nb_idx[row + m], j1 = nb_idx[row + m1];
+    const int h0 = c ? nb_shift[row + m] : 0, h1 = c ? nb_shift[row + m1] : 0;
+    const float4 x0 = xs4[j0], x1 = xs4[j1];
+    float w0[D3_KG][3], w1[D3_KG][3];
+#pragma unroll
+    for (int q = 0; q < D3_KG; ++q) {
+      const float* p0 = tv + ((size_t)G.k[q] * n_atoms + j0) * 3;
+      const float* p1 = tv + ((size_t)G.k[q] * n_atoms + j1) * 3;
+      w0[q][0] = p0[0], w0[q][1] = p0[1], w0[q][2] = p0[2];
+      w1[q][0] = p1[0], w1[q][1] = p1[1], w1[q][2] = p1[2];
+    }
+    const float rc0 = T.rcov[__float_as_int(x0.w)], rc1 = T.rcov[__float_as_int(x1.w)];
+    term(d3_geom(x0, j0, h0, C, xi, yi, zi, cutoff, true), rc0, w0);
+    term(d3_geom(x1, j1, h1, C, xi, yi, zi, cutoff, v1), rc1, w1);
+  }
+#pragma unroll
+  for (int q = 0; q < D3_KG; ++q) {
+    const float t = wave_sum(acc[q]);
+    if (lane == q && G.ok[q]) tcn4[(size_t)G.k[q] * n_atoms + i] = make_float4(vi[q][0], vi[q][1], vi[q][2], t);
+  }
+}
+
+__global__ __launch_bounds__(256) void d3_tpair_kernel(const float4* __restrict__ xs4, const int* __restrict__ mol_idx,
+                                                      const float* __restrict__ cell, int n_cell, const int* __restrict__ nb_idx,
+                                                      const int* __restrict__ nb_shift, const int* __restrict__ nb_cnt, int cap,
+                                                      D3Tables T, D3Params P3, float cutoff, int n_atoms,
+                                                      const float* __restrict__ d3w, const float4* __restrict__ tcn4, int K,
+                                                      float4* __restrict__ tg4, float* __restrict__ txbar) {
+  extern __shared__ float c6lds[];  // [4 waves][ns][25], as d3_pair_kernel
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + wid;
+  if (i >= n_atoms) return;
+  const D3Dirs G(blockIdx.y, K);
+  const int ns = T.ns;
+  float* c6s = c6lds + (size_t)wid * ns * 25;
+  const float4 x4 = xs4[i];
+  const int si = __float_as_int(x4.w);
+  for (int k = lane; k < ns * 25; k += 64) c6s[k] = T.c6slot[(size_t)si * ns * 25 + k];
+  __builtin_amdgcn_wave_barrier();
+  const float* c = cell ? cell + (n_cell == 1 ? 0 : (size_t)mol_idx[i] * 9) : nullptr;
+  const float xi = x4.x, yi = x4.y, zi = x4.z;
+  const int nref_i = T.nref[si];
+  float s_i[5], w_i[5], g_i[5];
+  const float cn_i = d3w[(size_t)i * D3W + 10];
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    s_i[a] = d3w[(size_t)i * D3W + a];
+    w_i[a] = d3w[(size_t)i * D3W + 5 + a];
+    g_i[a] = -8.0f * (cn_i - T.cnref[si * 5 + a]);
+  }
+  const float q_i = T.r4r2[si];
+  const int cnt = nb_cnt[i];
+  float4 ti[D3_KG];  // (v_i, t_cn_i) of every direction
+  float f[D3_KG][3], tg[D3_KG];
+#pragma unroll
+  for (int q = 0; q < D3_KG; ++q) {
+    ti[q] = tcn4[(size_t)G.k[q] * n_atoms + i];
+    f[q][0] = f[q][1] = f[q][2] = tg[q] = 0.0f;
+  }
+  const D3Cell C(c);
+  const size_t row = (size_t)i * cap;
+  auto body = [&](const D3Pair& P, const float4& sj0, const float4& sj1, const float4& sj2, const float (&cr_j)[5], float q_j,
+                  const float4 (&tj)[D3_KG]) {
+#pragma clang fp contract(off)
+    const float s_j[5] = {sj0.x, sj0.y, sj0.z, sj0.w, sj1.x};
+    const float w_j[5] = {sj1.y, sj1.z, sj1.w, sj2.x, sj2.y};
+    const float cn_j = sj2.z;
+    float g_j[5];
+#pragma unroll
+    for (int b = 0; b < 5; ++b) g_j[b] = -8.0f * (cn_j - cr_j[b]);
+    const float* cr = c6s + P.sj * 25;
+    // The kept (a, b) are the primal's mask, a constant of the evaluation.  With p = W / D, c' = c6ref - C6 and g~ = g - sum p g the
+    // combinations of the sums N_., D_. collapse to centred moments (sum p c' = 0 removes the -8 of d_ii W and every mean):
+    //   A_i = sum p c' g~_i,  A_j = sum p c' g~_j,  B_ii = sum p c' g~_i^2,  B_ij = sum p c' g~_i g~_j
+    // In fp32 the uncentred form (N_ii - C6 D_ii - 2 A_i D_i) / D loses 3 - 6e-5 of max|H v| to cancellation, this one 2 - 6e-6
+    // (tests/d3_tangent_yardstick.py).  Two walks over the 5 x 5 block: N, D and the means, then the moments.
+    float N = 0.f, D = 0.f, Di = 0.f, Dj = 0.f;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+      if (a < nref_i && s_i[a] >= -12.0f) {
+        float sb = 0.f, tb = 0.f, tgs = 0.f;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+          const float c6r = cr[a * 5 + b];
+          const float w = (s_i[a] + s_j[b] >= -12.0f && c6r != 0.0f) ? w_j[b] : 0.0f;
+          sb = fmaf(c6r, w, sb);
+          tb += w;
+          tgs = fmaf(w, g_j[b], tgs);
+        }
+        N = fmaf(w_i[a], sb, N);
+        D = fmaf(w_i[a], tb, D);
+        Di = fmaf(w_i[a] * g_i[a], tb, Di);
+        Dj = fmaf(w_i[a], tgs, Dj);
+      }
+    }
+    const bool has = D > 1.0e-12f;
+    const float invD = has ? frcp(fmaxf(D, 1.0e-12f)) : 0.0f;  // (no weight survives: C6 and all of its derivatives are zero)
+    const float c6 = N * invD, gim = Di * invD, gjm = Dj * invD;
+    float Ai = 0.f, Aj = 0.f, Bii = 0.f, Bij = 0.f;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+      if (a < nref_i && s_i[a] >= -12.0f) {
+        float m0 = 0.f, m1 = 0.f;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+          const float c6r = cr[a * 5 + b];
+          const float w = (s_i[a] + s_j[b] >= -12.0f && c6r != 0.0f) ? w_j[b] : 0.0f;
+          const float wc = w * (c6r - c6);
+          m0 += wc;
+          m1 = fmaf(wc, g_j[b] - gjm, m1);
+        }
+        const float gc = g_i[a] - gim, wa = w_i[a] * gc;
+        Ai = fmaf(wa, m0, Ai);
+        Aj = fmaf(w_i[a], m1, Aj);
+        Bii = fmaf(wa * gc, m0, Bii);
+        Bij = fmaf(wa, m1, Bij);
+      }
+    }
+    Ai *= invD, Aj *= invD, Bii *= invD, Bij *= invD;
+    // P = damp S5 and its first two derivatives (d in Bohr inside, per Angstrom outside)
+    const float db = fmaxf(P.d * BOHR_INV_F, 1e-12f);
+    const float qq = 3.0f * q_i * q_j;
+    const float r0 = fmaf(P3.a1, __builtin_amdgcn_sqrtf(qq), P3.a2);
+    const float d2 = db * db, d4 = d2 * d2, d6 = d4 * d2, d8 = d4 * d4;
+    const float r2 = r0 * r0, r4 = r2 * r2, r6 = r4 * r2, r8 = r4 * r4;
+    const float i6 = frcp(d6 + r6), i8 = frcp(d8 + r8);
+    const float k6 = P3.s6 * i6 * i6, k8 = P3.s8 * qq * i8 * i8;
+    const float damp = fmaf(P3.s6, i6, P3.s8 * qq * i8);
+    const float ddamp = fmaf(-8.0f * k8, d6 * db, -6.0f * k6 * (d4 * db));
+    const float d2damp = fmaf(k8 * d6, fmaf(128.0f, d8 * i8, -56.0f), k6 * d4 * fmaf(72.0f, d6 * i6, -30.0f));
+    float sw = 1.0f, dsw = 0.0f, d2sw = 0.0f;
+    if (P3.r_off > P3.r_on && db > P3.r_on) {
+      const float iw = frcp(P3.r_off - P3.r_on);
+      const float t = fminf(fmaxf((db - P3.r_on) * iw, 0.0f), 1.0f);
+      const float t2 = t * t, omt = 1.0f - t;
+      sw = fmaf(-(t2 * t), fmaf(6.0f, t2, fmaf(-15.0f, t, 10.0f)), 1.0f);
+      dsw = -30.0f * t2 * (omt * omt) * iw;
+      d2sw = -60.0f * t * omt * fmaf(-2.0f, t, 1.0f) * (iw * iw);
+    }
+    const float P0 = damp * sw;
+    const float P1 = fmaf(ddamp, sw, damp * dsw) * BOHR_INV_F;
+    const float P2 = fmaf(d2damp, sw, fmaf(2.0f * ddamp, dsw, damp * d2sw)) * (BOHR_INV_F * BOHR_INV_F);
+    const float invd = frcp(P.d);
+    const float c2 = -(c6 * P1);  // d e_ij / d d_ij, C6 held fixed: multiplies t_u
+    const float c6p2 = c6 * P2, p1a = P1 * Ai;
+#pragma unroll
+    for (int q = 0; q < D3_KG; ++q) {
+      const float dx = tj[q].x - ti[q].x, dy = tj[q].y - ti[q].y, dz = tj[q].z - ti[q].z;
+      const float td = fmaf(P.ux, dx, fmaf(P.uy, dy, P.uz * dz));
+      const float tci = ti[q].w, tcj = tj[q].w;
+      const float tc6 = fmaf(Ai, tci, Aj * tcj);
+      const float c1 = fmaf(-tc6, P1, -(c6p2 * td));
+      f[q][0] = fmaf(c1, P.ux, fmaf(c2, fmaf(-P.ux, td, dx) * invd, f[q][0]));
+      f[q][1] = fmaf(c1, P.uy, fmaf(c2, fmaf(-P.uy, td, dy) * invd, f[q][1]));
+      f[q][2] = fmaf(c1, P.uz, fmaf(c2, fmaf(-P.uz, td, dz) * invd, f[q][2]));
+      tg[q] = fmaf(-p1a, td, fmaf(-P0, fmaf(Bii, tci, Bij * tcj), tg[q]));
+    }
+  };
+  for (int m = lane; m < cnt; m += 128) {  // two list slots per trip, all of their loads issued before the arithmetic
+    const bool v1 = m + 64 < cnt;
+    const int m1 = v1 ? m + 64 : m;
+    const int j0 = nb_idx[row + m], j1 = nb_idx[row + m1];
+    const int h0 = c ? nb_shift[row + m] : 0, h1 = c ? nb_shift[row + m1] : 0;
+    const float4 x0 = xs4[j0], x1 = xs4[j1];
+    const float4* w0 = reinterpret_cast<const float4*>(d3w + (size_t)j0 * D3W);
+    const float4* w1 = reinterpret_cast<const float4*>(d3w + (size_t)j1 * D3W);
+    const float4 a0 = w0[0], b0 = w0[1], e0 = w0[2], a1 = w1[0], b1 = w1[1], e1 = w1[2];
+    float4 t0[D3_KG], t1[D3_KG];
+#pragma unroll
+    for (int q = 0; q < D3_KG; ++q) {
+      t0[q] = tcn4[(size_t)G.k[q] * n_atoms + j0];
+      t1[q] = tcn4[(size_t)G.k[q] * n_atoms + j1];
+    }
+    const int s0 = __float_as_int(x0.w), s1 = __float_as_int(x1.w);
+    float cr0[5], cr1[5];
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+      cr0[b] = T.cnref[s0 * 5 + b];
+      cr1[b] = T.cnref[s1 * 5 + b];
+    }
+    const float q0 = T.r4r2[s0], q1 = T.r4r2[s1];
+    const D3Pair P0 = d3_geom(x0, j0, h0, C, xi, yi, zi, cutoff, true);
+    const D3Pair P1 = d3_geom(x1, j1, h1, C, xi, yi, zi, cutoff, v1);
+    if (P0.ok) body(P0, a0, b0, e0, cr0, q0, t0);
+    if (P1.ok) body(P1, a1, b1, e1, cr1, q1, t1);
+  }
+#pragma unroll
+  for (int q = 0; q < D3_KG; ++q) {
+    const float f0 = wave_sum(f[q][0]), f1 = wave_sum(f[q][1]), f2 = wave_sum(f[q][2]), g = wave_sum(tg[q]);
+    if (lane == q && G.ok[q]) {  // E = k sum_ordered e: -2k on the gradient; e_ij and e_ji both depend on cn_i: 2k on t_G
+      const size_t o = (size_t)G.k[q] * n_atoms + i;
+      txbar[o * 3 + 0] += -2.0f * HALF_HARTREE_F * f0;
+      txbar[o * 3 + 1] += -2.0f * HALF_HARTREE_F * f1;
+      txbar[o * 3 + 2] += -2.0f * HALF_HARTREE_F * f2;
+      tg4[o] = make_float4(ti[q].x, ti[q].y, ti[q].z, 2.0f * HALF_HARTREE_F * g);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void d3_tcnforce_kernel(const float4* __restrict__ xs4, const int* __restrict__ mol_idx,
+                                                         const float* __restrict__ cell, int n_cell,
+                                                         const int* __restrict__ nb_idx, const int* __restrict__ nb_shift,
+                                                         const int* __restrict__ nb_cnt, int cap, D3Tables T, float cutoff,
+                                                         int n_atoms, const float* __restrict__ dEdcn,
+                                                         const float4* __restrict__ tg4, int K, float* __restrict__ txbar) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_atoms) return;
+  const int lane = threadIdx.x & 63;
+  const D3Dirs G(blockIdx.y, K);
+  const float* c = cell ? cell + (n_cell == 1 ? 0 : (size_t)mol_idx[i] * 9) : nullptr;
+  const float4 x4 = xs4[i];
+  const float xi = x4.x, yi = x4.y, zi = x4.z;
+  const float rci = T.rcov[__float_as_int(x4.w)];
+  const float gi = dEdcn[i];
+  const int cnt = nb_cnt[i];
+  float4 ti[D3_KG];  // (v_i, t_G_i)
+  float f[D3_KG][3];
+#pragma unroll
+  for (int q = 0; q < D3_KG; ++q) {
+    ti[q] = tg4[(size_t)G.k[q] * n_atoms + i];
+    f[q][0] = f[q][1] = f[q][2] = 0.0f;
+  }
+  const D3Cell C(c);
+  const size_t row = (size_t)i * cap;
+  auto term = [&](const D3Pair& P, float rcj, float gj, const float4 (&tj)[D3_KG]) {
+#pragma clang fp contract(off)
+    const float R = rci + rcj;
+    const float idb = frcp(fmaxf(P.d * BOHR_INV_F, 1e-12f));
+    const float sg = frcp(1.0f + fexp(-16.0f * (R * idb - 1.0f)));
+    const float a1 = -16.0f * R * idb * idb, sp = sg * (1.0f - sg);
+    const float s1 = P.ok ? sp * a1 * BOHR_INV_F : 0.0f;  // sigma' and sigma'' per Angstrom (and per Angstrom^2)
+    const float s2 = P.ok ? sp * fmaf(fmaf(-2.0f, sg, 1.0f) * a1, a1, 32.0f * R * idb * idb * idb) * (BOHR_INV_F * BOHR_INV_F) : 0.0f;
+    const float gs = gi + gj;
+    const float c2 = gs * s1, gs2 = gs * s2;
+    const float invd = frcp(P.d);
+#pragma unroll
+    for (int q = 0; q < D3_KG; ++q) {
+      const float dx = tj[q].x - ti[q].x, dy = tj[q].y - ti[q].y, dz = tj[q].z - ti[q].z;
+      const float td = fmaf(P.ux, dx, fmaf(P.uy, dy, P.uz * dz));
+      const float c1 = fmaf(ti[q].w + tj[q].w, s1, gs2 * td);
+      f[q][0] = fmaf(c1, P.ux, fmaf(c2, fmaf(-P.ux, td, dx) * invd, f[q][0]));
+      f[q][1] = fmaf(c1, P.uy, fmaf(c2, fmaf(-P.uy, td, dy) * invd, f[q][1]));
+      f[q][2] = fmaf(c1, P.uz, fmaf(c2, fmaf(-P.uz, td, dz) * invd, f[q][2]));
+    }
+  };
+  for (int m = lane; m < cnt; m += 128) {
+    const bool v1 = m + 64 < cnt;
+    const int m1 = v1 ? m + 64 : m;
+    const int j0 = nb_idx[row + m], j1 = nb_idx[row + m1];
+    const int h0 = c ? nb_shift[row + m] : 0, h1 = c ? nb_shift[row + m1] : 0;
+    const float4 x0 = xs4[j0], x1 = xs4[j1];
+    const float g0 = dEdcn[j0], g1 = dEdcn[j1];
+    float4 t0[D3_KG], t1[D3_KG];
+#pragma unroll
+    for (int q = 0; q < D3_KG; ++q) {
+      t0[q] = tg4[(size_t)G.k[q] * n_atoms + j0];
+      t1[q] = tg4[(size_t)G.k[q] * n_atoms + j1];
+    }
+    const float rc0 = T.rcov[__float_as_int(x0.w)], rc1 = T.rcov[__float_as_int(x1.w)];
+    term(d3_geom(x0, j0, h0, C, xi, yi, zi, cutoff, true), rc0, g0, t0);
+    term(d3_geom(x1, j1, h1, C, xi, yi, zi, cutoff, v1), rc1, g1, t1);
+  }
+#pragma unroll
+  for (int q = 0; q < D3_KG; ++q) {
+    const float f0 = wave_sum(f[q][0]), f1 = wave_sum(f[q][1]), f2 = wave_sum(f[q][2]);
+    if (lane == q && G.ok[q]) {
+      const size_t o = ((size_t)G.k[q] * n_atoms + i) * 3;
+      txbar[o + 0] -= f0;
+      txbar[o + 1] -= f1;
+      txbar[o + 2] -= f2;
+    }
+  }
+}
+
+int launch_dftd3_tangent(hipStream_t s, const int* mol_idx, const float* cell, int n_cell, const int* nb_idx, const int* nb_shift,
+                         const int* nb_cnt, int cap, D3Tables T, D3Params P, float cutoff, int n_atoms, const float4* xs4,
+                         const float* d3w, const float* dEdcn, const float* tv, int n_dir, float4* tcn4, float4* tg4, float* txbar) {
+  const dim3 grid(ceil_div(n_atoms, 4), ceil_div(n_dir, D3_KG)), block(256);
+  hipLaunchKernelGGL(d3_tcn_kernel, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff, n_atoms, tv,
+                     n_dir, tcn4);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(d3_tpair_kernel, grid, block, (size_t)4 * T.ns * 25 * sizeof(float), s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift,
+                     nb_cnt, cap, T, P, cutoff, n_atoms, d3w, tcn4, n_dir, tg4, txbar);
+  AIMNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(d3_tcnforce_kernel, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff, n_atoms,
+                     dEdcn, tg4, n_dir, txbar);
+  AIMNET_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace aimnet

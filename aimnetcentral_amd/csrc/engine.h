@@ -177,6 +177,9 @@ struct aimnet_engine {
   aimnet_embedding_tangent emb_tangent{};
   // aimnet_engine_set_pme_tangent: aimnet_engine_hvp carries AIMNET_COULOMB_PME (tangent_plan.h: pme); off: it refuses, as it always has
   bool pme_tangent_on = false;
+  // aimnet_engine_set_dftd3_tangent: the dispersion block of aimnet_engine_hvp is the analytic tangent of d3.hip (tangent_plan.h:
+  // d3_analytic); off: the central difference of the D3 gradient, as it always has been
+  bool d3_tangent_on = false;
   float* unit_cell = nullptr;  // 3 x 3 identity (device): "cell" of the virial sums of a decomposed evaluation
   double* sae;
   // species slots of the pass-0 moment backward: slot = rank of the atomic number among the embedding rows that

@@ -1270,6 +1270,12 @@ int aimnet_engine_set_pme_tangent(aimnet_engine* e, int32_t on) {
   return AIMNET_OK;
 }
 
+int aimnet_engine_set_dftd3_tangent(aimnet_engine* e, int32_t on) {
+  if (!e) return AIMNET_E_INVALID;
+  e->d3_tangent_on = on != 0;
+  return AIMNET_OK;
+}
+
 int aimnet_engine_set_dftd3(aimnet_engine* e, const aimnet_dftd3_tables* t) {
   if (!e || !t || t->n_z <= 0 || !t->c6ab || !t->cn_ref || !t->rcov || !t->r4r2) {
     set_last_error("set_dftd3: null argument");

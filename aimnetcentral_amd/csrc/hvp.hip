@@ -884,6 +884,7 @@ struct HvpWs {
   float *d3c_x, *d3c_w, *d3c_dEdcn, *d3c_g, *d3_scale;
   float4* d3c_xs;
   double* d3c_e;
+  float4 *d3t_cn, *d3t_g;  // plan: d3_analytic - [K][N] (v_i, t_cn_i) and (v_i, t_G_i) of d3.hip's tangent passes (no replicas then)
   size_t total;
 };
 
@@ -983,7 +984,16 @@ void tangent_layout(const aimnet_engine* e, int N, int n_mol, int K, const Tange
       W.pt.field = c.take<double>(n * 10);
       if (P.pme_qtot) W.qsum = c.take<float>(n);
     }
-    if (P.d3_block) {
+    if (P.d3_analytic) {  // the one list, the primal's per-atom buffers, and 32 bytes per (direction, atom)
+      const size_t cap_d3 = (size_t)P.cap_d3;
+      W.d3_idx = c.take<int>(n * cap_d3), W.d3_shift = c.take<int>(n * cap_d3), W.d3_cnt = c.take<int>(n);
+      W.aslot = c.take<int>(n), W.present_part = c.take<unsigned long long>((n + 255) / 256);
+      W.d3c_g = c.take<float>(n * 3);
+      W.d3c_w = c.take<float>(n * 12), W.d3c_dEdcn = c.take<float>(n);
+      W.d3c_xs = c.take<float4>(n);
+      W.d3c_e = c.take<double>(n);
+      W.d3t_cn = c.take<float4>(kn), W.d3t_g = c.take<float4>(kn);
+    } else if (P.d3_block) {
       const size_t cn = 4 * kn, cap_d3 = (size_t)P.cap_d3;
       W.d3_idx = c.take<int>(n * cap_d3), W.d3_shift = c.take<int>(n * cap_d3), W.d3_cnt = c.take<int>(n);
       W.aslot = c.take<int>(n), W.present_part = c.take<unsigned long long>((n + 255) / 256);
@@ -1306,13 +1316,27 @@ int Tangent::backward() {
   return 0;
 }
 
-// the dispersion block: central difference of the D3 gradient over all directions in one batch (see the kernels)
+// the dispersion block: central difference of the D3 gradient over all directions in one batch (see the kernels) - or, armed
+// (plan: d3_analytic), the analytic tangent of d3.hip on the one list
 int Tangent::d3_block(bool want_forces) {
-  const int cap_d3 = P.cap_d3, NC = 4 * K * N;
+  const int cap_d3 = P.cap_d3;
   const float h = 4e-3f;
   const dim3 b256(256);
   RC(launch_nlist(s, N, n_mol, mol_c, in->cell, n_cell, in->pbc, opt->d3_cutoff, -1.0f, cap_d3, N, 0, W.nl, W.d3_idx, W.d3_shift,
                   W.d3_cnt, status + 4, status + 5));
+  if (P.d3_analytic) {
+    // armed: the primal term once at x - the evaluation's own launches; with forces wanted they land in xbar exactly as the launch at
+    // the end of the finite-difference block adds them, otherwise in a scratch row - then the three tangent passes of d3.hip
+    const D3Params dp = d3_params(opt);
+    float* g = want_forces ? W.xbar : W.d3c_g;
+    if (!want_forces) AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_g, 0, (size_t)N * 3 * sizeof(float), s));
+    AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_e, 0, (size_t)N * sizeof(double), s));
+    RC(launch_dftd3(s, true, false, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp,
+                    opt->d3_cutoff, N, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, g, nullptr, false, cp, nullptr, nullptr));
+    return launch_dftd3_tangent(s, mol_c, in->cell, n_cell, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp, opt->d3_cutoff, N,
+                                W.d3c_xs, W.d3c_w, W.d3c_dEdcn, vectors, K, W.d3t_cn, W.d3t_g, W.txbar);
+  }
+  const int NC = 4 * K * N;  // (tangent_validate: below 2^31 on this branch)
   hipLaunchKernelGGL(hvp_d3_scale_kernel, dim3(K), b256, 0, s, vectors, N, K, W.d3_scale);
   AIMNET_LAUNCH_CHECK();
   hipLaunchKernelGGL(hvp_d3_replicate_kernel, dim3(N, 4 * K), dim3(64), 0, s, W.nl.xw, vectors, W.d3_scale, mol_c, W.aslot, W.d3_idx,
@@ -1373,6 +1397,7 @@ TangentRequest tangent_request(TangentEntry entry, const aimnet_engine* e, int N
   }
   r.pme_tangent = entry == TangentEntry::Hvp && e->pme_tangent_on;
   r.pme_max_mesh = opt->pme_max_mesh; r.pme_part = PME_PART;
+  r.d3_tangent = entry == TangentEntry::Hvp && e->d3_tangent_on;
   if (!in) return r;
   r.pbc = in->cell != nullptr; r.n_cell = in->n_cell;
   const bool mesh_armed = opt->coulomb == AIMNET_COULOMB_PME && r.pme_tangent;
@@ -1437,6 +1462,29 @@ int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_ev
   RC(t.backward());
   if (t.P.embedding) RC(t.embedding_sites());
   if (t.P.d3_block) RC(t.d3_block(forces != nullptr));
+  return t.write_hvp(hv, forces);
+}
+
+int aimnet_debug_dftd3_tangent(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const float* vectors,
+                               int32_t n_vec, float* hv, float* forces, int32_t* status, void* workspace, size_t workspace_bytes,
+                               void* hip_stream) {
+  if (!e || !in || !opt || !vectors || !hv || !status || !workspace || n_vec <= 0) return AIMNET_E_INVALID;
+  if (!opt->dftd3) {
+    set_last_error("debug_dftd3_tangent: options.dftd3 is off");
+    return AIMNET_E_INVALID;
+  }
+  TangentRequest rq = tangent_request(TangentEntry::Hvp, e, in->n_atoms, in->n_mol, n_vec, opt, in);
+  if (!rq.d3_tangent) {
+    set_last_error("debug_dftd3_tangent: arm the engine first (aimnet_engine_set_dftd3_tangent(e, 1)): the workspace is the armed one");
+    return AIMNET_E_INVALID;
+  }
+  rq.hv = true; rq.forces = forces != nullptr;
+  Tangent t{e, (hipStream_t)hip_stream, in, opt, vectors, n_vec, status};
+  RC(t.open(rq, workspace, workspace_bytes));
+  RC(t.lists());  // (the block reads the wrapped coordinates, the species slots and the bins of the sweep's own list build)
+  AIMNET_HIP_CHECK(hipMemsetAsync(t.W.txbar, 0, t.kn() * 3 * sizeof(float), t.s));
+  AIMNET_HIP_CHECK(hipMemsetAsync(t.W.xbar, 0, (size_t)t.N * 3 * sizeof(float), t.s));
+  RC(t.d3_block(forces != nullptr));
   return t.write_hvp(hv, forces);
 }
 

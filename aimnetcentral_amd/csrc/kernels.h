@@ -409,6 +409,13 @@ int launch_dftd3(hipStream_t s, bool grad, bool stress, const float* xw, const i
                  bool cn_done = false,
                  const DdLink* dd = nullptr);  // domain decomposition: halo rows of d3w / dE/dcn come from their owners (dd->fn, what = 2)  // cn_done: d3w was filled by the list build (D3CnRider): no d3_cn_kernel launch
 // with_dsf: the DSF Coulomb pair sum (cutoff == cp.dsf_rc) is evaluated in the same pair pass; adds to ecoul / qbar too
+// d3.hip: the analytic tangent of the term's gradient (hvp.hip; armed by aimnet_engine_set_dftd3_tangent).  After launch_dftd3(grad =
+// true) on the same list (xs4, d3w, dEdcn: its outputs): H_d3 v^k ADDED onto txbar [n_dir][n_atoms][3] for tv [n_dir][n_atoms][3], the
+// cell fixed.  tcn4 / tg4 [n_dir][n_atoms]: (v_i, t_cn_i) / (v_i, t_G_i), written and read here.  No atomics; bitwise repeatable and
+// independent of how the directions are split over calls.
+int launch_dftd3_tangent(hipStream_t s, const int* mol_idx, const float* cell, int n_cell, const int* nb_idx, const int* nb_shift,
+                         const int* nb_cnt, int cap, D3Tables T, D3Params P, float cutoff, int n_atoms, const float4* xs4,
+                         const float* d3w, const float* dEdcn, const float* tv, int n_dir, float4* tcn4, float4* tg4, float* txbar);
 // Independent work that rides on the SR-Coulomb launch (role-dispatched blocks behind the pair blocks; a kernel boundary costs
 // 4-5 us on the device): the last energy-head layer k -> 1 with its adjoint seed zbar = w * d (n_head_blocks = ceil(n_atoms / 4), 0 = none) and the charge stream of the
 // list-free DSF walk (n_stream_blocks = ceil(n_atoms / 256), 0 = none; xs / xq = NlistBuffers::xs / sorted_tmp_xq)

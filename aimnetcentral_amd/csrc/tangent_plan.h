@@ -31,6 +31,9 @@ struct TangentRequest {
   // holds ewald_args_check of the inputs as for Ewald, and of the options:
   bool pme_tangent;
   int pme_max_mesh, pme_part;  // options.pme_max_mesh; PME_PART (kernels.h)
+  // aimnet_engine_set_dftd3_tangent armed the sweep for the dispersion term (read with dftd3 != 0 and Hvp only): its block is the
+  // analytic tangent of csrc/d3.hip on the one D3 list, not the central difference over 4 n_vec displaced copies
+  bool d3_tangent;
 };
 
 // ---- argument checks: 0, or AIMNET_E_INVALID with the message in msg.  Nothing has been launched when they run --------------------
@@ -64,11 +67,13 @@ inline int tangent_validate(const TangentRequest& r, char* msg, size_t n) {
                        hvp ? "lists" : "list");
   if (d3 && !r.d3_tables) return plan_reject(msg, n, "hvp: DFT-D3 requested but aimnet_engine_set_dftd3 was never called");
   // the tangent kernels index the directions with grid.y (HIP limit 65535); the D3 block replicates every direction four times
-  const int k_max = d3 ? 16383 : 65535;
+  // (armed, aimnet_engine_set_dftd3_tangent: nothing is replicated, and the two limits of the replicas do not apply)
+  const bool d3_fd = d3 && !r.d3_tangent;
+  const int k_max = d3_fd ? 16383 : 65535;
   if (r.n_vec > k_max)
     return plan_reject(msg, n, "%s: at most %d directions per sweep (%d given): split them over several calls", who, k_max, r.n_vec);
   if (hvp) {
-    if (d3 && 4 * (size_t)r.n_vec * (size_t)r.N * (size_t)std::max(1, r.max_nb_d3) >= (size_t)INT32_MAX)
+    if (d3_fd && 4 * (size_t)r.n_vec * (size_t)r.N * (size_t)std::max(1, r.max_nb_d3) >= (size_t)INT32_MAX)
       return plan_reject(msg, n, "hvp: n_vec * n_atoms * max_nb_d3 too large for one sweep (split the directions)");
     if (r.coulomb == AIMNET_COULOMB_DSF && r.max_nb_lr <= 0)
       return plan_reject(msg, n,
@@ -132,6 +137,7 @@ struct TangentPlan {
   bool ewald, ewald_qtot;   // Ewald stages; a two-channel model: the structure factors see alpha + beta, formed in a buffer of its own
   int ewald_max_k;          // Ewald k entries (0: method not chosen)
   bool d3_block;            // the external DFT-D3 block (central difference of its gradient over all directions)
+  bool d3_analytic;         // ... armed: the block is the analytic tangent (d3.hip); tcn4 / tg4 [K][N] take the place of the 4 K replicas
   bool want_species;        // species slots + present masks are formed (DFT-D3)
   bool bbox;                // non-periodic: bounding-box cell grid
   bool embedding;           // the embedding's seeds join the Coulomb seeds (armed), and after the backward its site pass
@@ -153,6 +159,7 @@ inline TangentPlan tangent_plan(const TangentRequest& r) {
   P.cap = std::max(1, r.max_nb);
   P.cap_lr = hvp ? std::max(0, r.max_nb_lr) : 0;
   P.d3_block = hvp && r.dftd3 != 0;
+  P.d3_analytic = P.d3_block && r.d3_tangent;
   P.cap_d3 = P.d3_block ? std::max(1, r.max_nb_d3) : 0;
   P.ewald = hvp && r.coulomb == AIMNET_COULOMB_EWALD;
   P.pme = hvp && r.coulomb == AIMNET_COULOMB_PME && r.pme_tangent;

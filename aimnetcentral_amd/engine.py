@@ -546,7 +546,8 @@ class HipEngine(capacity.Capacities):
 
     # ------------------------------------------------------------------------------------------
     HVP_BYTES_BUDGET = 6 << 30  # workspace of one tangent sweep; more directions than fit are processed in several sweeps
-    HVP_MAX_DIRECTIONS = 65535  # the tangent kernels put the direction index in grid.y (HIP limit 65535; 4 K with DFT-D3: 16383)
+    # the tangent kernels put the direction index in grid.y (HIP limit 65535; 4 K with the finite-difference DFT-D3 block: 16383)
+    HVP_MAX_DIRECTIONS = 65535
     # one direction costs ~3/4 us per atom (7.5 ms on 10 080 atoms, profiles/r3_hvp.md): calls that would run for more than
     # this many seconds are announced (or refused, HVP_ON_LONG) (a dense Hessian of a 10 k-atom crystal is 30 240 directions = minutes)
     HVP_MAX_SECONDS = 120.0
@@ -555,7 +556,8 @@ class HipEngine(capacity.Capacities):
     def hvp(self, coord, numbers, mol_idx, charge, vectors, cell=None, pbc=(True, True, True), coulomb: str = "simple",
             dsf_rc: float = 15.0, dsf_alpha: float = 0.2, want_forces: bool = False,
             dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6,
-            embedding: dict[str, Any] | None = None, pme_tangent: bool = False) -> dict[str, Any]:
+            embedding: dict[str, Any] | None = None, pme_tangent: bool = False, d3_tangent: bool = False,
+            _d3_block_only: bool = False) -> dict[str, Any]:
         """Analytic Hessian-vector products (csrc/hvp.hip, aimnet_engine_hvp): vectors [K, N, 3] -> hv [K, N, 3] on the device
         (+ the forces of the same sweep with `want_forces`).  Inputs as `eval` (`pbc`: three flags or per-system [n_cell, 3]);
         with `dftd3` the dispersion block is added as a central difference of the D3 gradient inside the same call.  The K
@@ -565,6 +567,10 @@ class HipEngine(capacity.Capacities):
         (aimnet_engine_set_pme_tangent, csrc/pme.hip): the real-space term on a list of cutoff r_c <= 10 A, the mesh tangents of
         every direction at 40 bytes per mesh point, direction and system (they enter the split by HVP_BYTES_BUDGET); status[7]
         grows the mesh capacity and the sweep repeats, as in `eval`.  The engine's switch is on for the sweeps of such a call only.
+        `d3_tangent=True` (with `dftd3`) arms the analytic dispersion block (aimnet_engine_set_dftd3_tangent, csrc/d3.hip): three
+        tangent passes over the one D3 list instead of the central difference over four displaced copies of it per direction - 32
+        bytes per direction and atom instead of the replicas (the split by HVP_BYTES_BUDGET sees the smaller figure), up to
+        HVP_MAX_DIRECTIONS directions per sweep; also for the sweeps of this call only.
         `embedding`: the dict of `eval`, carried through the sweep with the atoms moving and the sites clamped
         (include/aimnet_hip.h, aimnet_embedding_tangent): a `potential` needs `potential_grad` and `potential_hess` [N,6] (xx, yy,
         zz, xy, xz, yz) or [N,3,3] beside it (zeros for a uniform field).  hv and the forces then include the term; `want_ext_hv`
@@ -614,17 +620,31 @@ class HipEngine(capacity.Capacities):
             arm(k0, kc)  # (the embedding's tangent struct names this sweep's slice of ext_hv)
             return self.lib.aimnet_engine_hvp(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
                                               hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None, *tail)
-        kmax = self.HVP_MAX_DIRECTIONS // (4 if dftd3 is not None else 1)  # grid.y limit of the tangent kernels
+        d3_armed = bool(d3_tangent) and dftd3 is not None
+        if _d3_block_only:  # aimnet_debug_dftd3_tangent: the armed block alone (tests)
+            if not d3_armed:
+                raise ValueError("HipEngine.hvp: the dispersion block alone needs dftd3 and d3_tangent=True")
+
+            def call(opt, k0, kc, *tail):  # noqa: F811
+                return self.lib.aimnet_debug_dftd3_tangent(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
+                                                           hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None,
+                                                           *tail)
+        # grid.y limit of the tangent kernels (the finite-difference D3 block replicates every direction four times)
+        kmax = self.HVP_MAX_DIRECTIONS // (4 if dftd3 is not None and not d3_armed else 1)
         if method == _lib.COULOMB_PME:  # a (direction, system) slice of the mesh transforms is a grid.y index
             kmax = max(1, min(kmax, self.HVP_MAX_DIRECTIONS // n_mol))
         mesh = method == _lib.COULOMB_PME  # (armed: unarmed requests were refused above)
         try:
             if mesh:  # the engine's switch is on for the sweeps of this call only: no state leaks from one call into the next
                 _lib.check(self.lib.aimnet_engine_set_pme_tangent(self._h, 1), "aimnet_engine_set_pme_tangent")
+            if d3_armed:  # (likewise)
+                _lib.check(self.lib.aimnet_engine_set_dftd3_tangent(self._h, 1), "aimnet_engine_set_dftd3_tangent")
             self._tangent_sweeps("hvp", self.lib.aimnet_engine_hvp_workspace_bytes, rq, K, kmax, call)
         finally:
             if mesh:
                 self.lib.aimnet_engine_set_pme_tangent(self._h, 0)
+            if d3_armed:
+                self.lib.aimnet_engine_set_dftd3_tangent(self._h, 0)
             if embedding is not None:
                 self.lib.aimnet_engine_set_embedding(self._h, None)  # (disarms the tangent too)
         res = {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}

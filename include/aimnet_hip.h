@@ -328,6 +328,31 @@ int aimnet_engine_set_embedding_tangent(aimnet_engine* e, const aimnet_embedding
  * points per axis.  aimnet_engine_eval and aimnet_engine_charge_response do not read the switch. */
 int aimnet_engine_set_pme_tangent(aimnet_engine* e, int32_t on);
 
+/* DFT-D3 in the analytic Hessian sweep.  Arming is explicit, as for the mesh: by default (and after on = 0) the dispersion block of
+ * aimnet_engine_hvp is the 4-point central difference of the D3 gradient over 4 n_vec displaced copies of the D3 list, with its
+ * limits (n_vec <= 16383, 4 n_vec n_atoms max_nb_d3 < 2^31) - every launch, result and refusal as before.  After
+ * aimnet_engine_set_dftd3_tangent(e, 1) the block is the analytic tangent of the term's gradient on the one list (csrc/d3.hip): the
+ * evaluation's own three passes once at x (they leave the weights, dE/dcn = G and, when forces are asked for, the same forces bit
+ * for bit), then three tangent passes.  With d in Bohr inside P and sigma, k = Hartree / 2, u from i to j, the cell fixed:
+ *   primal   E = k sum_ordered -C6_ij P_ij,  P = (s6 / (d^6 + R0^6) + s8 Q / (d^8 + R0^8)) S5(d),  cn_i = sum_j sigma_ij,
+ *            G_i = dE/dcn_i = 2k sum_j -P_ij A_i,   dE/dx_i = -2k sum_j (-C6 P') u - sum_j (G_i + G_j) sigma' u
+ *   C6       W_ab = w_i[a] w_j[b] over the kept (a, b) (the -12 cut and c6ref != 0: a constant of the evaluation), g_i[a] = -8 (cn_i -
+ *            cnref_i[a]);  N_. = sum c6ref d_.W, D_. = sum d_.W with d_i W = g_i W, d_ii W = (g_i^2 - 8) W, d_ij W = g_i g_j W;
+ *            C6 = N / D, A_i = (N_i - C6 D_i) / D, A_j likewise, B_ii = (N_ii - C6 D_ii - 2 A_i D_i) / D,
+ *            B_ij = (N_ij - C6 D_ij - A_i D_j - A_j D_i) / D;  pairs with D <= 1e-12 give nothing
+ *   along v  Delta = v_j - v_i, t_d = u . Delta, t_u = (Delta - u t_d) / d
+ *            t_cn_i = sum_j sigma' t_d,   t_C6 = A_i t_cn_i + A_j t_cn_j,
+ *            t_G_i = 2k sum_j [-P' t_d A_i - P (B_ii t_cn_i + B_ij t_cn_j)]
+ *            (H_d3 v)_i = -2k sum_j [(-t_C6 P' - C6 P'' t_d) u + (-C6 P') t_u]
+ *                         - sum_j [(t_G_i + t_G_j) sigma' u + (G_i + G_j)(sigma'' t_d u + sigma' t_u)]
+ * P'' includes the second derivative of the quintic switch (C^2: the block is continuous across the window).  fp32 throughout, a wave
+ * per (atom, group of four directions), no atomics: H_d3 v is bitwise repeatable and independent of how the directions are grouped or
+ * split over calls.  Armed, n_vec <= 65535 and the 2^31 limit of the replicas is gone; the workspace holds 32 bytes per (direction,
+ * atom) for the block instead of 4 (8 max_nb_d3 + 60) (aimnet_engine_hvp_workspace_bytes counts what the engine's state asks for).
+ * Caller-supplied matrices stay refused; strain tangents and domain decomposition are not carried.  aimnet_engine_eval and
+ * aimnet_engine_charge_response do not read the switch. */
+int aimnet_engine_set_dftd3_tangent(aimnet_engine* e, int32_t on);
+
 /* Bytes of scratch `aimnet_engine_eval` needs for the given problem size. */
 size_t aimnet_engine_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_cell,
                                      const aimnet_eval_options* opt);
@@ -518,6 +543,14 @@ int aimnet_debug_pme_recip(const float* xw, const float* q, const int* order, co
 int aimnet_debug_pme_tangent(const float* xw, const float* q, const float* tq, const float* v, const int* order, const float* cell,
                              float total_charge, int n_atoms, int n_dir, float accuracy, int max_mesh, double* field, double* tphi,
                              double* tg, double* host_info, void* hip_stream);
+/* aimnet_debug_dftd3_tangent (csrc/d3.hip through csrc/hvp.hip): the armed dispersion block ALONE.  Arguments as aimnet_engine_hvp
+ * (inputs: coordinates, numbers, mol_idx, cell; options: dftd3 = 1 with its parameters and max_nb_d3; vectors [n_vec][n][3]); the
+ * engine must be armed (aimnet_engine_set_dftd3_tangent) and hold the tables, the workspace is aimnet_engine_hvp_workspace_bytes'.  It
+ * builds the sweep's lists, runs the primal D3 passes at x and the three tangent passes, and writes hv = H_d3 v [n_vec][n][3] and, if
+ * given, forces = the D3 forces [n][3] - no model, no Coulomb term.  status as aimnet_engine_hvp (status[4], status[5]: the D3 rows). */
+int aimnet_debug_dftd3_tangent(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const float* vectors,
+                               int32_t n_vec, float* hv, float* forces, int32_t* status, void* workspace, size_t workspace_bytes,
+                               void* hip_stream);
 
 /* Test hooks for the conv kernels that every evaluation runs (csrc/conv.hip): ONE launch each, on the given stream, on caller-allocated
  * device buffers in the layouts csrc/kernels.h documents; nothing is allocated, copied or synchronised.  Common arguments: nq = charge
