@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_set_embedding",
     "aimnet_embedding_tangent_scratch_bytes",
     "aimnet_engine_set_embedding_tangent",
+    "aimnet_embedding_periodic_scratch_bytes",
+    "aimnet_engine_set_embedding_periodic",
     "aimnet_engine_set_pme_tangent",
     "aimnet_engine_set_dftd3_tangent",
     "aimnet_neighbor_list",
@@ -202,6 +204,18 @@ class EmbeddingTangent(C.Structure):
     ]
 
 
+class EmbeddingPeriodic(C.Structure):
+    """aimnet_embedding_periodic: arms aimnet_engine_eval for sites periodic with the cell; device pointers, caller-owned scratch."""
+
+    _fields_ = [
+        ("accuracy", C.c_float),
+        ("max_k", C.c_int32),
+        ("status", C.c_void_p),
+        ("scratch", C.c_void_p),
+        ("scratch_bytes", C.c_size_t),
+    ]
+
+
 class Outputs(C.Structure):
     _fields_ = [
         ("energy", C.c_void_p),
@@ -273,6 +287,10 @@ def load() -> C.CDLL:
     lib.aimnet_embedding_tangent_scratch_bytes.argtypes = [i32, i32, i32]
     lib.aimnet_engine_set_embedding_tangent.restype = C.c_int
     lib.aimnet_engine_set_embedding_tangent.argtypes = [vp, C.POINTER(EmbeddingTangent)]
+    lib.aimnet_embedding_periodic_scratch_bytes.restype = sz
+    lib.aimnet_embedding_periodic_scratch_bytes.argtypes = [i32, i32, i32, i32]
+    lib.aimnet_engine_set_embedding_periodic.restype = C.c_int
+    lib.aimnet_engine_set_embedding_periodic.argtypes = [vp, C.POINTER(EmbeddingPeriodic)]
     lib.aimnet_debug_gemm.restype = C.c_int
     lib.aimnet_debug_gemm.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.aimnet_debug_split_bf3.restype = C.c_int

@@ -510,6 +510,28 @@ class AIMNet2Calculator:
         self._embedding_hessian_mode = mode
         self._embedding_mixed_block = bool(mixed_block) and mode is not None
 
+    # point-charge sites with a cell: None (refused) or "ewald" (the sites are periodic with the cell); see set_embedding_periodic
+    _embedding_periodic_mode = None
+    _embedding_periodic_accuracy = 1e-6
+
+    def set_embedding_periodic(self, mode: str | None = None, accuracy: float = 1e-6) -> None:
+        """Whether `ext_coord` / `ext_charge` are accepted together with a cell.  `None` (the default): they raise ValueError, the
+        sites have no images.  "ewald": a fully periodic input takes the sites of a system as periodic with its cell - E_emb =
+        sum_i q_i phi_i with phi the Ewald potential of the site lattice at `accuracy`, its neutralising background included (the
+        sites may carry a net charge), the exact gradient and the forces on the sites (include/aimnet_hip.h,
+        aimnet_embedding_periodic); flat and (B,N,3) layouts, per-system cells.  Partial `pbc` raises ValueError; `stress=True`,
+        `hessian=True`, `hessian_vector_product` and domain decomposition with periodic sites raise NotImplementedError.  Not
+        carried: the site-site energy, polarisation of the charges by the field."""
+        if mode not in (None, "ewald"):
+            raise ValueError(f"set_embedding_periodic: mode must be None or 'ewald', got {mode!r}")
+        if not (0.0 < float(accuracy) < 1.0):
+            raise ValueError("set_embedding_periodic: accuracy must lie in (0, 1)")
+        self._embedding_periodic_mode, self._embedding_periodic_accuracy = mode, float(accuracy)
+
+    def _periodic_sites(self, data: dict[str, Any]) -> bool:
+        """Point-charge sites with a cell while set_embedding_periodic("ewald") is on."""
+        return self._embedding_periodic_mode == "ewald" and data.get("ext_coord") is not None and data.get("cell") is not None
+
     def _embedding_hessian_ok(self, data: dict[str, Any]) -> bool:
         """Second derivatives of this embedded input run: the mode is set and the analytic sweep is what would carry them."""
         return (self._embedding_hessian_mode == "fixed_sites" and self.hvp_method == "analytic" and self._dd is None and
@@ -575,7 +597,7 @@ class AIMNet2Calculator:
         if mi is not None and xc is None:
             raise ValueError("ext_mol_idx given without ext_coord")
         if xc is not None:
-            if cell is not None:
+            if cell is not None and self._embedding_periodic_mode != "ewald":
                 raise ValueError("ext_coord / ext_charge take non-periodic input (the sites have no images): pass ext_potential / "
                                  "ext_potential_grad with a cell")
             if batch:
@@ -594,6 +616,8 @@ class AIMNet2Calculator:
                 if mi is None and data.get("mol_idx") is not None and int(torch.as_tensor(data["charge"]).numel()) > 1:
                     raise ValueError("ext_mol_idx is required when mol_idx names more than one molecule")
             emb.update(ext_coord=xc, ext_charge=qc, want_ext_forces=forces)
+            if cell is not None:  # (set_embedding_periodic("ewald")) the sites are periodic with the cell
+                emb["ewald_accuracy"] = self._embedding_periodic_accuracy
             if mi is not None:
                 emb["ext_mol_idx"] = mi
         if pg is not None and pot is None:
@@ -695,6 +719,9 @@ class AIMNet2Calculator:
             self._validate_species_and_charge(data)
         self._maybe_warn_mult_ignored(data)
         embedded = self._has_embedding(data)
+        if self._periodic_sites(data) and (stress or hessian or self._dd is not None):
+            raise NotImplementedError("periodic embedding sites (set_embedding_periodic) are carried by energies and forces only: not "
+                                      "with stress=True, hessian=True or domain decomposition")
         if embedded and (stress or self._dd is not None or (hessian and not self._embedding_hessian_ok(data))):
             raise NotImplementedError("electrostatic embedding (ext_coord / ext_charge / ext_potential) is carried by energies and "
                                       "forces only: not with stress=True, hessian=True or domain decomposition")
@@ -714,6 +741,8 @@ class AIMNet2Calculator:
                           "call set_lrcoulomb_method() to select a periodic method persistently.", stacklevel=2)
         lr.require_cell()
         pbc3 = self._normalize_pbc(d.get("pbc"), 1 if (cell is None or cell.ndim == 2) else int(cell.shape[0]))
+        if emb is not None and "ewald_accuracy" in emb and not (isinstance(pbc3, tuple) and all(pbc3)):
+            raise ValueError("periodic embedding sites (set_embedding_periodic) need a cell that is periodic along all three axes")
         if self._dd is not None:
             if (batch is not None or charge.shape[0] != 1 or cell is None or cell.ndim != 2 or pbc3 != (True, True, True) or ext_lists or
                     lr.method not in (None, "dsf") or defer_status):
@@ -963,6 +992,9 @@ class AIMNet2Calculator:
         if create_graph:
             raise NotImplementedError("create_graph=True needs autograd through the model; the native engine has none")
         embedded = self._has_embedding(data)
+        if self._periodic_sites(data):
+            raise NotImplementedError("hessian_vector_product: periodic embedding sites (set_embedding_periodic) are not carried by "
+                                      "the tangent sweep")
         if embedded and not self._embedding_hessian_ok(data):  # (set_embedding_hessian("fixed_sites") switches the term on)
             raise NotImplementedError("hessian_vector_product: the electrostatic-embedding term is not carried by the tangent sweep")
         if validate_species:

@@ -115,6 +115,7 @@ class Capacities:
         self._max_nb_lr: dict[float, int] = {}
         self._ewald_nb_lr = 0     # row capacity of the real-space list of Ewald summation in `hvp` (0: sized from r_c at first use)
         self._ewald_max_k = 8192  # capacity of the Ewald k arrays (entries; grows to what status[7] reports)
+        self._emb_max_k = 8192    # of the periodic embedding's own k arrays (grows to what its status[0] reports, HipEngine._eval_embedded)
         self._pme_max_mesh = PME_START_MESH  # of one system's PME mesh (points; every system of a batch gets a slice)
 
     def lr_capacity(self, rc: float) -> int:

@@ -79,6 +79,25 @@ __device__ __forceinline__ float erf_fast(float x) {
   return a < 0.921875f ? p * x : big;
 }
 
+// erfc(al d) = exp(-x^2) t P(t), t = 1 / (1 + x / 2), x = al d: the degree-9 fit of erfcx(x) / t on x in [0, 6.5] of the list-free
+// walk (model.hip, coulomb_dsf_walk_kernel: 6.5e-9 relative, the fp32 Horner evaluation adds 2.5e-7).  ex = exp(-al^2 d^2) comes
+// back too: the derivative of the pair term needs it.
+__device__ __forceinline__ float erfc_walk(float al, float d, float d2, float& ex) {
+  ex = __builtin_amdgcn_exp2f(-1.4426950408889634f * al * al * d2);
+  const float tt = __builtin_amdgcn_rcpf(fmaf(0.5f * al, d, 1.0f));
+  float pe = 2.672036890e-02f;
+  pe = fmaf(pe, tt, -2.020067459e-01f);
+  pe = fmaf(pe, tt, 6.150174393e-01f);
+  pe = fmaf(pe, tt, -9.195323909e-01f);
+  pe = fmaf(pe, tt, 6.300562657e-01f);
+  pe = fmaf(pe, tt, -2.111610618e-01f);
+  pe = fmaf(pe, tt, 2.648643249e-01f);
+  pe = fmaf(pe, tt, 2.301390953e-01f);
+  pe = fmaf(pe, tt, 2.838921720e-01f);
+  pe = fmaf(pe, tt, 2.820105286e-01f);
+  return pe * tt * ex;
+}
+
 // exact-erf GELU and its derivative (torch.nn.GELU default, aimnet/modules/core.py:27)
 __device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.0f + erf_fast(z * 0.70710678118654752f)); }
 __device__ __forceinline__ void gelu_and_grad(float z, float& h, float& d) {

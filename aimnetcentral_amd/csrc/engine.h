@@ -175,6 +175,9 @@ struct aimnet_engine {
   // aimnet_engine_set_embedding_tangent: aimnet_engine_hvp carries the embedding (hvp.hip, Tangent::embedding_seeds); off with emb_on
   bool emb_tangent_on = false;
   aimnet_embedding_tangent emb_tangent{};
+  // aimnet_engine_set_embedding_periodic: aimnet_engine_eval sums the sites' periodic images (embed.hip); off with emb_on
+  bool emb_periodic_on = false;
+  aimnet_embedding_periodic emb_periodic{};
   // aimnet_engine_set_pme_tangent: aimnet_engine_hvp carries AIMNET_COULOMB_PME (tangent_plan.h: pme); off: it refuses, as it always has
   bool pme_tangent_on = false;
   // aimnet_engine_set_dftd3_tangent: the dispersion block of aimnet_engine_hvp is the analytic tangent of d3.hip (tangent_plan.h:

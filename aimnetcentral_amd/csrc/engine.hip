@@ -813,6 +813,20 @@ int Eval::embedding() {
   const aimnet_embedding& m = e->emb;
   EmbedBuffers b;
   embed_carve(b, (char*)m.scratch, N, n_mol, m.n_ext);
+  if (e->emb_periodic_on && m.n_ext > 0) {  // armed: the sites are periodic with the cell - Ewald sums instead of the bare 1 / d
+    const aimnet_embedding_periodic& mp = e->emb_periodic;
+    EmbedPbcBuffers pb;
+    embed_pbc_carve(pb, (char*)mp.scratch, N, n_mol, m.n_ext, mp.max_k);
+    RC(launch_embed_sites(s, m.ext_mol_idx, m.n_ext, n_mol, b, out->status + 6));
+    RC(launch_embed_pbc_field(s, in->coord, mol_c, W.nl.mol_start, N, n_mol, in->cell, n_cell, in->charge, nq, m.ext_coord,
+                              m.ext_charge, m.n_ext, mp.accuracy, b, pb, mp.status));
+    EmbedBuffers bp = b;  // the seed pass reads the periodic partials: the real-space slots, then the reciprocal-space slot
+    bp.part = pb.part;
+    RC(launch_embed_seed(s, P.grad, q_fin, N, m.n_ext, m.potential, m.potential_grad, bp, W.ecoul, W.qbar, W.fgrad, W.nl.mol_start,
+                         n_mol, m.energy, 1));
+    return launch_embed_pbc_site_pass(s, q_fin, W.nl.mol_start, N, n_mol, m.ext_charge, m.n_ext, b, pb, m.ext_forces,
+                                      m.ext_potential);
+  }
   RC(launch_embed_sites(s, m.ext_mol_idx, m.n_ext, n_mol, b, out->status + 6));
   RC(launch_embed_field(s, in->coord, mol_c, N, n_mol, m.ext_coord, m.ext_charge, m.n_ext, b));
   RC(launch_embed_seed(s, P.grad, q_fin, N, m.n_ext, m.potential, m.potential_grad, b, W.ecoul, W.qbar, W.fgrad, W.nl.mol_start,
@@ -987,6 +1001,16 @@ EvalRequest eval_request(const aimnet_engine* e, const aimnet_inputs* in, const 
     r.emb_potential = m.potential != nullptr;
     r.emb_potential_grad = m.potential_grad != nullptr;
     r.emb_scratch_ok = m.scratch && m.n_ext >= 0 && m.scratch_bytes >= aimnet_embedding_scratch_bytes(N, n_mol, m.n_ext);
+    if (e->emb_periodic_on) {
+      const aimnet_embedding_periodic& mp = e->emb_periodic;
+      r.emb_periodic = 1;
+      r.emb_pbc_full = !in->pbc_sys && in->pbc[0] && in->pbc[1] && in->pbc[2];
+      r.emb_periodic_accuracy = mp.accuracy;
+      r.emb_periodic_max_k = mp.max_k;
+      r.emb_periodic_status = mp.status != nullptr;
+      r.emb_periodic_scratch_ok = mp.scratch && m.n_ext >= 0 && mp.max_k > 0 &&
+                                  mp.scratch_bytes >= aimnet_embedding_periodic_scratch_bytes(N, n_mol, m.n_ext, mp.max_k);
+    }
   }
   return r;
 }
@@ -1219,6 +1243,8 @@ int aimnet_engine_set_embedding(aimnet_engine* e, const aimnet_embedding* emb) {
   if (!e) return AIMNET_E_INVALID;
   e->emb_tangent_on = false;  // a new embedding, or none, starts unarmed (aimnet_engine_set_embedding_tangent)
   e->emb_tangent = aimnet_embedding_tangent{};
+  e->emb_periodic_on = false;  // (likewise: aimnet_engine_set_embedding_periodic)
+  e->emb_periodic = aimnet_embedding_periodic{};
   if (!emb) {
     e->emb_on = false;
     e->emb = aimnet_embedding{};
@@ -1261,6 +1287,33 @@ int aimnet_engine_set_embedding_tangent(aimnet_engine* e, const aimnet_embedding
   }
   e->emb_tangent = *t;  // (checked against the problem size by every aimnet_engine_hvp call, tangent_plan.h)
   e->emb_tangent_on = true;
+  return AIMNET_OK;
+}
+
+size_t aimnet_embedding_periodic_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext, int32_t max_k) {
+  if (n_atoms <= 0 || n_mol <= 0 || n_ext < 0 || max_k <= 0) return 0;
+  aimnet::EmbedPbcBuffers b;
+  aimnet::embed_pbc_carve(b, nullptr, n_atoms, n_mol, n_ext, max_k);
+  return b.total;
+}
+
+int aimnet_engine_set_embedding_periodic(aimnet_engine* e, const aimnet_embedding_periodic* p) {
+  if (!e) return AIMNET_E_INVALID;
+  if (!p) {
+    e->emb_periodic_on = false;
+    e->emb_periodic = aimnet_embedding_periodic{};
+    return AIMNET_OK;
+  }
+  if (!e->emb_on) {
+    set_last_error("set_embedding_periodic: no embedding is set (aimnet_engine_set_embedding first)");
+    return AIMNET_E_INVALID;
+  }
+  if (!p->scratch) {
+    set_last_error("set_embedding_periodic: scratch is required (aimnet_embedding_periodic_scratch_bytes)");
+    return AIMNET_E_INVALID;
+  }
+  e->emb_periodic = *p;  // (checked against the problem size by every aimnet_engine_eval call, eval_plan.h)
+  e->emb_periodic_on = true;
   return AIMNET_OK;
 }
 

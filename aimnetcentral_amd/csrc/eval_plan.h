@@ -83,6 +83,13 @@ struct EvalRequest {
   bool emb_sites_ok;                                        // n_ext == 0, or ext_coord and ext_charge given
   bool emb_ext_mol_idx, emb_potential, emb_potential_grad;  // which optional arrays are given
   bool emb_scratch_ok;                                      // scratch given and at least aimnet_embedding_scratch_bytes
+  // sites periodic with the cell (aimnet_engine_set_embedding_periodic); emb_periodic == 0: unarmed, nothing below is read
+  int emb_periodic;
+  bool emb_pbc_full;                                        // pbc all true and no per-system flags
+  float emb_periodic_accuracy;
+  int emb_periodic_max_k;
+  bool emb_periodic_status;                                 // status given
+  bool emb_periodic_scratch_ok;                             // scratch given and at least aimnet_embedding_periodic_scratch_bytes
 };
 
 enum class Prep { FusedSmall, Separate, SeparateSetupRider };  // launch_prep_small / launch_mol_start + launch_wrap (+ the setup rider)
@@ -184,7 +191,20 @@ inline int eval_validate(const EvalRequest& r, char* msg, size_t n) {
     if (want_s) return plan_reject(msg, n, "eval: the embedding term has no stress (AIMNET_STRESS with an embedding set)");
     if (r.dd) return plan_reject(msg, n, "eval: the embedding term is not carried by a domain-decomposed evaluation");
     if (r.emb_n_ext < 0 || !r.emb_sites_ok) return plan_reject(msg, n, "eval: embedding: n_ext > 0 needs ext_coord and ext_charge");
-    if (r.emb_n_ext > 0 && r.pbc)
+    if (r.emb_periodic) {  // armed (aimnet_engine_set_embedding_periodic): the sites are periodic with the cell
+      if (!r.pbc) return plan_reject(msg, n, "eval: periodic embedding sites need a cell");
+      if (!r.emb_pbc_full)
+        return plan_reject(msg, n, "eval: periodic embedding sites need a cell that is periodic along all three axes (no pbc_sys)");
+      if (!(r.emb_periodic_accuracy > 0.0f && r.emb_periodic_accuracy < 1.0f))
+        return plan_reject(msg, n, "eval: periodic embedding sites need 0 < accuracy < 1");
+      if (r.emb_periodic_max_k <= 0 || r.emb_periodic_max_k % r.L.ewald_kb != 0)
+        return plan_reject(msg, n, "eval: periodic embedding sites need max_k > 0, a multiple of %d (got %d)", r.L.ewald_kb,
+                           r.emb_periodic_max_k);
+      if (!r.emb_periodic_scratch_ok)
+        return plan_reject(msg, n, "eval: periodic embedding sites: scratch missing or smaller than "
+                                   "aimnet_embedding_periodic_scratch_bytes");
+      if (!r.emb_periodic_status) return plan_reject(msg, n, "eval: periodic embedding sites: status is required");
+    } else if (r.emb_n_ext > 0 && r.pbc)
       return plan_reject(msg, n, "eval: embedding point charges take non-periodic input (no images of the sites): pass a per-atom "
                                  "potential with a cell");
     if (r.emb_potential_grad && !r.emb_potential) return plan_reject(msg, n, "eval: embedding: potential_grad without potential");

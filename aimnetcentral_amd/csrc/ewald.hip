@@ -31,76 +31,19 @@ namespace aimnet {
 
 namespace {
 
-constexpr double EW_TWO_PI = 6.283185307179586;
-
 __global__ void ewald_setup_kernel(const float* __restrict__ cell, int n_cell, const int* __restrict__ mol_start,
                                    const float* __restrict__ charge, int nq, int n_mol, float accuracy, int max_k,
                                    EwaldSystem* __restrict__ es, int* __restrict__ status_k) {
   for (int s = threadIdx.x; s < n_mol; s += blockDim.x) {
-    const float* c = cell + (n_cell == 1 ? 0 : (size_t)s * 9);
-    double m[9];
-    EwaldSystem E;
-    const double det = ewald_cell_geometry(c, m, E);
-    const double vol = fabs(det);
-    const int ns = max(1, mol_start[s + 1] - mol_start[s]);
-    const double eta = cbrt(sqrt(vol * vol / (double)ns)) / sqrt(EW_TWO_PI);
-    const double f = sqrt(-2.0 * log((double)accuracy));
-    const double alpha = 1.0 / (sqrt(2.0) * eta), rc = f * eta, kc = f / eta;
-    E.alpha = (float)alpha;
-    E.rc = (float)rc;
-    E.kc2 = (float)(kc * kc);
-    E.inv4a2 = (float)(1.0 / (4.0 * alpha * alpha));
     double Q = 0.0;
     for (int ch = 0; ch < nq; ++ch) Q += (double)charge[(size_t)ch * n_mol + s];
-    E.phi_bg = (float)(-3.141592653589793 * Q / (vol * alpha * alpha));
-    E.pref = 8.0 * 3.141592653589793 / vol;
-    for (int a = 0; a < 3; ++a) {
-      for (int cc = 0; cc < 3; ++cc) E.b[a * 3 + cc] = EW_TWO_PI * E.inv[cc * 3 + a];
-      const double len = sqrt(m[3 * a] * m[3 * a] + m[3 * a + 1] * m[3 * a + 1] + m[3 * a + 2] * m[3 * a + 2]);
-      E.nmax[a] = (int)floor(kc * len / EW_TWO_PI);
-    }
-    E.n2w = 2 * E.nmax[1] + 1;
-    E.n3w = 2 * E.nmax[2] + 1;
-    const long box = (long)(E.nmax[0] + 1) * E.n2w * E.n3w;
-    E.n_box = (int)min(box, (long)(1 << 28));
-    E.k_offset = 0;
+    double m[9];
+    EwaldSystem E;
+    ewald_system_setup(cell + (n_cell == 1 ? 0 : (size_t)s * 9), mol_start[s + 1] - mol_start[s], accuracy, Q, m, E);
     es[s] = E;
   }
   __syncthreads();
-  // slices of the k arrays: offsets = running sum of the box sizes padded to whole blocks of the structure-factor kernel.  The
-  // serial pass runs over LDS (a batch of 10^3 small cells would otherwise pay a dependent global round trip per system);
-  // batches beyond the LDS table take the slow form.
-  constexpr int TAB = 4096;
-  __shared__ int s_need[TAB];
-  __shared__ long s_total;
-  const bool in_lds = n_mol <= TAB;
-  if (in_lds)
-    for (int s = threadIdx.x; s < n_mol; s += blockDim.x) s_need[s] = (es[s].n_box + EWALD_KB - 1) / EWALD_KB * EWALD_KB;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    long off = 0;
-    for (int s = 0; s < n_mol; ++s) {
-      const long need = in_lds ? (long)s_need[s] : ((long)es[s].n_box + EWALD_KB - 1) / EWALD_KB * EWALD_KB;
-      const long at = min(off, (long)max_k);
-      const int take = (int)max(0L, min(need, (long)max_k - at));  // truncated when the capacity is too small (flagged)
-      if (in_lds) {
-        s_need[s] = (int)at;  // (the offset; the size follows from the next offset below)
-      } else {
-        es[s].k_offset = (int)at;
-        es[s].n_box = take;
-      }
-      off += need;
-    }
-    s_total = off;
-    *status_k = (int)min(off, (long)INT32_MAX);
-  }
-  __syncthreads();
-  if (in_lds)
-    for (int s = threadIdx.x; s < n_mol; s += blockDim.x) {
-      const long end = s + 1 < n_mol ? (long)s_need[s + 1] : min(s_total, (long)max_k);
-      es[s].k_offset = s_need[s];
-      es[s].n_box = (int)max(0L, min(end, (long)max_k) - (long)s_need[s]);
-    }
+  ewald_k_slices(es, n_mol, max_k, status_k);
 }
 
 __global__ void ewald_frac_kernel(const float* __restrict__ xw, const int* __restrict__ mol_idx, int n_atoms,

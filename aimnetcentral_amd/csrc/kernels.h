@@ -511,9 +511,10 @@ int launch_embed_sites(hipStream_t s, const int* ext_mol_idx, int n_ext, int n_m
 int launch_embed_field(hipStream_t s, const float* x, const int* mol_c, int n_atoms, int n_mol, const float* ext_coord,
                        const float* ext_charge, int n_ext, const EmbedBuffers& b, bool tensor = false);
 // seed pass: ecoul += q phi; grad: qbar += phi, fgrad += q grad phi; then the molecule sums of q phi into energy (may be NULL)
+// (extra_slots: b.part holds that many partials per atom behind the field pass's own - the periodic sites' reciprocal-space slot)
 int launch_embed_seed(hipStream_t s, bool grad, const float* q, int n_atoms, int n_ext, const float* potential,
                       const float* potential_grad, const EmbedBuffers& b, double* ecoul, float* qbar, float* fgrad,
-                      const int* mol_start, int n_mol, double* energy);
+                      const int* mol_start, int n_mol, double* energy, int extra_slots = 0);
 // site pass: ext_forces[A] = -dE_emb/dX_A, ext_potential[A] = k_e sum_i q_i / |x_i - X_A| (either may be NULL)
 int launch_embed_site_pass(hipStream_t s, const float* x, const float* q, const int* mol_start, int n_mol, const float* ext_coord,
                            const float* ext_charge, int n_ext, const EmbedBuffers& b, float* ext_forces, float* ext_potential);
@@ -527,5 +528,34 @@ int launch_embed_tseed(hipStream_t s, const float* q, const float* tq, int nq, c
 int launch_embed_tsite(hipStream_t s, const float* x, const float* q, const float* tq, int nq, const float* vectors, int n_atoms,
                        int n_vec, const int* mol_start, const float* ext_coord, const float* ext_charge, int n_ext,
                        const EmbedBuffers& b, float* ext_hv);
+
+// ---- embed.hip: sites that are periodic with the cell (aimnet_engine_set_embedding_periodic) --------------------------------
+// phi_i = Ewald potential of the site lattice at the atoms, psi_A = that of the atoms' charges at the sites, each with its own
+// neutralising background.  Per system (alpha, rc, kc) follow ewald_setup_kernel's rule with n_eff = atoms + sites; the k arrays,
+// fractional coordinates and EwaldSystem rows are the embedding's own (its scratch), never the workspace's.
+struct EmbedPbcSystem {   // per system, beside its EwaldSystem row
+  double cell[9];         // the row-vector cell in double: translation n is sum_a n_a cell[a * 3 + c]
+  double bg_ext, bg_atoms;  // -pi Q / (V alpha^2) of the sites' charges and of the atoms' (aimnet_inputs.charge) in double
+  int img[3];             // translations |n_a| <= img[a] = floor(rc / h_a + 1/2), h_a the perpendicular width, reach every image in rc
+  int pad;
+};
+struct EmbedPbcBuffers {  // carved from aimnet_embedding_periodic.scratch (embed_pbc_carve; base == NULL: sizes only)
+  EwaldBuffers ew;        // sys [n_mol], frac [n_atoms][3] of the atoms, k [max_k]: A(k) S_ext(k)
+  EmbedPbcSystem* ps;     // [n_mol]
+  double* frac_ext;       // [n_ext][3] fractional coordinates of the sites
+  EwaldK* k_atoms;        // [max_k]: A(k) S_q(k) of the final total charges (site pass)
+  double* part;           // [n_atoms][n_slots + 1][4]: the real-space slots, then the reciprocal-space slot with the background
+  double* site_part;      // [n_ext][4]: reciprocal space at the sites
+  size_t total;
+};
+void embed_pbc_carve(EmbedPbcBuffers& b, char* base, int n_atoms, int n_mol, int n_ext, int max_k);
+// after launch_embed_sites (eb: its lists): setup, fractional coordinates of atoms and sites, S_ext(k), real and reciprocal space at
+// the atoms into b.part; status2[0] = k entries the batch needs, status2[1] = 0.  charge [nq][n_mol]: the molecules' charges.
+int launch_embed_pbc_field(hipStream_t s, const float* x, const int* mol_c, const int* mol_start, int n_atoms, int n_mol,
+                           const float* cell, int n_cell, const float* charge, int nq, const float* ext_coord, const float* ext_charge,
+                           int n_ext, float accuracy, const EmbedBuffers& eb, EmbedPbcBuffers& b, int* status2);
+// site pass (either output may be NULL; both: nothing runs): S_q(k) of the final total charges q, reciprocal then real space at the sites
+int launch_embed_pbc_site_pass(hipStream_t s, const float* q, const int* mol_start, int n_atoms, int n_mol, const float* ext_charge,
+                               int n_ext, const EmbedBuffers& eb, const EmbedPbcBuffers& b, float* ext_forces, float* ext_potential);
 
 }  // namespace aimnet

@@ -360,6 +360,8 @@ class HipEngine(capacity.Capacities):
         e0, e_bytes = out.spans[1]
         host = out.buf.cpu() if host_out else out.buf[: e0 + e_bytes].cpu()
         st = host[:32].view(torch.int32).numpy()
+        # (periodic embedding sites: its two status words follow the engine's eight in the same section, and so in the same copy)
+        self._emb_status = host[32:40].view(torch.int32).numpy() if out.spans[0][1] >= 40 else None
         watched = [] if not watch else [v for k, v in out.views(host).items() if k != "status"] if host_out else [host[e0:].view(torch.float64)]
         # (status[6] bit 5 = a non-finite energy or FORCE seen on the device: an overflow in the adjoint sweep leaves the energies finite)
         finite = all(bool(torch.isfinite(v).all()) for v in watched) and not (watch and int(st[6]) & NONFINITE_FLAG)
@@ -368,7 +370,8 @@ class HipEngine(capacity.Capacities):
     def eval(self, coord, numbers, mol_idx, charge, cell=None, pbc=(True, True, True), forces: bool = False, stress: bool = False,
              coulomb: str = "simple", dsf_rc: float = 15.0, dsf_alpha: float = 0.2, ewald_accuracy: float = 1e-6, sync: bool = True,
              dftd3: dict[str, float] | None = None, host_out: bool = False, defer: bool = False, nbmat=None, shifts=None,
-             nbmat_lr=None, shifts_lr=None, nbmat_d3=None, shifts_d3=None, embedding: dict[str, Any] | None = None) -> dict[str, Any]:
+             nbmat_lr=None, shifts_lr=None, nbmat_d3=None, shifts_d3=None, embedding: dict[str, Any] | None = None,
+             _arm_periodic=None) -> dict[str, Any]:
         """One evaluation on device tensors (coord f32 [N,3], numbers/mol_idx i32 [N], charge f32
         [n_mol] - for a 2-channel NSE model [n_mol, 2] = the alpha / beta charges of aimnet2.py:94-100 -,
         cell f32 [3,3]|[n_mol,3,3]).  Returns device tensors (NSE: plus spin_charges); retries with x1.5 row
@@ -380,7 +383,9 @@ class HipEngine(capacity.Capacities):
         [N, width] with entries outside [0, N) as padding, integer shifts [N, width, 3] - the engine then builds no list and takes the
         coordinates as given (include/aimnet_hip.h, aimnet_inputs.nbmat).
         `embedding`: electrostatic embedding of the charges, E_emb = sum_i q_i phi_i (include/aimnet_hip.h, aimnet_embedding) - a
-        dict with point charges `ext_coord` [M,3], `ext_charge` [M] (+ `ext_mol_idx` [M], sorted, for more than one molecule) and / or
+        dict with point charges `ext_coord` [M,3], `ext_charge` [M] (+ `ext_mol_idx` [M], sorted, for more than one molecule; with a
+        cell they are refused unless `ewald_accuracy` (a float in (0, 1)) is among the keys: then the input must be fully periodic and
+        the sites of a system are periodic with its cell, by Ewald summation at that accuracy - aimnet_embedding_periodic) and / or
         a per-atom `potential` [N] (V) with `potential_grad` [N,3] (V/A); `want_ext_forces` / `want_ext_potential` ask for the
         forces on the sites and the potential of the atoms' charges at them.  The energy and forces include the term; the
         result gains `embedding_energy` [n_mol] (and `ext_forces` [M,3], `ext_potential` [M]).  Not with `stress`."""
@@ -406,13 +411,17 @@ class HipEngine(capacity.Capacities):
         np_walk_on = method == _lib.COULOMB_DSF and cell is None and bool(self.get_option("dsf_np_walk"))  # (read only where it matters)
         rq = capacity.Request("eval", n, n_mol, cell is not None, method, float(dsf_rc), float(dsf_alpha), float(ewald_accuracy), dftd3,
                               widths, (_lib.FORCES if forces else 0) | (_lib.STRESS if stress else 0), np_walk_on)
-        sections = [("status", torch.int32, (8,)), ("energy", torch.float64, (n_mol,)), ("charges", torch.float32, (n,))]
+        # (_arm_periodic, from _eval_embedded: the status section carries the two words of aimnet_embedding_periodic behind the engine's)
+        sections = [("status", torch.int32, (8 if _arm_periodic is None else 10,)), ("energy", torch.float64, (n_mol,)), ("charges", torch.float32, (n,))]
         sections += [("spin_charges", torch.float32, (n,))] if self.nq == 2 else []
         sections += [("forces", torch.float32, (n, 3))] if forces else []
         sections += [("stress", torch.float32, (max(inp.n_cell, 1), 3, 3))] if stress else []
         out = _OutBuffer(sections, self.device)
         res = out.views(out.buf)
         outs = _lib.Outputs(**{name: v.data_ptr() for name, v in res.items()})
+        if _arm_periodic is not None:
+            res["status"][8:].zero_()  # (without sites nothing writes them)
+            _arm_periodic(res["status"].data_ptr() + 32)
         fallback, host = _RangeFallback(self), None
         while True:  # fill the options, run, read the status; then the fallback, growth, or shrink and leave
             opt = self.fill_options(rq)
@@ -451,7 +460,8 @@ class HipEngine(capacity.Capacities):
             res["stress"] = res["stress"][0]
         return res
 
-    EMBEDDING_KEYS = ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "want_ext_forces", "want_ext_potential")
+    EMBEDDING_KEYS = ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "want_ext_forces", "want_ext_potential",
+                      "ewald_accuracy")
     EMBEDDING_KEYS_HVP = EMBEDDING_KEYS + ("potential_hess", "want_ext_hv", "want_field")
 
     def _embedding_arrays(self, who: str, emb: dict[str, Any], keys, n: int, n_mol: int, periodic: bool) -> dict[str, Any]:
@@ -475,7 +485,7 @@ class HipEngine(capacity.Capacities):
             if xc.ndim != 2 or xc.shape[1] != 3 or tuple(qc.shape) != (xc.shape[0],):
                 raise ValueError(f"{who}: ext_coord must be [M, 3] and ext_charge [M], got {tuple(xc.shape)}, {tuple(qc.shape)}")
             m = int(xc.shape[0])
-            if m and periodic:
+            if m and periodic and emb.get("ewald_accuracy") is None:
                 raise ValueError(f"{who}: embedding point charges take non-periodic input; pass a per-atom potential with a cell")
             if mi is not None:
                 mi = torch.as_tensor(mi).to(device=dev, dtype=torch.int32).contiguous()
@@ -521,6 +531,19 @@ class HipEngine(capacity.Capacities):
         n = int(kw["coord"].shape[0])
         n_mol = int(kw["charge"].shape[0]) if self.nq == 2 else int(kw["charge"].numel())
         arr = self._embedding_arrays("eval", emb, self.EMBEDDING_KEYS, n, n_mol, kw["cell"] is not None)
+        accuracy = emb.get("ewald_accuracy")
+        if accuracy is not None:  # sites periodic with the cell (aimnet_engine_set_embedding_periodic)
+            accuracy = float(accuracy)
+            if not (0.0 < accuracy < 1.0):
+                raise ValueError("HipEngine.eval: embedding ewald_accuracy must lie in (0, 1)")
+            if kw["cell"] is None:
+                raise ValueError("HipEngine.eval: embedding ewald_accuracy (periodic sites) needs a cell")
+            if not bool(torch.as_tensor(kw["pbc"]).bool().all()):
+                raise ValueError("HipEngine.eval: periodic embedding sites need a cell that is periodic along all three axes")
+            if not kw["sync"]:
+                raise ValueError("HipEngine.eval: periodic embedding sites are evaluated synchronously (the capacity of their k arrays "
+                                 "is read back)")
+            kw = dict(kw, pbc=(True, True, True))
         xc, qc, mi, pot, pg, m = (arr[k] for k in ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "m"))
         if pot is not None and pg is None and kw["forces"]:
             raise ValueError("HipEngine.eval: forces with an embedding potential need potential_grad")
@@ -534,11 +557,30 @@ class HipEngine(capacity.Capacities):
         s = _lib.Embedding(n_ext=m, ext_coord=ptr(xc), ext_charge=ptr(qc), ext_mol_idx=ptr(mi), potential=ptr(pot), potential_grad=ptr(pg),
                            ext_forces=ptr(outs.get("ext_forces")), ext_potential=ptr(outs.get("ext_potential")),
                            energy=outs["embedding_energy"].data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
-        _lib.check(self.lib.aimnet_engine_set_embedding(self._h, C.byref(s)), "aimnet_engine_set_embedding")
         try:
-            res = self.eval(**kw)
+            while True:
+                _lib.check(self.lib.aimnet_engine_set_embedding(self._h, C.byref(s)), "aimnet_engine_set_embedding")
+                if accuracy is not None:  # its own k arrays, scratch and status words: nothing of the system's own Ewald sum is shared
+                    max_k = self._emb_max_k
+                    pscratch = self._embedding_scratch(
+                        "_emb_periodic_scratch", int(self.lib.aimnet_embedding_periodic_scratch_bytes(n, n_mol, m, max_k)))
+
+                    def arm(status_ptr: int, max_k=max_k, pscratch=pscratch) -> None:  # (eval owns the status words: its one buffer)
+                        sp = _lib.EmbeddingPeriodic(accuracy=accuracy, max_k=max_k, status=status_ptr, scratch=pscratch.data_ptr(),
+                                                    scratch_bytes=pscratch.numel())
+                        _lib.check(self.lib.aimnet_engine_set_embedding_periodic(self._h, C.byref(sp)),
+                                   "aimnet_engine_set_embedding_periodic")
+                    res = self.eval(**kw, _arm_periodic=arm)
+                else:
+                    res = self.eval(**kw)
+                if accuracy is None:
+                    break
+                need = int(self._emb_status[0])  # (read with the status copy of the evaluation: no round trip of its own)
+                if need <= max_k:
+                    break
+                self._emb_max_k = capacity.ewald_k_capacity(need)  # the k boxes did not fit: their size is now known - repeat
         finally:
-            self.lib.aimnet_engine_set_embedding(self._h, None)
+            self.lib.aimnet_engine_set_embedding(self._h, None)  # (disarms the periodic sites too)
         if kw["host_out"]:
             outs = {k: v.cpu() for k, v in outs.items()}
         res.update(outs)
@@ -658,6 +700,8 @@ class HipEngine(capacity.Capacities):
         import torch
 
         dev, f32 = self.device, torch.float32
+        if emb.get("ewald_accuracy") is not None:
+            raise NotImplementedError("HipEngine.hvp: periodic embedding sites (ewald_accuracy) are not carried by the tangent sweep")
         arr = self._embedding_arrays("hvp", emb, self.EMBEDDING_KEYS_HVP, n, n_mol, periodic)
         xc, qc, mi, pot, pg, m = (arr[k] for k in ("ext_coord", "ext_charge", "ext_mol_idx", "potential", "potential_grad", "m"))
         ph = emb.get("potential_hess")

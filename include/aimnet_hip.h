@@ -245,8 +245,9 @@ int aimnet_engine_set_dd(aimnet_engine* e, const float* owned, aimnet_dd_exchang
  * Two sources, alone or together:
  *   point charges  n_ext sites, ext_coord [n_ext, 3] in A, in the frame of aimnet_inputs.coord as given; ext_charge [n_ext] in e;
  *                  ext_mol_idx [n_ext], non-decreasing: a site acts on the atoms of its own molecule only (NULL: n_mol must be
- *                  1).  A molecule may own no site.  Non-periodic input only (no images of the sites).  A site on top of an atom
- *                  is caller error and surfaces as status[6] bit 5.
+ *                  1).  A molecule may own no site.  Non-periodic input only, unless aimnet_engine_set_embedding_periodic (below)
+ *                  has armed the Ewald sum over the sites' images in a fully periodic cell; sites with partial periodicity are
+ *                  not carried.  A site on top of an atom is caller error and surfaces as status[6] bit 5.
  *   per atom       potential [n_atoms] in V and potential_grad [n_atoms, 3] in V / A, computed by the caller (an MM engine's mesh
  *                  sum, a uniform field phi = -E.x, grad phi = -E); allowed with a cell.  potential_grad may be NULL for an
  *                  energy-only request.
@@ -307,6 +308,46 @@ typedef struct aimnet_embedding_tangent {
 } aimnet_embedding_tangent;
 size_t aimnet_embedding_tangent_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext);
 int aimnet_engine_set_embedding_tangent(aimnet_engine* e, const aimnet_embedding_tangent* t);
+
+/* Point-charge sites that are periodic with the cell.  Arming is explicit, as for the tangent: with only aimnet_engine_set_embedding
+ * called, aimnet_engine_eval refuses n_ext > 0 with a cell as before; after aimnet_engine_set_embedding_periodic a FULLY periodic
+ * input (a cell, pbc all true, no pbc_sys) takes the sites of a system as a lattice with that system's cell, by Ewald summation.
+ * Per system, with V the volume and (alpha, r_c, k_c) from the engine's Ewald rule at n_eff = atoms + sites of the system
+ * (eta = (V^2 / n_eff)^(1/6) / sqrt(2 pi), alpha = 1 / (sqrt(2) eta), r_c = f eta, k_c = f / eta, f = sqrt(-2 ln accuracy), decided
+ * on the device from the cell):
+ *   phi_i / k_e =  sum_A sum_n Q_A erfc(alpha d) / d ,  d = |x_i - X_A + n C| < r_c           (every lattice translation in reach)
+ *               +  sum_{k in half space, |k| <= k_c} A(k) Re[conj(S_ext(k)) e^{i k x_i}] ,    A = (8 pi / V) e^{-k^2 / 4 alpha^2} / k^2
+ *               -  pi Q_ext / (V alpha^2)                                                     (neutralising background: the sites
+ *                                                                                              may carry a net charge)
+ * plus aimnet_embedding.potential as before; E_emb = sum_i q_i phi_i with its exact gradient, charge response included.  There is
+ * no self term and no site-site term (the sites are not atoms; their mutual energy is the caller's).  ext_potential[A] = psi_A, the
+ * same three terms with atoms and sites exchanged (background of the atoms' total charge), ext_forces[A] = -Q_A grad psi_A.  The
+ * sites may lie in any periodic image: fractional differences are reduced in double.  A site exactly on top of an atom is caller
+ * error here too and surfaces as status[6] bit 5 (its term is not finite; it is not treated as lying outside r_c).  The real-space sums are direct loops over
+ * the system's sites, O(n_atoms n_ext images): an ML region in a solvent box, not two sets of 10^5 particles.
+ *   accuracy   of the site sums, in (0, 1), e.g. 1e-6
+ *   max_k      capacity of the embedding's own two k arrays, in entries: a positive multiple of 8 (the k entries per block of the
+ *              structure-factor kernel)
+ *   status     device, 2 words: [0] = k entries the batch needed (> max_k: the boxes were truncated, the results are meaningless;
+ *              arm again with at least that many), [1] reserved, written 0.  aimnet_outputs.status[7] is not touched: with
+ *              AIMNET_COULOMB_EWALD / PME it belongs to the system's own sum, which runs beside this one.
+ *   scratch    device memory of at least aimnet_embedding_periodic_scratch_bytes(n_atoms, n_mol, n_ext, max_k) bytes; the
+ *              embedding's k arrays, fractional coordinates and per-system parameters live there, never in the workspace.
+ * Rejected by aimnet_engine_eval while armed: no cell, pbc not all true (or pbc_sys given), accuracy outside (0, 1), a bad max_k,
+ * a missing status, a missing or short scratch; AIMNET_STRESS and domain decomposition as for every embedding.  Not carried:
+ * aimnet_engine_hvp (sites with a cell keep its refusal, armed or not), partial periodicity, a mesh form of the sums.  With n_ext
+ * == 0 the armed engine launches what the unarmed one does.  Pair terms fp32, every sum fp64 in fixed orders, no atomics on
+ * results: the outputs are bitwise repeatable and do not depend on max_k once it suffices.
+ * p == NULL disarms; aimnet_engine_set_embedding (with a struct or with NULL) disarms too.  The struct is copied. */
+typedef struct aimnet_embedding_periodic {
+  float accuracy;
+  int32_t max_k;
+  int32_t* status;
+  void* scratch;
+  size_t scratch_bytes;
+} aimnet_embedding_periodic;
+size_t aimnet_embedding_periodic_scratch_bytes(int32_t n_atoms, int32_t n_mol, int32_t n_ext, int32_t max_k);
+int aimnet_engine_set_embedding_periodic(aimnet_engine* e, const aimnet_embedding_periodic* p);
 
 /* Particle-mesh Ewald in the analytic Hessian sweep.  Arming is explicit, as for the embedding: by default (and after on = 0)
  * aimnet_engine_hvp refuses AIMNET_COULOMB_PME with the message it always had; after aimnet_engine_set_pme_tangent(e, 1) it carries the
