@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_set_embedding_periodic",
     "aimnet_engine_set_pme_tangent",
     "aimnet_engine_set_dftd3_tangent",
+    "aimnet_engine_set_strain_tangent",
     "aimnet_neighbor_list",
     "aimnet_neighbor_list_workspace_bytes",
     "aimnet_conv_sv_2d_sp_fwd",
@@ -204,6 +205,16 @@ class EmbeddingTangent(C.Structure):
     ]
 
 
+class StrainTangent(C.Structure):
+    """aimnet_strain_tangent: arms aimnet_engine_hvp for strain directions; device pointers (strain fp32, the virials fp64)."""
+
+    _fields_ = [
+        ("strain", C.c_void_p),
+        ("dvirial", C.c_void_p),
+        ("virial", C.c_void_p),
+    ]
+
+
 class EmbeddingPeriodic(C.Structure):
     """aimnet_embedding_periodic: arms aimnet_engine_eval for sites periodic with the cell; device pointers, caller-owned scratch."""
 
@@ -320,6 +331,8 @@ def load() -> C.CDLL:
     lib.aimnet_engine_set_pme_tangent.argtypes = [vp, C.c_int32]
     lib.aimnet_engine_set_dftd3_tangent.restype = C.c_int
     lib.aimnet_engine_set_dftd3_tangent.argtypes = [vp, C.c_int32]
+    lib.aimnet_engine_set_strain_tangent.restype = C.c_int
+    lib.aimnet_engine_set_strain_tangent.argtypes = [vp, C.POINTER(StrainTangent)]
     # the conv kernels one launch at a time (tests/test_gpu_conv_kernels.py); `shifts` is a host pointer
     ci, cf = C.c_int, C.c_float
     lib.aimnet_debug_conv_fwd.restype = C.c_int

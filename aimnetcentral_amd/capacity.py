@@ -59,6 +59,16 @@ def ewald_list_cutoff(volumes, counts, accuracy: float) -> float:
     return float(np.max(math.sqrt(-2.0 * math.log(float(accuracy))) * eta)) * (1.0 + 1e-5)
 
 
+STRAIN_TANGENT_BYTES = 36  # the armed strain tangent (csrc/hvp.hip): 9 floats of virial per atom, and 9 per direction and atom
+
+
+def strain_tangent_bytes(n: int, k: int) -> int:
+    """Workspace the armed strain tangent adds to a sweep of `k` directions on `n` atoms: its two buffers, each rounded up to the
+    256 bytes every workspace buffer is aligned to (aimnet_engine_hvp_workspace_bytes reports the sum while armed)."""
+    up = lambda b: (int(b) + 255) // 256 * 256  # noqa: E731
+    return up(STRAIN_TANGENT_BYTES * n) + up(STRAIN_TANGENT_BYTES * n * k)
+
+
 def same_cutoff(a: float, b: float) -> bool:
     """`d3_cutoff == dsf_rc` as the engine decides it (engine.hip, d3_shares_lr_list / np_walk): on the float32 values of
     aimnet_eval_options - every host-side copy of that rule goes through here."""

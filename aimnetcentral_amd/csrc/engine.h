@@ -183,6 +183,10 @@ struct aimnet_engine {
   // aimnet_engine_set_dftd3_tangent: the dispersion block of aimnet_engine_hvp is the analytic tangent of d3.hip (tangent_plan.h:
   // d3_analytic); off: the central difference of the D3 gradient, as it always has been
   bool d3_tangent_on = false;
+  // aimnet_engine_set_strain_tangent: the directions of aimnet_engine_hvp carry a strain, and the sweep returns the virial tangent
+  // (tangent_plan.h: strain); a copy of the caller's struct
+  bool strain_tangent_on = false;
+  aimnet_strain_tangent strain_tangent{};
   float* unit_cell = nullptr;  // 3 x 3 identity (device): "cell" of the virial sums of a decomposed evaluation
   double* sae;
   // species slots of the pass-0 moment backward: slot = rank of the atomic number among the embedding rows that

@@ -24,6 +24,11 @@
 // Coulomb pair weights, the tangent structure factors of Ewald summation (ewald.hip: launch_ewald_tangent), and the tangent of
 // the NSE charge normalisation and of its adjoint.
 //
+// Strain directions (opt-in, aimnet_engine_set_strain_tangent): a direction may carry a 3 x 3 strain eps beside v - the path x (1 + t eps)
+// + t v with the cell moving along.  The pair tangent takes r eps (geom_tangent_strain), and the three centre-major pair kernels add
+// the centre's share of the virial S = sum_pairs r (x) rbar and its tangent (VirAcc) as `bool STRAIN` instantiations of their own; the
+// unarmed ones are the code they were.  strain_virial_kernel sums the shares per system in double.
+//
 // These kernels are written for clarity and exactness, not for the roofline: a Hessian of a 40-atom molecule is 120
 // directions x 40 atoms = 4 800 tangent rows (the GEMMs see a 4 800-row batch), everything else is far below a millisecond.
 #include <algorithm>
@@ -66,6 +71,41 @@ __device__ __forceinline__ float4 geom_tangent(float4 ud, const float* __restric
   return make_float4((rx - ud.x * td) * inv, (ry - ud.y * td) * inv, (rz - ud.z * td) * inv, td);
 }
 
+// ... with a strain direction (armed, aimnet_engine_set_strain_tangent): the cell moves with the atoms, x -> x (1 + t eps) + t v in
+// the row-vector convention of the stress, so t_r = v_j - v_i + (d u) eps whatever image the pair was found in; eps = 9 floats, row-major
+__device__ __forceinline__ float4 geom_tangent_strain(float4 ud, const float* __restrict__ tvk, const float* __restrict__ eps, int i,
+                                                      int j) {
+  const float x = ud.x * ud.w, y = ud.y * ud.w, z = ud.z * ud.w;
+  const float rx = tvk[3 * j] - tvk[3 * i] + (x * eps[0] + y * eps[3] + z * eps[6]);
+  const float ry = tvk[3 * j + 1] - tvk[3 * i + 1] + (x * eps[1] + y * eps[4] + z * eps[7]);
+  const float rz = tvk[3 * j + 2] - tvk[3 * i + 2] + (x * eps[2] + y * eps[5] + z * eps[8]);
+  const float td = ud.x * rx + ud.y * ry + ud.z * rz;
+  const float inv = 1.0f / ud.w;
+  return make_float4((rx - ud.x * td) * inv, (ry - ud.y * td) * inv, (rz - ud.z * td) * inv, td);
+}
+template <bool STRAIN>
+__device__ __forceinline__ float4 geom_tangent_of(float4 ud, const float* __restrict__ tvk, const float* __restrict__ eps, int i, int j) {
+  if constexpr (STRAIN) return geom_tangent_strain(ud, tvk, eps, i, j);
+  else return geom_tangent(ud, tvk, i, j);
+}
+
+// The virial share of a centre and its tangent (armed): S_i = -1/2 sum_m r (x) inc_m, t_S_i = -1/2 sum_m (t_r (x) inc_m + r (x) t_inc_m)
+// with r = d u, t_r = d t_u + t_d u and inc_m the pair's increment to xbar_i.  LINEAR in (inc, t_inc): every thread adds its own share.
+struct VirAcc {
+  float w[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+__device__ __forceinline__ void vir_add(VirAcc& A, float4 u, float4 tu, const float inc[3], const float tinc[3]) {
+  const float r[3] = {u.x * u.w, u.y * u.w, u.z * u.w};
+  const float tr[3] = {tu.x * u.w + u.x * tu.w, tu.y * u.w + u.y * tu.w, tu.z * u.w + u.z * tu.w};
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      A.w[a * 3 + b] += r[a] * inc[b];
+      A.tw[a * 3 + b] += tr[a] * inc[b] + r[a] * tinc[b];
+    }
+}
+
 template <typename T>
 __device__ __forceinline__ T block_sum256(T v, T* sh) {  // 256 threads
   v = wave_sum(v);
@@ -82,9 +122,10 @@ struct Stage {  // one chunk of a centre's neighbour row in LDS
   int j[HCH];
 };
 
+template <bool STRAIN = false>
 __device__ __forceinline__ void stage_chunk(Stage& st, int i, int m0, int cnt, const int* __restrict__ nb_idx,
                                             const float4* __restrict__ pg, int cap, const float* __restrict__ tvk,
-                                            const BasisParams& bp) {
+                                            const BasisParams& bp, const float* __restrict__ eps = nullptr) {
   __syncthreads();
   const int t = threadIdx.x;
   if (t < HCH && m0 + t < cnt) {
@@ -92,7 +133,7 @@ __device__ __forceinline__ void stage_chunk(Stage& st, int i, int m0, int cnt, c
     const float4 ud = pg[p];
     const int j = nb_idx[p];
     st.u[t] = ud;
-    st.tu[t] = geom_tangent(ud, tvk, i, j);
+    st.tu[t] = geom_tangent_of<STRAIN>(ud, tvk, eps, i, j);
     const float3 f = envelope3(bp, ud.w);
     st.fc[t] = make_float4(f.x, f.y, f.z, 0.0f);
     st.j[t] = j;
@@ -104,7 +145,7 @@ __device__ __forceinline__ void stage_chunk(Stage& st, int i, int m0, int cnt, c
 // block = (centre i, direction k), thread = feature (a, g).  S[f][c] = sum_m a_j[f] gs_g (1, u)[c] and
 // t_S = sum_m t_a_j gs (1,u) + a_j t_gs (1,u) + a_j gs (0, t_u); then V = agh . S_vec, the MLP input row
 // [a | S0 | |V|^2 | q | Sq0 | |Vq|^2] and its tangent [t_a | t_S0 | 2 V . t_V | ...].
-template <int NQ>
+template <int NQ, bool STRAIN = false>
 __global__ __launch_bounds__(256) void hvp_conv_fwd_kernel(const float* __restrict__ a, const int* __restrict__ row_of,
                                                           const float* __restrict__ ta, const float* __restrict__ q,
                                                           const float* __restrict__ tq, const int* __restrict__ nb_idx,
@@ -113,7 +154,8 @@ __global__ __launch_bounds__(256) void hvp_conv_fwd_kernel(const float* __restri
                                                           const float* __restrict__ agh_q, BasisParams bp,
                                                           float* __restrict__ x, float* __restrict__ tx, int ldx,
                                                           float* __restrict__ V, float* __restrict__ tV,
-                                                          float* __restrict__ Vq, float* __restrict__ tVq, int N) {
+                                                          float* __restrict__ Vq, float* __restrict__ tVq, int N,
+                                                          const float* __restrict__ strain) {
   __shared__ Stage st;
   __shared__ float sS[NF * 4], stS[NF * 4];
   __shared__ float sSq[(NQ ? NQ : 1) * 64], stSq[(NQ ? NQ : 1) * 64];
@@ -121,12 +163,13 @@ __global__ __launch_bounds__(256) void hvp_conv_fwd_kernel(const float* __restri
   const int i = blockIdx.x, k = blockIdx.y, f = threadIdx.x, g = f & 15;
   if (f < 16) s_shift[f] = bp.shifts[f];
   const float* tvk = tv + (size_t)k * N * 3;
+  const float* eps = STRAIN ? strain + (size_t)k * 9 : nullptr;
   const int cnt = nb_cnt[i];
   float S[4] = {0, 0, 0, 0}, tS[4] = {0, 0, 0, 0}, Sq[4] = {0, 0, 0, 0}, tSq[4] = {0, 0, 0, 0};
   const bool qthr = NQ > 0 && f < NQ * 16;
   const int qc = f >> 4;
   for (int m0 = 0; m0 < cnt; m0 += HCH) {
-    stage_chunk(st, i, m0, cnt, nb_idx, pg, cap, tvk, bp);
+    stage_chunk<STRAIN>(st, i, m0, cnt, nb_idx, pg, cap, tvk, bp, eps);
     const float shift = s_shift[g];
     const int mc = min(HCH, cnt - m0);
     for (int m = 0; m < mc; ++m) {
@@ -344,8 +387,9 @@ __global__ void hvp_update_a_kernel(const float* __restrict__ a, const int* __re
 struct CoulAcc {
   float qb = 0.f, tqb = 0.f, f[3] = {0, 0, 0}, tf[3] = {0, 0, 0};
 };
+template <bool STRAIN = false>
 __device__ __forceinline__ void coul_add(CoulAcc& A, float w, float dw, float d2w, float qi, float tqi, float qj, float tqj,
-                                         float4 u, float4 tu) {
+                                         float4 u, float4 tu, VirAcc* VA = nullptr) {
   A.qb += w * qj;
   A.tqb += dw * tu.w * qj + w * tqj;
   const float qq = qi * qj, tqq = tqi * qj + qi * tqj;
@@ -354,6 +398,24 @@ __device__ __forceinline__ void coul_add(CoulAcc& A, float w, float dw, float d2
   A.tf[0] += tt * u.x + t * tu.x;
   A.tf[1] += tt * u.y + t * tu.y;
   A.tf[2] += tt * u.z + t * tu.z;
+  if constexpr (STRAIN) {  // inc = -2 sign k (t u): the factor goes on in coul_vir_store
+    const float inc[3] = {t * u.x, t * u.y, t * u.z};
+    const float tinc[3] = {tt * u.x + t * tu.x, tt * u.y + t * tu.y, tt * u.z + t * tu.z};
+    vir_add(*VA, u, tu, inc, tinc);
+  }
+}
+// armed: the centre's virial share of the pair term and its tangent, -1/2 r (x) (-2 sign k t u) = sign k r (x) (t u), 9 floats each
+__device__ __forceinline__ void coul_vir_store(VirAcc& VA, int i, int k, int N, int lane, float sign_k, bool accum,
+                                               float* __restrict__ vir, float* __restrict__ tvir) {
+#pragma unroll
+  for (int c = 0; c < 9; ++c) {
+    const float v = sign_k * wave_sum(VA.w[c]), tvv = sign_k * wave_sum(VA.tw[c]);
+    if (lane == 0) {
+      const size_t pe = (size_t)i * 9 + c, te = ((size_t)k * N + i) * 9 + c;
+      if (k == 0) vir[pe] = accum ? vir[pe] + v : v;
+      tvir[te] = accum ? tvir[te] + tvv : tvv;
+    }
+  }
 }
 __device__ __forceinline__ void coul_store(CoulAcc& A, int i, int k, int N, int nq, int lane, float sign_k, float self, float qi,
                                            float tqi, bool accum, float* qbar, float* tqbar, float* xbar, float* txbar) {
@@ -391,20 +453,25 @@ __device__ __forceinline__ void q_total(const float* __restrict__ q, const float
   }
 }
 
-// embedded short-range Coulomb (subtracted; lr.py:21-62): initialises the seeds (enabled == false: zeros)
+// embedded short-range Coulomb (subtracted; lr.py:21-62): initialises the seeds (enabled == false: zeros) - armed (STRAIN), the
+// per-atom virial rows and their tangents too
+template <bool STRAIN = false>
 __global__ __launch_bounds__(256) void hvp_coulomb_sr_kernel(bool enabled, const float* __restrict__ q, const float* __restrict__ tq,
                                                             int nq, const int* __restrict__ nb_idx, const int* __restrict__ nb_cnt,
                                                             const float4* __restrict__ pg, int cap, const float* __restrict__ tv,
                                                             CoulombParams cp, int N, float* __restrict__ qbar,
                                                             float* __restrict__ tqbar, float* __restrict__ xbar,
-                                                            float* __restrict__ txbar) {
+                                                            float* __restrict__ txbar, const float* __restrict__ strain,
+                                                            float* __restrict__ vir, float* __restrict__ tvir) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), k = blockIdx.y;
   if (i >= N) return;
   const int lane = threadIdx.x & 63;
   const float* tvk = tv + (size_t)k * N * 3;
+  const float* eps = STRAIN ? strain + (size_t)k * 9 : nullptr;
   float qi, tqi;
   q_total(q, tq, nq, N, k, i, qi, tqi);
   CoulAcc A;
+  VirAcc VA;
   if (enabled) {
     const int cnt = nb_cnt[i];
     const float rc = cp.sr_rc;
@@ -412,7 +479,7 @@ __global__ __launch_bounds__(256) void hvp_coulomb_sr_kernel(bool enabled, const
       const size_t p = (size_t)i * cap + m;
       const float4 u = pg[p];
       const int j = nb_idx[p];
-      const float4 tu = geom_tangent(u, tvk, i, j);
+      const float4 tu = geom_tangent_of<STRAIN>(u, tvk, eps, i, j);
       const float d = u.w;
       float fc, dfc, d2fc;
       if (cp.sr_envelope == 0) {  // exp envelope: fc = exp(-1 / (1 - t^2)) e, t = d / rc
@@ -435,10 +502,11 @@ __global__ __launch_bounds__(256) void hvp_coulomb_sr_kernel(bool enabled, const
       const float inv = 1.0f / d;
       float qj, tqj;
       q_total(q, tq, nq, N, k, j, qj, tqj);
-      coul_add(A, fc * inv, dfc * inv - fc * inv * inv, d2fc * inv - 2.0f * dfc * inv * inv + 2.0f * fc * inv * inv * inv, qi, tqi,
-               qj, tqj, u, tu);
+      coul_add<STRAIN>(A, fc * inv, dfc * inv - fc * inv * inv, d2fc * inv - 2.0f * dfc * inv * inv + 2.0f * fc * inv * inv * inv, qi,
+                       tqi, qj, tqj, u, tu, &VA);
     }
   }
+  if constexpr (STRAIN) coul_vir_store(VA, i, k, N, lane, -cp.factor, false, vir, tvir);
   coul_store(A, i, k, N, nq, lane, -cp.factor, 0.0f, qi, tqi, false, qbar, tqbar, xbar, txbar);
 }
 
@@ -453,7 +521,7 @@ __global__ void hvp_qtot_kernel(const float* __restrict__ q, int N, float* __res
 // reciprocal-space block follows in ewald.hip.  status6 (read by the Ewald mode alone): takes STATUS_EWALD_LIST_SHORT when the
 // list cutoff cp.dsf_rc is below rc.
 enum class LrMode { Simple, Dsf, Ewald };
-template <LrMode MODE>
+template <LrMode MODE, bool STRAIN = false>
 __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __restrict__ q, const float* __restrict__ tq, int nq,
                                                             const float* __restrict__ xw, const int* __restrict__ mol_idx,
                                                             const int* __restrict__ mol_start, const float* __restrict__ cell,
@@ -462,7 +530,8 @@ __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __rest
                                                             int cap, const float* __restrict__ tv, CoulombParams cp, int N,
                                                             float* __restrict__ qbar, float* __restrict__ tqbar,
                                                             float* __restrict__ xbar, float* __restrict__ txbar,
-                                                            int* __restrict__ status6) {
+                                                            int* __restrict__ status6, const float* __restrict__ strain,
+                                                            float* __restrict__ vir, float* __restrict__ tvir) {
   constexpr bool DSF = MODE != LrMode::Simple;  // a pair term over the long-range list
   constexpr bool EW = MODE == LrMode::Ewald;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), k = blockIdx.y;
@@ -481,7 +550,9 @@ __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __rest
   if (EW && k == 0 && lane == 0 && i == mol_start[mi] && !(cp.dsf_rc >= Rc)) atomicOr(status6, STATUS_EWALD_LIST_SHORT);
   const float* c = (DSF && cell) ? cell + (n_cell == 1 ? 0 : (size_t)mi * 9) : nullptr;
   const int lo = DSF ? 0 : mol_start[mi], hi = DSF ? nb_cnt[i] : mol_start[mi + 1];
+  const float* eps = STRAIN ? strain + (size_t)k * 9 : nullptr;
   CoulAcc A;
+  VirAcc VA;
   for (int m = lo + lane; m < hi; m += 64) {
     int j;
     float rx, ry, rz;
@@ -505,7 +576,7 @@ __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __rest
     if (DSF && !(d < Rc)) continue;
     const float inv = 1.0f / d;
     const float4 u = make_float4(rx * inv, ry * inv, rz * inv, d);
-    const float4 tu = geom_tangent(u, tvk, i, j);
+    const float4 tu = geom_tangent_of<STRAIN>(u, tvk, eps, i, j);
     float w, dw, d2w;
     if (DSF) {
       const float ec = erfcf(al * d), ex = expf(-al * al * d * d);
@@ -519,9 +590,10 @@ __global__ __launch_bounds__(256) void hvp_coulomb_lr_kernel(const float* __rest
     }
     float qj, tqj;
     q_total(q, tq, nq, N, k, j, qj, tqj);
-    coul_add(A, w, dw, d2w, qi, tqi, qj, tqj, u, tu);
+    coul_add<STRAIN>(A, w, dw, d2w, qi, tqi, qj, tqj, u, tu, &VA);
   }
   const float self = DSF ? -4.0f * cp.factor * (sv * 0.5f + al * 0.56418958354775629f) : 0.0f;  // d/dq of 2 k cs q^2
+  if constexpr (STRAIN) coul_vir_store(VA, i, k, N, lane, cp.factor, true, vir, tvir);
   coul_store(A, i, k, N, nq, lane, cp.factor, self, qi, tqi, true, qbar, tqbar, xbar, txbar);
 }
 
@@ -629,7 +701,10 @@ __device__ __forceinline__ void rbar_pair_add(float D, const float U[3], float t
 //   P' = Sbar_j0 - u . Sbar_jv   (the same pair seen from j: u_ji = -u)
 //   abar_i += gs P';  dbar_ij = a_j P gs', ubar_ij = gs a_j Sbar_iv;  dbar_ji = a_i P' gs', ubar_ji = gs a_i Sbar_jv
 //   xbar_i += sum_m rbar_ji - rbar_ij
-template <int NQ>
+// STRAIN (armed, aimnet_engine_set_strain_tangent): the pair tangent takes the strain of the direction, and the centre's share of the
+// virial -1/2 sum_m r (x) (rbar_ji - rbar_ij) with its tangent is added to vir [N][9] / tvir [K][N][9] (18 accumulators more: a form of
+// its own, so that the unarmed one keeps its registers)
+template <int NQ, bool STRAIN = false>
 __global__ __launch_bounds__(256) void hvp_conv_bwd_kernel(bool need_abar, const float* __restrict__ a, const int* __restrict__ row_of,
                                                           const float* __restrict__ ta, const float* __restrict__ q,
                                                           const float* __restrict__ tq, const float* __restrict__ Sbar,
@@ -639,13 +714,15 @@ __global__ __launch_bounds__(256) void hvp_conv_bwd_kernel(bool need_abar, const
                                                           const float* __restrict__ tv, BasisParams bp, float* __restrict__ abar,
                                                           float* __restrict__ tabar, float* __restrict__ qbar,
                                                           float* __restrict__ tqbar, float* __restrict__ xbar,
-                                                          float* __restrict__ txbar, int N) {
+                                                          float* __restrict__ txbar, int N, const float* __restrict__ strain,
+                                                          float* __restrict__ vir, float* __restrict__ tvir) {
   __shared__ Stage st;
   __shared__ float s_shift[16];
   __shared__ float sh[4];
   const int i = blockIdx.x, k = blockIdx.y, f = threadIdx.x, g = f & 15;
   if (f < 16) s_shift[f] = bp.shifts[f];
   const float* tvk = tv + (size_t)k * N * 3;
+  const float* eps = STRAIN ? strain + (size_t)k * 9 : nullptr;
   const int cnt = nb_cnt[i];
   const size_t tr = (size_t)k * N + i;
   const size_t ri = row_of ? (size_t)min(63, max(0, row_of[i])) : (size_t)i;
@@ -664,6 +741,7 @@ __global__ __launch_bounds__(256) void hvp_conv_bwd_kernel(bool need_abar, const
   }
   float ab = 0.f, tab = 0.f, qb = 0.f, tqb = 0.f;
   float xa[3] = {0, 0, 0}, txa[3] = {0, 0, 0};
+  VirAcc VA;
   // one (coefficient, adjoint-moment) pair -> its share of the four pair adjoints and of abar-like sums
   auto pair_terms = [&](float cj, float tcj, float ci, float tci, float4 Si, float4 tSi, float4 Sj, float4 tSj, float4 u, float4 tu,
                         float gs, float dgs, float tgs, float tdgs, float& acc_b, float& tacc_b) __attribute__((always_inline)) {
@@ -682,10 +760,21 @@ __global__ __launch_bounds__(256) void hvp_conv_bwd_kernel(bool need_abar, const
                           tci * Sj.w + ci * tSj.w - tcj * Si.w - cj * tSi.w};
     const float U[3] = {gs * v[0], gs * v[1], gs * v[2]};
     const float tU[3] = {tgs * v[0] + gs * tvv[0], tgs * v[1] + gs * tvv[1], tgs * v[2] + gs * tvv[2]};
-    rbar_pair_add(D, U, tD, tU, u, tu, xa, txa);
+    if constexpr (STRAIN) {  // the pair's own increment first (0 + x is exact: xa takes the bits of the unarmed form)
+      float inc[3] = {0, 0, 0}, tinc[3] = {0, 0, 0};
+      rbar_pair_add(D, U, tD, tU, u, tu, inc, tinc);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        xa[c] += inc[c];
+        txa[c] += tinc[c];
+      }
+      vir_add(VA, u, tu, inc, tinc);
+    } else {
+      rbar_pair_add(D, U, tD, tU, u, tu, xa, txa);
+    }
   };
   for (int m0 = 0; m0 < cnt; m0 += HCH) {
-    stage_chunk(st, i, m0, cnt, nb_idx, pg, cap, tvk, bp);
+    stage_chunk<STRAIN>(st, i, m0, cnt, nb_idx, pg, cap, tvk, bp, eps);
     const float shift = s_shift[g];
     const int mc = min(HCH, cnt - m0);
     // (requesting the NEXT neighbour's four rows before this one's arithmetic was measured slower: 3.0 -> 4.5 ms per sweep on
@@ -731,6 +820,44 @@ __global__ __launch_bounds__(256) void hvp_conv_bwd_kernel(bool need_abar, const
     if (f == 0) {
       if (k == 0) xbar[(size_t)i * 3 + c] += v;
       txbar[tr * 3 + c] += tvv;
+    }
+  }
+  if constexpr (STRAIN) {
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+      const float v = block_sum256(VA.w[c], sh), tvv = block_sum256(VA.tw[c], sh);
+      if (f == 0) {
+        if (k == 0) vir[(size_t)i * 9 + c] -= 0.5f * v;
+        tvir[tr * 9 + c] -= 0.5f * tvv;
+      }
+    }
+  }
+}
+
+// armed: dvirial[k][m] = sum of the tangent rows of the atoms of system m, virial[m] likewise from the primal rows (k == 0), in double
+// (strided loop, wave_sum, the four waves in index order: crs_dipole_kernel's sum).  block = (system, direction)
+__global__ __launch_bounds__(256) void strain_virial_kernel(const float* __restrict__ vir, const float* __restrict__ tvir,
+                                                           const int* __restrict__ mol_start, int n_mol, int N,
+                                                           double* __restrict__ virial, double* __restrict__ dvirial) {
+  __shared__ double sh[4];
+  const int m = blockIdx.x, k = blockIdx.y;
+  const int i0 = mol_start[m], i1 = mol_start[m + 1];
+  const bool prim = k == 0 && virial != nullptr;
+  double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, pacc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+      acc[c] += (double)tvir[((size_t)k * N + i) * 9 + c];
+      if (prim) pacc[c] += (double)vir[(size_t)i * 9 + c];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 9; ++c) {
+    const double v = block_sum256(acc[c], sh);
+    if (threadIdx.x == 0) dvirial[((size_t)k * n_mol + m) * 9 + c] = v;
+    if (prim) {  // (uniform over the block)
+      const double pv = block_sum256(pacc[c], sh);
+      if (threadIdx.x == 0) virial[(size_t)m * 9 + c] = pv;
     }
   }
 }
@@ -874,6 +1001,7 @@ struct HvpWs {
   float *h[2], *g[2];    // activations between GEMMs / adjoint ping-pong (stacked: tangent rows follow the N primal rows)
   float *Sbar, *tSbar, *Sqbar, *tSqbar, *abar, *tabar, *qbar[2], *tqbar[2], *xbar, *txbar;
   float* wlast;
+  float *vir, *tvir;  // plan: strain - [N][9] per-atom virial shares and [K][N][9] their tangents
   EwaldBuffers ew;  // Ewald summation: per-system parameters, fractional coordinates, k entries (ewald.hip)
   double* ew_tk;    // [K][max_k][2] tangent structure factors (t_P, t_Q)
   float* qsum;      // [N] alpha + beta of every atom: for the structure factors of a two-channel model, and for crs_dipole_kernel
@@ -962,6 +1090,7 @@ void tangent_layout(const aimnet_engine* e, int N, int n_mol, int K, const Tange
     W.abar = c.take<float>(n * NF), W.tabar = c.take<float>(kn * NF);
     W.xbar = c.take<float>(n * 3), W.txbar = c.take<float>(kn * 3);
     W.wlast = c.take<float>((size_t)mw);
+    if (P.strain) W.vir = c.take<float>(n * 9), W.tvir = c.take<float>(kn * 9);
     // Ewald summation: the buffers of aimnet_engine_eval + the tangent structure factors of every direction
     W.ew.max_k = P.ewald_max_k;
     W.ew.sys = c.take<EwaldSystem>(P.ewald ? (size_t)n_mol : 0);
@@ -1019,6 +1148,13 @@ void nq_dispatch(int p, int nq, F&& launch) {
   else launch(std::integral_constant<int, 2>{});
 }
 
+// ... and for the armed form (plan: strain) or today's
+template <typename F>
+void strain_dispatch(bool strain, F&& launch) {
+  if (strain) launch(std::true_type{});
+  else launch(std::false_type{});
+}
+
 // ---- one tangent sweep in stages ------------------------------------------------------------------------------------------
 // tangent_plan.h decides, once, what runs; every stage below (a member of this context) reads it from the plan.
 struct Tangent {
@@ -1029,6 +1165,7 @@ struct Tangent {
   const float* vectors;  // [K][N][3]
   int K;
   int* status;
+  const float* strain = nullptr;  // [K][9] (plan: strain; set by open())
   TangentPlan P;  // (from here on: filled by open())
   HvpWs W;
   int N, n_mol, n_cell, np, nq;
@@ -1115,9 +1252,11 @@ int Tangent::forward() {
     const int* row_of = p == 0 ? in->numbers : nullptr;
     const float *q_p = p > 0 ? W.q[p - 1] : nullptr, *tq_p = p > 0 ? W.tq[p - 1] : nullptr;
     nq_dispatch(p, nq, [&](auto nqv) {
-      hipLaunchKernelGGL((hvp_conv_fwd_kernel<decltype(nqv)::value>), gik, b256, 0, s, a_p, row_of, W.ta[p], q_p, tq_p, W.nb_idx,
-                         W.nb_cnt, W.pg, P.cap, vectors, e->agh_a, e->agh_q, e->bp, W.x[p], W.tx[p], ldx, W.V[p], W.tV[p], W.Vq[p],
-                         W.tVq[p], N);
+      strain_dispatch(P.strain, [&](auto sv) {
+        hipLaunchKernelGGL((hvp_conv_fwd_kernel<decltype(nqv)::value, decltype(sv)::value>), gik, b256, 0, s, a_p, row_of, W.ta[p], q_p,
+                           tq_p, W.nb_idx, W.nb_cnt, W.pg, P.cap, vectors, e->agh_a, e->agh_q, e->bp, W.x[p], W.tx[p], ldx, W.V[p],
+                           W.tV[p], W.Vq[p], W.tVq[p], N, strain);
+      });
     });
     AIMNET_LAUNCH_CHECK();
     RC(mlp_forward(Ls, nl, e->arch.last_linear[p] != 0, W.x[p], W.z[p], W.y[p]));
@@ -1204,13 +1343,17 @@ int Tangent::lists() {
 int Tangent::coulomb_seeds() {
   const dim3 gwk(ceil_div(N, 4), K), b256(256);
   const float *q_fin = W.q[np - 2], *tq_fin = W.tq[np - 2];
-  hipLaunchKernelGGL(hvp_coulomb_sr_kernel, gwk, b256, 0, s, e->arch.sr_coulomb != 0, q_fin, tq_fin, nq, W.nb_idx, W.nb_cnt, W.pg,
-                     P.cap, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar);
+  strain_dispatch(P.strain, [&](auto sv) {  // (armed: initialises the virial rows too)
+    hipLaunchKernelGGL(hvp_coulomb_sr_kernel<decltype(sv)::value>, gwk, b256, 0, s, e->arch.sr_coulomb != 0, q_fin, tq_fin, nq, W.nb_idx,
+                       W.nb_cnt, W.pg, P.cap, vectors, cp, N, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar, strain, W.vir, W.tvir);
+  });
   AIMNET_LAUNCH_CHECK();
   auto long_range = [&](auto mode) {
-    hipLaunchKernelGGL(hvp_coulomb_lr_kernel<decltype(mode)::value>, gwk, b256, 0, s, q_fin, tq_fin, nq, W.nl.xw, mol_c,
-                       W.nl.mol_start, in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, P.cap_lr, vectors, cp, N, W.qbar[qb],
-                       W.tqbar[qb], W.xbar, W.txbar, status + 6);
+    strain_dispatch(P.strain, [&](auto sv) {
+      hipLaunchKernelGGL((hvp_coulomb_lr_kernel<decltype(mode)::value, decltype(sv)::value>), gwk, b256, 0, s, q_fin, tq_fin, nq,
+                         W.nl.xw, mol_c, W.nl.mol_start, in->cell, n_cell, W.lr_idx, W.lr_shift, W.lr_cnt, P.cap_lr, vectors, cp, N,
+                         W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar, status + 6, strain, W.vir, W.tvir);
+    });
   };
   if (opt->coulomb == AIMNET_COULOMB_SIMPLE) long_range(std::integral_constant<LrMode, LrMode::Simple>{});
   if (opt->coulomb == AIMNET_COULOMB_DSF) long_range(std::integral_constant<LrMode, LrMode::Dsf>{});
@@ -1295,9 +1438,11 @@ int Tangent::backward() {
     });
     AIMNET_LAUNCH_CHECK();
     nq_dispatch(p, nq, [&](auto nqv) {
-      hipLaunchKernelGGL((hvp_conv_bwd_kernel<decltype(nqv)::value>), gik, b256, 0, s, p > 0, a_p, row_of, W.ta[p], q_p, tq_p,
-                         W.Sbar, W.tSbar, W.Sqbar, W.tSqbar, W.nb_idx, W.nb_cnt, W.pg, P.cap, vectors, e->bp, W.abar, W.tabar,
-                         W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar, N);
+      strain_dispatch(P.strain, [&](auto sv) {
+        hipLaunchKernelGGL((hvp_conv_bwd_kernel<decltype(nqv)::value, decltype(sv)::value>), gik, b256, 0, s, p > 0, a_p, row_of, W.ta[p],
+                           q_p, tq_p, W.Sbar, W.tSbar, W.Sqbar, W.tSqbar, W.nb_idx, W.nb_cnt, W.pg, P.cap, vectors, e->bp, W.abar,
+                           W.tabar, W.qbar[qb], W.tqbar[qb], W.xbar, W.txbar, N, strain, W.vir, W.tvir);
+      });
     });
     AIMNET_LAUNCH_CHECK();
     if (p == 0) break;
@@ -1359,6 +1504,11 @@ int Tangent::d3_block(bool want_forces) {
 
 int Tangent::write_hvp(float* hv, float* forces) {
   AIMNET_HIP_CHECK(hipMemcpyAsync(hv, W.txbar, kn() * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (P.strain) {  // the per-atom virial rows -> per system, in double
+    hipLaunchKernelGGL(strain_virial_kernel, dim3(n_mol, K), dim3(256), 0, s, W.vir, W.tvir, W.nl.mol_start, n_mol, N,
+                       e->strain_tangent.virial, e->strain_tangent.dvirial);
+    AIMNET_LAUNCH_CHECK();
+  }
   if (forces) {
     hipLaunchKernelGGL(hvp_out_kernel, grid1((size_t)N * 3), dim3(256), 0, s, W.xbar, (size_t)N * 3, forces);
     AIMNET_LAUNCH_CHECK();
@@ -1398,6 +1548,8 @@ TangentRequest tangent_request(TangentEntry entry, const aimnet_engine* e, int N
   r.pme_tangent = entry == TangentEntry::Hvp && e->pme_tangent_on;
   r.pme_max_mesh = opt->pme_max_mesh; r.pme_part = PME_PART;
   r.d3_tangent = entry == TangentEntry::Hvp && e->d3_tangent_on;
+  r.strain_tangent = e->strain_tangent_on;  // (both entries: charge_response refuses an armed engine)
+  r.strain_arrays = e->strain_tangent.strain && e->strain_tangent.dvirial;
   if (!in) return r;
   r.pbc = in->cell != nullptr; r.n_cell = in->n_cell;
   const bool mesh_armed = opt->coulomb == AIMNET_COULOMB_PME && r.pme_tangent;
@@ -1430,6 +1582,7 @@ int Tangent::open(const TangentRequest& rq, void* workspace, size_t workspace_by
   }
   N = rq.N, n_mol = rq.n_mol, n_cell = rq.pbc ? rq.n_cell : 0, np = rq.n_pass, nq = rq.nq, pbc = rq.pbc;
   mol_c = W.nl.mol_c, cp = coulomb_params(e->arch, opt);
+  strain = P.strain ? e->strain_tangent.strain : nullptr;
   return 0;
 }
 
@@ -1444,6 +1597,13 @@ size_t aimnet_engine_hvp_workspace_bytes(const aimnet_engine* e, int32_t n_atoms
                                          const aimnet_eval_options* opt) {
   if (!e || !opt || n_atoms <= 0 || n_mol <= 0 || n_vec <= 0) return 0;
   return tangent_workspace_bytes(TangentEntry::Hvp, e, n_atoms, n_mol, n_vec, opt);
+}
+
+int aimnet_engine_set_strain_tangent(aimnet_engine* e, const aimnet_strain_tangent* s) {
+  if (!e) return AIMNET_E_INVALID;
+  e->strain_tangent_on = s != nullptr;
+  e->strain_tangent = s ? *s : aimnet_strain_tangent{};  // (checked by every call while armed, tangent_plan.h)
+  return AIMNET_OK;
 }
 
 int aimnet_engine_hvp(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const float* vectors,

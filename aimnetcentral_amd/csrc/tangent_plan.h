@@ -34,6 +34,9 @@ struct TangentRequest {
   // aimnet_engine_set_dftd3_tangent armed the sweep for the dispersion term (read with dftd3 != 0 and Hvp only): its block is the
   // analytic tangent of csrc/d3.hip on the one D3 list, not the central difference over 4 n_vec displaced copies
   bool d3_tangent;
+  // aimnet_engine_set_strain_tangent armed the sweep for strain directions (read by both entries: charge_response refuses it); then
+  // strain_arrays: the struct's strain and dvirial are both given
+  bool strain_tangent, strain_arrays;
 };
 
 // ---- argument checks: 0, or AIMNET_E_INVALID with the message in msg.  Nothing has been launched when they run --------------------
@@ -118,6 +121,23 @@ inline int tangent_validate(const TangentRequest& r, char* msg, size_t n) {
   if (r.pbc && !(r.n_cell == 1 || r.n_cell == r.n_mol)) return plan_reject(msg, n, "%s: n_cell must be 1 or n_mol", who);
   if ((size_t)r.n_vec * (size_t)r.N * (size_t)r.max_width >= (size_t)INT32_MAX)
     return plan_reject(msg, n, "%s: n_vec * n_atoms too large for one sweep (split the directions)", who);
+  if (r.strain_tangent) {  // armed (aimnet_engine_set_strain_tangent): after every other check, so that each keeps its precedence
+    if (!hvp)
+      return plan_reject(msg, n, "charge_response: a strain tangent is armed, and the charge response carries displacements only "
+                                 "(aimnet_engine_set_strain_tangent(e, NULL) first)");
+    if (!r.pbc) return plan_reject(msg, n, "hvp: strain tangent: a strain direction needs a cell");
+    if (r.coulomb == AIMNET_COULOMB_EWALD)
+      return plan_reject(msg, n, "hvp: strain tangent: Ewald summation is not carried under strain (its k vectors move with the cell); "
+                                 "use DSF");
+    if (r.coulomb == AIMNET_COULOMB_PME)
+      return plan_reject(msg, n, "hvp: strain tangent: particle-mesh Ewald is not carried under strain (its mesh moves with the cell); "
+                                 "use DSF");
+    if (r.dftd3 != 0) return plan_reject(msg, n, "hvp: strain tangent: the DFT-D3 block is not carried under strain (options.dftd3 = 0)");
+    if (r.emb_on)
+      return plan_reject(msg, n, "hvp: strain tangent: the embedding term is not carried under strain (aimnet_engine_set_embedding(e, "
+                                 "NULL) first)");
+    if (!r.strain_arrays) return plan_reject(msg, n, "hvp: strain tangent: strain and dvirial are required");
+  }
   return 0;
 }
 
@@ -145,6 +165,9 @@ struct TangentPlan {
   // the primal potential mesh + field pass and the mesh tangents of every direction (pme.hip)
   bool pme, pme_qtot;       // pme_qtot: a two-channel model - the mesh sees alpha + beta, formed in a buffer of its own
   int pme_max_mesh, pme_max_parts;  // mesh points of one system's slice, blocks of its influence kernel (0: branch not taken)
+  // strain directions (armed): the pair tangents take r eps_k, the three centre-major pair kernels write the per-atom virial and its
+  // tangent (36 bytes per atom, 36 per direction and atom), summed per system in double after the backward sweep
+  bool strain;
 };
 
 inline TangentPlan tangent_plan(const TangentRequest& r) {
@@ -172,6 +195,7 @@ inline TangentPlan tangent_plan(const TangentRequest& r) {
   P.want_species = P.d3_block;
   P.bbox = !r.pbc && r.bbox_ok;
   P.embedding = hvp && r.emb_on && r.emb_tangent;
+  P.strain = hvp && r.strain_tangent;
   return P;
 }
 

@@ -599,7 +599,7 @@ class HipEngine(capacity.Capacities):
             dsf_rc: float = 15.0, dsf_alpha: float = 0.2, want_forces: bool = False,
             dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6,
             embedding: dict[str, Any] | None = None, pme_tangent: bool = False, d3_tangent: bool = False,
-            _d3_block_only: bool = False) -> dict[str, Any]:
+            _d3_block_only: bool = False, strain=None) -> dict[str, Any]:
         """Analytic Hessian-vector products (csrc/hvp.hip, aimnet_engine_hvp): vectors [K, N, 3] -> hv [K, N, 3] on the device
         (+ the forces of the same sweep with `want_forces`).  Inputs as `eval` (`pbc`: three flags or per-system [n_cell, 3]);
         with `dftd3` the dispersion block is added as a central difference of the D3 gradient inside the same call.  The K
@@ -617,7 +617,14 @@ class HipEngine(capacity.Capacities):
         (include/aimnet_hip.h, aimnet_embedding_tangent): a `potential` needs `potential_grad` and `potential_hess` [N,6] (xx, yy,
         zz, xy, xz, yz) or [N,3,3] beside it (zeros for a uniform field).  hv and the forces then include the term; `want_ext_hv`
         adds `ext_hv` [K, M, 3], the mixed atom-site block applied to the directions, `want_field` adds `ext_field` [N, 10] (phi,
-        grad phi, grad grad phi as the sweep used them, float64)."""
+        grad phi, grad grad phi as the sweep used them, float64).
+        `strain` [K, 3, 3] (or [3, 3], the same for every direction) arms the strain tangent (aimnet_engine_set_strain_tangent):
+        direction k is the path x -> x (1 + t strain_k) + t vectors_k, cell -> cell (1 + t strain_k), in the row-vector convention
+        of the stress; any 3 x 3 matrix, shared by the systems of the batch.  The result gains `dvirial` [K, n_mol, 3, 3], the
+        tangent of the un-normalised virial S_ab = sum_pairs r_a rbar_b (volume x stress) along the path, and `virial` [n_mol, 3, 3]
+        (both float64); hv is dG/dt along the same path.  Needs a cell; coulomb "none" or "dsf"; no dftd3, no embedding (the
+        engine refuses those before anything is launched).  36 bytes of workspace more per direction and atom; armed for the
+        sweeps of this call only."""
         import torch
 
         inp, t = self._inputs("hvp", coord, numbers, mol_idx, charge, cell, pbc)
@@ -662,6 +669,22 @@ class HipEngine(capacity.Capacities):
             arm(k0, kc)  # (the embedding's tangent struct names this sweep's slice of ext_hv)
             return self.lib.aimnet_engine_hvp(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
                                               hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None, *tail)
+        if strain is not None:
+            eps = torch.as_tensor(strain).to(device=dev, dtype=torch.float32)
+            if tuple(eps.shape) == (3, 3):
+                eps = eps.expand(K, 3, 3)
+            if tuple(eps.shape) != (K, 3, 3):
+                raise ValueError(f"HipEngine.hvp: strain must have shape ({K}, 3, 3) or (3, 3), got {tuple(eps.shape)}")
+            eps = eps.contiguous()
+            outs["dvirial"] = torch.empty(K, n_mol, 3, 3, dtype=torch.float64, device=dev)
+            outs["virial"] = torch.empty(n_mol, 3, 3, dtype=torch.float64, device=dev)
+            arm_rest = arm
+
+            def arm(k0, kc):  # noqa: F811  (the struct names this sweep's slice of the strains and of dvirial)
+                arm_rest(k0, kc)
+                st = _lib.StrainTangent(strain=eps[k0 : k0 + kc].data_ptr(), dvirial=outs["dvirial"][k0 : k0 + kc].data_ptr(),
+                                        virial=outs["virial"].data_ptr())
+                _lib.check(self.lib.aimnet_engine_set_strain_tangent(self._h, C.byref(st)), "aimnet_engine_set_strain_tangent")
         d3_armed = bool(d3_tangent) and dftd3 is not None
         if _d3_block_only:  # aimnet_debug_dftd3_tangent: the armed block alone (tests)
             if not d3_armed:
@@ -681,6 +704,9 @@ class HipEngine(capacity.Capacities):
                 _lib.check(self.lib.aimnet_engine_set_pme_tangent(self._h, 1), "aimnet_engine_set_pme_tangent")
             if d3_armed:  # (likewise)
                 _lib.check(self.lib.aimnet_engine_set_dftd3_tangent(self._h, 1), "aimnet_engine_set_dftd3_tangent")
+            if strain is not None:  # (likewise; armed without arrays, so that the size queries of the split see the armed state)
+                _lib.check(self.lib.aimnet_engine_set_strain_tangent(self._h, C.byref(_lib.StrainTangent())),
+                           "aimnet_engine_set_strain_tangent")
             self._tangent_sweeps("hvp", self.lib.aimnet_engine_hvp_workspace_bytes, rq, K, kmax, call)
         finally:
             if mesh:
@@ -689,6 +715,8 @@ class HipEngine(capacity.Capacities):
                 self.lib.aimnet_engine_set_dftd3_tangent(self._h, 0)
             if embedding is not None:
                 self.lib.aimnet_engine_set_embedding(self._h, None)  # (disarms the tangent too)
+            if strain is not None:
+                self.lib.aimnet_engine_set_strain_tangent(self._h, None)
         res = {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}
         res.update(outs)
         return res

@@ -394,6 +394,36 @@ int aimnet_engine_set_pme_tangent(aimnet_engine* e, int32_t on);
  * aimnet_engine_charge_response do not read the switch. */
 int aimnet_engine_set_dftd3_tangent(aimnet_engine* e, int32_t on);
 
+/* Strain directions in the analytic Hessian sweep: the derivatives in which the cell moves.  Arming is explicit, as for the mesh; unarmed
+ * (the default, and after s == NULL) every entry point does exactly what it did.  Armed, direction k of aimnet_engine_hvp is the pair
+ * (v_k [n_atoms][3], eps_k [3][3]) and defines, in the row-vector convention of AIMNET_STRESS, the path
+ *   x_i(t) = x_i (1 + t eps_k) + t v_k,i ,   cell(t) = cell (1 + t eps_k)          (eps_k: any 3 x 3 matrix, shared by all systems)
+ * The pair tangent becomes t_r = v_j - v_i + r_ij eps_k (independent of how the coordinates were wrapped); t_d and t_u follow as before.
+ * With G = dE/dx and S_ab = sum_pairs r_a rbar_b (the un-normalised virial of a system: volume x stress), the sweep returns
+ *   hv       [n_vec][n_atoms][3]     dG/dt at t = 0 (the argument of aimnet_engine_hvp, as always)
+ *   dvirial  [n_vec][n_mol][9]       dS/dt at t = 0, S(t) being the derivative with respect to a further scaling of the configuration at t
+ *   virial   [n_mol][9] or NULL      S itself
+ * The centre-major pair kernels (hvp_conv_bwd_kernel, hvp_coulomb_sr_kernel, the DSF mode of hvp_coulomb_lr_kernel) hold, per pair m of
+ * centre i, the increment inc_m of xbar_i and its tangent: the centre's share of S is -1/2 sum_m r_ij (x) inc_m, its tangent -1/2 sum_m
+ * (t_r (x) inc_m + r_ij (x) t_inc_m) - written per (direction, atom) as 9 floats (36 bytes of workspace per direction and atom, 36 per
+ * atom; aimnet_engine_hvp_workspace_bytes counts them while armed), then summed per system in double in a fixed order.  No atomics:
+ * hv and dvirial are bitwise repeatable, and nothing the armed form adds depends on how the directions are split into calls (the
+ * sweep's GEMMs choose their kernel by the number of stacked rows, as they do unarmed: calls that stay on one side of 256 rows agree
+ * bit for bit).
+ *   strain   [n_vec][9] device fp32, row-major eps_k (this call's slice: a caller that splits its directions arms again per call)
+ *   dvirial  [n_vec][n_mol][9] device fp64 (likewise this call's slice)
+ *   virial   [n_mol][9] device fp64 or NULL
+ * Rejected while armed, before anything is launched: aimnet_engine_charge_response; aimnet_engine_hvp without a cell, with
+ * AIMNET_COULOMB_EWALD or AIMNET_COULOMB_PME, with options.dftd3, with an embedding, or with strain or dvirial NULL.  Carried:
+ * AIMNET_COULOMB_NONE and AIMNET_COULOMB_DSF, one and two charge channels, partial and per-system pbc, n_cell 1 or n_mol.
+ * aimnet_engine_eval does not read the struct.  s == NULL disarms.  The struct is copied. */
+typedef struct aimnet_strain_tangent {
+  const float* strain;
+  double* dvirial;
+  double* virial;
+} aimnet_strain_tangent;
+int aimnet_engine_set_strain_tangent(aimnet_engine* e, const aimnet_strain_tangent* s);
+
 /* Bytes of scratch `aimnet_engine_eval` needs for the given problem size. */
 size_t aimnet_engine_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_cell,
                                      const aimnet_eval_options* opt);
