@@ -15,6 +15,7 @@ ABI_VERSION = 12  # AIMNET_ABI_VERSION of include/aimnet_hip.h this binding was 
 FORCES, STRESS = 1, 2
 COULOMB_NONE, COULOMB_SIMPLE, COULOMB_DSF, COULOMB_EWALD, COULOMB_PME = 0, 1, 2, 3, 4
 E_INVALID, E_HIP, E_WORKSPACE = -1, -2, -3
+STRAIN_TERMS = {"dftd3": 1}  # AIMNET_STRAIN_TERM_*: what an armed strain sweep may carry beside its own terms
 EMBED_CHUNK = 1024  # csrc/kernels.h: sites per chunk of the embedding field pass (the partition depends on n_ext and n_mol alone)
 EMBED_MAX_SLOTS = 64  # csrc/kernels.h: partial sums per atom, min(ceil(ceil(n_ext / n_mol) / EMBED_CHUNK), this)
 PROF_FAMILIES = ("nlist", "geom", "conv_fwd", "gemm", "pointwise", "coulomb", "unconcat", "conv_bwd", "other")
@@ -66,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "aimnet_engine_set_pme_tangent",
     "aimnet_engine_set_dftd3_tangent",
     "aimnet_engine_set_strain_tangent",
+    "aimnet_engine_set_strain_terms",
     "aimnet_neighbor_list",
     "aimnet_neighbor_list_workspace_bytes",
     "aimnet_conv_sv_2d_sp_fwd",
@@ -333,6 +335,8 @@ def load() -> C.CDLL:
     lib.aimnet_engine_set_dftd3_tangent.argtypes = [vp, C.c_int32]
     lib.aimnet_engine_set_strain_tangent.restype = C.c_int
     lib.aimnet_engine_set_strain_tangent.argtypes = [vp, C.POINTER(StrainTangent)]
+    lib.aimnet_engine_set_strain_terms.restype = C.c_int
+    lib.aimnet_engine_set_strain_terms.argtypes = [vp, C.c_uint32]
     # the conv kernels one launch at a time (tests/test_gpu_conv_kernels.py); `shifts` is a host pointer
     ci, cf = C.c_int, C.c_float
     lib.aimnet_debug_conv_fwd.restype = C.c_int

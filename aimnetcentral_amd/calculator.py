@@ -878,7 +878,8 @@ class AIMNet2Calculator:
         "analytic" - the tangent of the term's gradient on the one list (HipEngine.hvp(..., d3_tangent=True), csrc/d3.hip) at fp32
         round-off, 32 bytes per direction and atom.  Read by hessian_vector_product, eval(hessian=True) and
         AIMNet2ASE.get_hessian() while `hvp_method` is "analytic"; combinable with set_pme_hessian and set_embedding_hessian;
-        `hvp_method = "fd"` (and "pme" without its own arming) differences the forces and does not read it."""
+        `hvp_method = "fd"` (and "pme" without its own arming) differences the forces and does not read it.  `strain_response` and
+        `elastic_constants` carry the term in this mode only (the finite-difference block has no strain form)."""
         if mode not in (None, "analytic"):
             raise ValueError(f"set_dftd3_hessian: mode must be None or 'analytic', got {mode!r}")
         self._dftd3_hessian = mode
@@ -1066,8 +1067,12 @@ class AIMNet2Calculator:
         if lr.method in ("ewald", "pme"):
             raise NotImplementedError(f"{what}: Coulomb method '{lr.method}' is not carried by the strain tangent (its reciprocal-space "
                                       "sum moves with the cell); use set_lrcoulomb_method('dsf')")
+        d3_kw = {}
         if lr.dftd3 is not None:
-            raise NotImplementedError(f"{what}: the external DFT-D3 term is not carried by the strain tangent")
+            if self._dftd3_hessian != "analytic":
+                raise NotImplementedError(f"{what}: the external DFT-D3 term is carried by the strain tangent through its analytic "
+                                          "block only: call set_dftd3_hessian('analytic') first")
+            d3_kw = dict(d3_tangent=True, strain_terms=("dftd3",))
         n = d["coord"].shape[0]
         eps = torch.as_tensor(strains, dtype=torch.float32, device=self.device)
         if eps.shape[-2:] != (3, 3) or eps.ndim not in (2, 3):
@@ -1080,7 +1085,7 @@ class AIMNet2Calculator:
             raise ValueError(f"vectors must give one (N, 3) displacement per strain ({K}), got {tuple(v.shape)}")
         res = self.engine.hvp(d["coord"], d["numbers"], torch.zeros(n, dtype=torch.int32, device=self.device),
                               self._engine_charge(d["charge"], d.get("mult")), v, cell=cell, pbc=self._normalize_pbc(d.get("pbc"), 1),
-                              want_forces=True, strain=eps3, **lr.kwargs())
+                              want_forces=True, strain=eps3, **lr.kwargs(), **d3_kw)
         volume = float(torch.linalg.det(cell.reshape(3, 3).double()).abs())
         return d, res, volume, eps
 
@@ -1091,8 +1096,9 @@ class AIMNet2Calculator:
         convention of `eval`'s stress; any 3 x 3 matrix; `vectors` None: pure strains.  `strains` (3,3) or (K,3,3).  Returns, in
         `eval`'s units: `forces` (N,3), `stress` (3,3), `force_derivative` (K,N,3) = dF/dt and `stress_derivative` (K,3,3) =
         d stress/dt = (dS/dt - S tr strain) / V with S = V stress the virial (the volume moves along the path too).  No reference
-        counterpart.  Ewald, PME, external DFT-D3, an embedding, domain decomposition and hvp_method = "fd" raise
-        NotImplementedError."""
+        counterpart.  The external DFT-D3 term is carried after set_dftd3_hessian("analytic") (its analytic tangent block takes
+        the strain and adds its share of the virial and of its tangent; with the default finite-difference block it raises
+        NotImplementedError).  Ewald, PME, an embedding, domain decomposition and hvp_method = "fd" raise NotImplementedError."""
         d, res, vol, eps = self._strain_sweep(data, strains, vectors, "strain_response", validate_species)
         S = res["virial"][0]
         tr = eps.reshape(-1, 3, 3).double().diagonal(dim1=-2, dim2=-1).sum(-1)
@@ -1108,7 +1114,8 @@ class AIMNet2Calculator:
         for GPa): `born` (6,6), the clamped-ion term (1/V) d2E/ds ds of the ADDITIVE strain x -> x + x s (from the sweep's dS/dt by
         removing the first-order term strain^T S); `internal_strain` (N,3,6) = d2E / dx ds; `hessian` (N,3,N,3); `relaxed` (6,6) =
         born - (1/V) L^T H^+ L with the three translations projected out of H; and `forces`, `stress`, `volume`.  `born` and
-        `relaxed` are the elastic tensor only at zero stress and zero forces (elasticity.py says what they are otherwise)."""
+        `relaxed` are the elastic tensor only at zero stress and zero forces (elasticity.py says what they are otherwise).  A
+        model with the external DFT-D3 term needs set_dftd3_hessian("analytic") first, as `strain_response` does."""
         import torch
 
         from . import elasticity

@@ -494,6 +494,14 @@ int launch_dftd3(hipStream_t s, bool grad, bool stress, const float* xw, const i
 // once per pair and group.  Every direction owns its accumulators and runs the same instruction sequence whatever slot of a group it
 // sits in - ONE instantiation, no contraction in the bodies, every fused multiply-add written out - so H v^k is bitwise repeatable and
 // does not depend on how the directions are grouped or split into sweeps.  All sums are fp32 (a lane adds ~10 terms, wave_sum is a tree).
+//
+// STRAIN (armed, aimnet_engine_set_strain_terms with the strain tangent of hvp.hip): instantiations of their own, the unarmed ones are the
+// code they were.  Direction k carries eps_k [9] (row-major, wave-uniform: scalar registers) and the pair tangent becomes t_r = v_j - v_i
+// + r eps_k, whatever image the pair was found in; t_d, t_u and everything downstream keep their form.  The pair pass and the cn-force
+// pass add, beside the tangent increment t_inc of a pair to txbar, the centre's share of the virial tangent in the VirAcc convention of
+// hvp.hip (9 floats, row = component of r, column = component of the gradient), -1/2 sum_pairs (t_r (x) inc + r (x) t_inc), onto tvir
+// [K][N][9] - wave_sum, lane q of the group writes, no atomics.  The primal share -1/2 sum_pairs r (x) inc is launch_dftd3's
+// virial_atom (stress = true): the same layout and sign, added onto vir [N][9] by the block's primal launch.
 constexpr int D3_KG = 4;
 
 struct D3Dirs {  // the directions of this wave's group, clamped to the first one beyond K (computed, never stored)
@@ -508,15 +516,47 @@ struct D3Dirs {  // the directions of this wave's group, clamped to the first on
   }
 };
 
+// armed: eps of the group's directions; the addresses are uniform over the wave, so the 9 x D3_KG values live in scalar registers
+template <bool STRAIN>
+struct D3Eps {
+  float e[STRAIN ? D3_KG : 1][9];
+  __device__ __forceinline__ D3Eps(const D3Dirs& G, const float* __restrict__ strain) {
+    if constexpr (STRAIN) {
+#pragma unroll
+      for (int q = 0; q < D3_KG; ++q)
+#pragma unroll
+        for (int c = 0; c < 9; ++c) e[q][c] = strain[(size_t)G.k[q] * 9 + c];
+    }
+  }
+};
+// r eps (row vector times matrix), every fused multiply-add written out
+__device__ __forceinline__ void d3_r_eps(const float (&e)[9], float rx, float ry, float rz, float& ox, float& oy, float& oz) {
+#pragma clang fp contract(off)
+  ox = fmaf(rx, e[0], fmaf(ry, e[3], rz * e[6]));
+  oy = fmaf(rx, e[1], fmaf(ry, e[4], rz * e[7]));
+  oz = fmaf(rx, e[2], fmaf(ry, e[5], rz * e[8]));
+}
+// armed: a pair's share of the virial tangent, tw += t_r (x) (c2 u) + r (x) tf with tf = c1 u + c2 t_u the pair's tangent increment
+__device__ __forceinline__ void d3_tvir_add(float (&tw)[9], const float (&r)[3], const float (&tr)[3], const float (&inc)[3],
+                                            const float (&tf)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) tw[a * 3 + b] = fmaf(tr[a], inc[b], fmaf(r[a], tf[b], tw[a * 3 + b]));
+}
+
+template <bool STRAIN>
 __global__ __launch_bounds__(256) void d3_tcn_kernel(const float4* __restrict__ xs4, const int* __restrict__ mol_idx,
                                                     const float* __restrict__ cell, int n_cell, const int* __restrict__ nb_idx,
                                                     const int* __restrict__ nb_shift, const int* __restrict__ nb_cnt, int cap,
                                                     D3Tables T, float cutoff, int n_atoms, const float* __restrict__ tv, int K,
-                                                    float4* __restrict__ tcn4) {
+                                                    float4* __restrict__ tcn4, const float* __restrict__ strain) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n_atoms) return;
   const int lane = threadIdx.x & 63;
   const D3Dirs G(blockIdx.y, K);
+  const D3Eps<STRAIN> E(G, strain);
   const float* c = cell ? cell + (n_cell == 1 ? 0 : (size_t)mol_idx[i] * 9) : nullptr;
   const float4 x4 = xs4[i];
   const float xi = x4.x, yi = x4.y, zi = x4.z;
@@ -539,8 +579,16 @@ __global__ __launch_bounds__(256) void d3_tcn_kernel(const float4* __restrict__ 
     const float dsg = P.ok ? sg * (1.0f - sg) * (-16.0f * R * idb * idb) * BOHR_INV_F : 0.0f;  // d sigma / d d_ij per Angstrom
 #pragma unroll
     for (int q = 0; q < D3_KG; ++q) {
-      const float td = fmaf(P.ux, vj[q][0] - vi[q][0], fmaf(P.uy, vj[q][1] - vi[q][1], P.uz * (vj[q][2] - vi[q][2])));
-      acc[q] = fmaf(dsg, td, acc[q]);
+      if constexpr (STRAIN) {
+        float ex, ey, ez;
+        d3_r_eps(E.e[q], P.ux * P.d, P.uy * P.d, P.uz * P.d, ex, ey, ez);
+        const float dx = (vj[q][0] - vi[q][0]) + ex, dy = (vj[q][1] - vi[q][1]) + ey, dz = (vj[q][2] - vi[q][2]) + ez;
+        const float td = fmaf(P.ux, dx, fmaf(P.uy, dy, P.uz * dz));
+        acc[q] = fmaf(dsg, td, acc[q]);
+      } else {
+        const float td = fmaf(P.ux, vj[q][0] - vi[q][0], fmaf(P.uy, vj[q][1] - vi[q][1], P.uz * (vj[q][2] - vi[q][2])));
+        acc[q] = fmaf(dsg, td, acc[q]);
+      }
     }
   };
   for (int m = lane; m < cnt; m += 128) {  // two list slots per trip, all of their loads issued before the arithmetic
@@ -568,17 +616,20 @@ __global__ __launch_bounds__(256) void d3_tcn_kernel(const float4* __restrict__ 
   }
 }
 
+template <bool STRAIN>
 __global__ __launch_bounds__(256) void d3_tpair_kernel(const float4* __restrict__ xs4, const int* __restrict__ mol_idx,
                                                       const float* __restrict__ cell, int n_cell, const int* __restrict__ nb_idx,
                                                       const int* __restrict__ nb_shift, const int* __restrict__ nb_cnt, int cap,
                                                       D3Tables T, D3Params P3, float cutoff, int n_atoms,
                                                       const float* __restrict__ d3w, const float4* __restrict__ tcn4, int K,
-                                                      float4* __restrict__ tg4, float* __restrict__ txbar) {
+                                                      float4* __restrict__ tg4, float* __restrict__ txbar,
+                                                      const float* __restrict__ strain, float* __restrict__ tvir) {
   extern __shared__ float c6lds[];  // [4 waves][ns][25], as d3_pair_kernel
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + wid;
   if (i >= n_atoms) return;
   const D3Dirs G(blockIdx.y, K);
+  const D3Eps<STRAIN> E(G, strain);
   const int ns = T.ns;
   float* c6s = c6lds + (size_t)wid * ns * 25;
   const float4 x4 = xs4[i];
@@ -600,10 +651,15 @@ __global__ __launch_bounds__(256) void d3_tpair_kernel(const float4* __restrict_
   const int cnt = nb_cnt[i];
   float4 ti[D3_KG];  // (v_i, t_cn_i) of every direction
   float f[D3_KG][3], tg[D3_KG];
+  float tw[STRAIN ? D3_KG : 1][9];  // armed: the virial tangent share of every direction
 #pragma unroll
   for (int q = 0; q < D3_KG; ++q) {
     ti[q] = tcn4[(size_t)G.k[q] * n_atoms + i];
     f[q][0] = f[q][1] = f[q][2] = tg[q] = 0.0f;
+    if constexpr (STRAIN) {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) tw[q][c] = 0.0f;
+    }
   }
   const D3Cell C(c);
   const size_t row = (size_t)i * cap;
@@ -693,15 +749,32 @@ __global__ __launch_bounds__(256) void d3_tpair_kernel(const float4* __restrict_
     const float c6p2 = c6 * P2, p1a = P1 * Ai;
 #pragma unroll
     for (int q = 0; q < D3_KG; ++q) {
-      const float dx = tj[q].x - ti[q].x, dy = tj[q].y - ti[q].y, dz = tj[q].z - ti[q].z;
-      const float td = fmaf(P.ux, dx, fmaf(P.uy, dy, P.uz * dz));
-      const float tci = ti[q].w, tcj = tj[q].w;
-      const float tc6 = fmaf(Ai, tci, Aj * tcj);
-      const float c1 = fmaf(-tc6, P1, -(c6p2 * td));
-      f[q][0] = fmaf(c1, P.ux, fmaf(c2, fmaf(-P.ux, td, dx) * invd, f[q][0]));
-      f[q][1] = fmaf(c1, P.uy, fmaf(c2, fmaf(-P.uy, td, dy) * invd, f[q][1]));
-      f[q][2] = fmaf(c1, P.uz, fmaf(c2, fmaf(-P.uz, td, dz) * invd, f[q][2]));
-      tg[q] = fmaf(-p1a, td, fmaf(-P0, fmaf(Bii, tci, Bij * tcj), tg[q]));
+      if constexpr (STRAIN) {  // t_r = v_j - v_i + r eps; the pair's increments inc = c2 u, t_inc = c1 u + c2 t_u (times -2k at the end)
+        const float r[3] = {P.ux * P.d, P.uy * P.d, P.uz * P.d};
+        float ex, ey, ez;
+        d3_r_eps(E.e[q], r[0], r[1], r[2], ex, ey, ez);
+        const float tr[3] = {(tj[q].x - ti[q].x) + ex, (tj[q].y - ti[q].y) + ey, (tj[q].z - ti[q].z) + ez};
+        const float td = fmaf(P.ux, tr[0], fmaf(P.uy, tr[1], P.uz * tr[2]));
+        const float tci = ti[q].w, tcj = tj[q].w;
+        const float tc6 = fmaf(Ai, tci, Aj * tcj);
+        const float c1 = fmaf(-tc6, P1, -(c6p2 * td));
+        const float inc[3] = {c2 * P.ux, c2 * P.uy, c2 * P.uz};
+        const float tf[3] = {fmaf(c1, P.ux, c2 * (fmaf(-P.ux, td, tr[0]) * invd)), fmaf(c1, P.uy, c2 * (fmaf(-P.uy, td, tr[1]) * invd)),
+                             fmaf(c1, P.uz, c2 * (fmaf(-P.uz, td, tr[2]) * invd))};
+        f[q][0] += tf[0], f[q][1] += tf[1], f[q][2] += tf[2];
+        d3_tvir_add(tw[q], r, tr, inc, tf);
+        tg[q] = fmaf(-p1a, td, fmaf(-P0, fmaf(Bii, tci, Bij * tcj), tg[q]));
+      } else {
+        const float dx = tj[q].x - ti[q].x, dy = tj[q].y - ti[q].y, dz = tj[q].z - ti[q].z;
+        const float td = fmaf(P.ux, dx, fmaf(P.uy, dy, P.uz * dz));
+        const float tci = ti[q].w, tcj = tj[q].w;
+        const float tc6 = fmaf(Ai, tci, Aj * tcj);
+        const float c1 = fmaf(-tc6, P1, -(c6p2 * td));
+        f[q][0] = fmaf(c1, P.ux, fmaf(c2, fmaf(-P.ux, td, dx) * invd, f[q][0]));
+        f[q][1] = fmaf(c1, P.uy, fmaf(c2, fmaf(-P.uy, td, dy) * invd, f[q][1]));
+        f[q][2] = fmaf(c1, P.uz, fmaf(c2, fmaf(-P.uz, td, dz) * invd, f[q][2]));
+        tg[q] = fmaf(-p1a, td, fmaf(-P0, fmaf(Bii, tci, Bij * tcj), tg[q]));
+      }
     }
   };
   for (int m = lane; m < cnt; m += 128) {  // two list slots per trip, all of their loads issued before the arithmetic
@@ -742,19 +815,29 @@ __global__ __launch_bounds__(256) void d3_tpair_kernel(const float4* __restrict_
       txbar[o * 3 + 2] += -2.0f * HALF_HARTREE_F * f2;
       tg4[o] = make_float4(ti[q].x, ti[q].y, ti[q].z, 2.0f * HALF_HARTREE_F * g);
     }
+    if constexpr (STRAIN) {  // -1/2 (t_r (x) inc + r (x) t_inc) with the -2k of the increments: k times the sums
+#pragma unroll
+      for (int c = 0; c < 9; ++c) {
+        const float w = wave_sum(tw[q][c]);
+        if (lane == q && G.ok[q]) tvir[((size_t)G.k[q] * n_atoms + i) * 9 + c] += HALF_HARTREE_F * w;
+      }
+    }
   }
 }
 
+template <bool STRAIN>
 __global__ __launch_bounds__(256) void d3_tcnforce_kernel(const float4* __restrict__ xs4, const int* __restrict__ mol_idx,
                                                          const float* __restrict__ cell, int n_cell,
                                                          const int* __restrict__ nb_idx, const int* __restrict__ nb_shift,
                                                          const int* __restrict__ nb_cnt, int cap, D3Tables T, float cutoff,
                                                          int n_atoms, const float* __restrict__ dEdcn,
-                                                         const float4* __restrict__ tg4, int K, float* __restrict__ txbar) {
+                                                         const float4* __restrict__ tg4, int K, float* __restrict__ txbar,
+                                                         const float* __restrict__ strain, float* __restrict__ tvir) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n_atoms) return;
   const int lane = threadIdx.x & 63;
   const D3Dirs G(blockIdx.y, K);
+  const D3Eps<STRAIN> E(G, strain);
   const float* c = cell ? cell + (n_cell == 1 ? 0 : (size_t)mol_idx[i] * 9) : nullptr;
   const float4 x4 = xs4[i];
   const float xi = x4.x, yi = x4.y, zi = x4.z;
@@ -763,10 +846,15 @@ __global__ __launch_bounds__(256) void d3_tcnforce_kernel(const float4* __restri
   const int cnt = nb_cnt[i];
   float4 ti[D3_KG];  // (v_i, t_G_i)
   float f[D3_KG][3];
+  float tw[STRAIN ? D3_KG : 1][9];  // armed: the virial tangent share of every direction
 #pragma unroll
   for (int q = 0; q < D3_KG; ++q) {
     ti[q] = tg4[(size_t)G.k[q] * n_atoms + i];
     f[q][0] = f[q][1] = f[q][2] = 0.0f;
+    if constexpr (STRAIN) {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) tw[q][c] = 0.0f;
+    }
   }
   const D3Cell C(c);
   const size_t row = (size_t)i * cap;
@@ -783,12 +871,26 @@ __global__ __launch_bounds__(256) void d3_tcnforce_kernel(const float4* __restri
     const float invd = frcp(P.d);
 #pragma unroll
     for (int q = 0; q < D3_KG; ++q) {
-      const float dx = tj[q].x - ti[q].x, dy = tj[q].y - ti[q].y, dz = tj[q].z - ti[q].z;
-      const float td = fmaf(P.ux, dx, fmaf(P.uy, dy, P.uz * dz));
-      const float c1 = fmaf(ti[q].w + tj[q].w, s1, gs2 * td);
-      f[q][0] = fmaf(c1, P.ux, fmaf(c2, fmaf(-P.ux, td, dx) * invd, f[q][0]));
-      f[q][1] = fmaf(c1, P.uy, fmaf(c2, fmaf(-P.uy, td, dy) * invd, f[q][1]));
-      f[q][2] = fmaf(c1, P.uz, fmaf(c2, fmaf(-P.uz, td, dz) * invd, f[q][2]));
+      if constexpr (STRAIN) {  // as in the pair pass; the increments carry -1 here
+        const float r[3] = {P.ux * P.d, P.uy * P.d, P.uz * P.d};
+        float ex, ey, ez;
+        d3_r_eps(E.e[q], r[0], r[1], r[2], ex, ey, ez);
+        const float tr[3] = {(tj[q].x - ti[q].x) + ex, (tj[q].y - ti[q].y) + ey, (tj[q].z - ti[q].z) + ez};
+        const float td = fmaf(P.ux, tr[0], fmaf(P.uy, tr[1], P.uz * tr[2]));
+        const float c1 = fmaf(ti[q].w + tj[q].w, s1, gs2 * td);
+        const float inc[3] = {c2 * P.ux, c2 * P.uy, c2 * P.uz};
+        const float tf[3] = {fmaf(c1, P.ux, c2 * (fmaf(-P.ux, td, tr[0]) * invd)), fmaf(c1, P.uy, c2 * (fmaf(-P.uy, td, tr[1]) * invd)),
+                             fmaf(c1, P.uz, c2 * (fmaf(-P.uz, td, tr[2]) * invd))};
+        f[q][0] += tf[0], f[q][1] += tf[1], f[q][2] += tf[2];
+        d3_tvir_add(tw[q], r, tr, inc, tf);
+      } else {
+        const float dx = tj[q].x - ti[q].x, dy = tj[q].y - ti[q].y, dz = tj[q].z - ti[q].z;
+        const float td = fmaf(P.ux, dx, fmaf(P.uy, dy, P.uz * dz));
+        const float c1 = fmaf(ti[q].w + tj[q].w, s1, gs2 * td);
+        f[q][0] = fmaf(c1, P.ux, fmaf(c2, fmaf(-P.ux, td, dx) * invd, f[q][0]));
+        f[q][1] = fmaf(c1, P.uy, fmaf(c2, fmaf(-P.uy, td, dy) * invd, f[q][1]));
+        f[q][2] = fmaf(c1, P.uz, fmaf(c2, fmaf(-P.uz, td, dz) * invd, f[q][2]));
+      }
     }
   };
   for (int m = lane; m < cnt; m += 128) {
@@ -817,21 +919,46 @@ __global__ __launch_bounds__(256) void d3_tcnforce_kernel(const float4* __restri
       txbar[o + 1] -= f1;
       txbar[o + 2] -= f2;
     }
+    if constexpr (STRAIN) {  // -1/2 (t_r (x) inc + r (x) t_inc) with the -1 of the increments
+#pragma unroll
+      for (int c = 0; c < 9; ++c) {
+        const float w = wave_sum(tw[q][c]);
+        if (lane == q && G.ok[q]) tvir[((size_t)G.k[q] * n_atoms + i) * 9 + c] += 0.5f * w;
+      }
+    }
   }
 }
 
 int launch_dftd3_tangent(hipStream_t s, const int* mol_idx, const float* cell, int n_cell, const int* nb_idx, const int* nb_shift,
                          const int* nb_cnt, int cap, D3Tables T, D3Params P, float cutoff, int n_atoms, const float4* xs4,
-                         const float* d3w, const float* dEdcn, const float* tv, int n_dir, float4* tcn4, float4* tg4, float* txbar) {
+                         const float* d3w, const float* dEdcn, const float* tv, int n_dir, float4* tcn4, float4* tg4, float* txbar,
+                         const float* strain, float* tvir) {
   const dim3 grid(ceil_div(n_atoms, 4), ceil_div(n_dir, D3_KG)), block(256);
-  hipLaunchKernelGGL(d3_tcn_kernel, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff, n_atoms, tv,
-                     n_dir, tcn4);
+  const size_t lds = (size_t)4 * T.ns * 25 * sizeof(float);
+  if (strain) {  // armed (plan: d3_strain): the instantiations that take r eps and write the virial tangent
+    if (!tvir || !cell) {
+      set_last_error("hvp: the DFT-D3 block under strain needs a cell and the virial rows");
+      return -1;
+    }
+    hipLaunchKernelGGL(d3_tcn_kernel<true>, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff,
+                       n_atoms, tv, n_dir, tcn4, strain);
+    AIMNET_LAUNCH_CHECK();
+    hipLaunchKernelGGL(d3_tpair_kernel<true>, grid, block, lds, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, P, cutoff,
+                       n_atoms, d3w, tcn4, n_dir, tg4, txbar, strain, tvir);
+    AIMNET_LAUNCH_CHECK();
+    hipLaunchKernelGGL(d3_tcnforce_kernel<true>, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff,
+                       n_atoms, dEdcn, tg4, n_dir, txbar, strain, tvir);
+    AIMNET_LAUNCH_CHECK();
+    return 0;
+  }
+  hipLaunchKernelGGL(d3_tcn_kernel<false>, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff,
+                     n_atoms, tv, n_dir, tcn4, nullptr);
   AIMNET_LAUNCH_CHECK();
-  hipLaunchKernelGGL(d3_tpair_kernel, grid, block, (size_t)4 * T.ns * 25 * sizeof(float), s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift,
-                     nb_cnt, cap, T, P, cutoff, n_atoms, d3w, tcn4, n_dir, tg4, txbar);
+  hipLaunchKernelGGL(d3_tpair_kernel<false>, grid, block, lds, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, P, cutoff,
+                     n_atoms, d3w, tcn4, n_dir, tg4, txbar, nullptr, nullptr);
   AIMNET_LAUNCH_CHECK();
-  hipLaunchKernelGGL(d3_tcnforce_kernel, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff, n_atoms,
-                     dEdcn, tg4, n_dir, txbar);
+  hipLaunchKernelGGL(d3_tcnforce_kernel<false>, grid, block, 0, s, xs4, mol_idx, cell, n_cell, nb_idx, nb_shift, nb_cnt, cap, T, cutoff,
+                     n_atoms, dEdcn, tg4, n_dir, txbar, nullptr, nullptr);
   AIMNET_LAUNCH_CHECK();
   return 0;
 }

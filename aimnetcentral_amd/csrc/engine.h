@@ -187,6 +187,7 @@ struct aimnet_engine {
   // (tangent_plan.h: strain); a copy of the caller's struct
   bool strain_tangent_on = false;
   aimnet_strain_tangent strain_tangent{};
+  uint32_t strain_terms = 0;  // aimnet_engine_set_strain_terms: AIMNET_STRAIN_TERM_* the armed strain sweep may carry beside its own
   float* unit_cell = nullptr;  // 3 x 3 identity (device): "cell" of the virial sums of a decomposed evaluation
   double* sae;
   // species slots of the pass-0 moment backward: slot = rank of the atomic number among the embedding rows that

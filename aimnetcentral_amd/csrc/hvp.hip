@@ -1476,6 +1476,14 @@ int Tangent::d3_block(bool want_forces) {
     float* g = want_forces ? W.xbar : W.d3c_g;
     if (!want_forces) AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_g, 0, (size_t)N * 3 * sizeof(float), s));
     AIMNET_HIP_CHECK(hipMemsetAsync(W.d3c_e, 0, (size_t)N * sizeof(double), s));
+    if (P.d3_strain) {
+      // under strain: the same primal launches with their per-atom virial (the VirAcc layout and sign: d3.hip, d3_store) added onto the
+      // rows the backward sweep wrote, then the armed instantiations of the three passes, which add the tangent rows
+      RC(launch_dftd3(s, true, true, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp,
+                      opt->d3_cutoff, N, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, g, W.vir, false, cp, nullptr, nullptr));
+      return launch_dftd3_tangent(s, mol_c, in->cell, n_cell, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp, opt->d3_cutoff, N,
+                                  W.d3c_xs, W.d3c_w, W.d3c_dEdcn, vectors, K, W.d3t_cn, W.d3t_g, W.txbar, strain, W.tvir);
+    }
     RC(launch_dftd3(s, true, false, W.nl.xw, mol_c, in->cell, n_cell, W.aslot, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp,
                     opt->d3_cutoff, N, W.d3c_xs, W.d3c_w, W.d3c_dEdcn, W.d3c_e, g, nullptr, false, cp, nullptr, nullptr));
     return launch_dftd3_tangent(s, mol_c, in->cell, n_cell, W.d3_idx, W.d3_shift, W.d3_cnt, cap_d3, e->d3, dp, opt->d3_cutoff, N,
@@ -1550,6 +1558,7 @@ TangentRequest tangent_request(TangentEntry entry, const aimnet_engine* e, int N
   r.d3_tangent = entry == TangentEntry::Hvp && e->d3_tangent_on;
   r.strain_tangent = e->strain_tangent_on;  // (both entries: charge_response refuses an armed engine)
   r.strain_arrays = e->strain_tangent.strain && e->strain_tangent.dvirial;
+  r.strain_d3 = entry == TangentEntry::Hvp && (e->strain_terms & AIMNET_STRAIN_TERM_DFTD3) != 0;
   if (!in) return r;
   r.pbc = in->cell != nullptr; r.n_cell = in->n_cell;
   const bool mesh_armed = opt->coulomb == AIMNET_COULOMB_PME && r.pme_tangent;
@@ -1603,6 +1612,17 @@ int aimnet_engine_set_strain_tangent(aimnet_engine* e, const aimnet_strain_tange
   if (!e) return AIMNET_E_INVALID;
   e->strain_tangent_on = s != nullptr;
   e->strain_tangent = s ? *s : aimnet_strain_tangent{};  // (checked by every call while armed, tangent_plan.h)
+  if (!s) e->strain_terms = 0;  // disarming clears the terms too; arming with a struct leaves them
+  return AIMNET_OK;
+}
+
+int aimnet_engine_set_strain_terms(aimnet_engine* e, uint32_t mask) {
+  if (!e) return AIMNET_E_INVALID;
+  if (mask & ~(uint32_t)AIMNET_STRAIN_TERM_DFTD3) {
+    set_last_error("set_strain_terms: unknown bits in the mask (%#x): AIMNET_STRAIN_TERM_DFTD3 is the one term", mask);
+    return AIMNET_E_INVALID;
+  }
+  e->strain_terms = mask;
   return AIMNET_OK;
 }
 
@@ -1644,6 +1664,10 @@ int aimnet_debug_dftd3_tangent(aimnet_engine* e, const aimnet_inputs* in, const 
   RC(t.lists());  // (the block reads the wrapped coordinates, the species slots and the bins of the sweep's own list build)
   AIMNET_HIP_CHECK(hipMemsetAsync(t.W.txbar, 0, t.kn() * 3 * sizeof(float), t.s));
   AIMNET_HIP_CHECK(hipMemsetAsync(t.W.xbar, 0, (size_t)t.N * 3 * sizeof(float), t.s));
+  if (t.P.d3_strain) {  // under strain the block's own virial and virial tangent come back alone too
+    AIMNET_HIP_CHECK(hipMemsetAsync(t.W.vir, 0, (size_t)t.N * 9 * sizeof(float), t.s));
+    AIMNET_HIP_CHECK(hipMemsetAsync(t.W.tvir, 0, t.kn() * 9 * sizeof(float), t.s));
+  }
   RC(t.d3_block(forces != nullptr));
   return t.write_hvp(hv, forces);
 }

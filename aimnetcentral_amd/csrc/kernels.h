@@ -415,7 +415,10 @@ int launch_dftd3(hipStream_t s, bool grad, bool stress, const float* xw, const i
 // independent of how the directions are split over calls.
 int launch_dftd3_tangent(hipStream_t s, const int* mol_idx, const float* cell, int n_cell, const int* nb_idx, const int* nb_shift,
                          const int* nb_cnt, int cap, D3Tables T, D3Params P, float cutoff, int n_atoms, const float4* xs4,
-                         const float* d3w, const float* dEdcn, const float* tv, int n_dir, float4* tcn4, float4* tg4, float* txbar);
+                         const float* d3w, const float* dEdcn, const float* tv, int n_dir, float4* tcn4, float4* tg4, float* txbar,
+                         const float* strain = nullptr, float* tvir = nullptr);
+// strain [n_dir][9] != NULL (hvp.hip, plan: d3_strain; needs a cell): the pair tangents take r eps and the centre's share of the virial
+// tangent is ADDED onto tvir [n_dir][n_atoms][9]; the primal share is launch_dftd3's virial_atom (stress = true)
 // Independent work that rides on the SR-Coulomb launch (role-dispatched blocks behind the pair blocks; a kernel boundary costs
 // 4-5 us on the device): the last energy-head layer k -> 1 with its adjoint seed zbar = w * d (n_head_blocks = ceil(n_atoms / 4), 0 = none) and the charge stream of the
 // list-free DSF walk (n_stream_blocks = ceil(n_atoms / 256), 0 = none; xs / xq = NlistBuffers::xs / sorted_tmp_xq)

@@ -37,6 +37,9 @@ struct TangentRequest {
   // aimnet_engine_set_strain_tangent armed the sweep for strain directions (read by both entries: charge_response refuses it); then
   // strain_arrays: the struct's strain and dvirial are both given
   bool strain_tangent, strain_arrays;
+  // aimnet_engine_set_strain_terms named AIMNET_STRAIN_TERM_DFTD3: the armed strain sweep may carry the dispersion block (read with
+  // strain_tangent and dftd3 != 0 only), by its analytic tangent (d3_tangent).  Last, so that `TangentRequest rq{}` leaves it false
+  bool strain_d3;
 };
 
 // ---- argument checks: 0, or AIMNET_E_INVALID with the message in msg.  Nothing has been launched when they run --------------------
@@ -132,7 +135,11 @@ inline int tangent_validate(const TangentRequest& r, char* msg, size_t n) {
     if (r.coulomb == AIMNET_COULOMB_PME)
       return plan_reject(msg, n, "hvp: strain tangent: particle-mesh Ewald is not carried under strain (its mesh moves with the cell); "
                                  "use DSF");
-    if (r.dftd3 != 0) return plan_reject(msg, n, "hvp: strain tangent: the DFT-D3 block is not carried under strain (options.dftd3 = 0)");
+    if (r.dftd3 != 0 && !r.strain_d3)
+      return plan_reject(msg, n, "hvp: strain tangent: the DFT-D3 block is not carried under strain (options.dftd3 = 0)");
+    if (r.dftd3 != 0 && !r.d3_tangent)
+      return plan_reject(msg, n, "hvp: strain tangent: the DFT-D3 block is carried under strain by its analytic tangent only "
+                                 "(aimnet_engine_set_dftd3_tangent(e, 1))");
     if (r.emb_on)
       return plan_reject(msg, n, "hvp: strain tangent: the embedding term is not carried under strain (aimnet_engine_set_embedding(e, "
                                  "NULL) first)");
@@ -168,6 +175,9 @@ struct TangentPlan {
   // strain directions (armed): the pair tangents take r eps_k, the three centre-major pair kernels write the per-atom virial and its
   // tangent (36 bytes per atom, 36 per direction and atom), summed per system in double after the backward sweep
   bool strain;
+  // ... with the dispersion block (armed: strain, d3_analytic and aimnet_engine_set_strain_terms): the three tangent passes of d3.hip
+  // take r eps_k and add their share onto the same virial rows; no bytes of its own
+  bool d3_strain;
 };
 
 inline TangentPlan tangent_plan(const TangentRequest& r) {
@@ -196,6 +206,7 @@ inline TangentPlan tangent_plan(const TangentRequest& r) {
   P.bbox = !r.pbc && r.bbox_ok;
   P.embedding = hvp && r.emb_on && r.emb_tangent;
   P.strain = hvp && r.strain_tangent;
+  P.d3_strain = P.strain && P.d3_analytic && r.strain_d3;
   return P;
 }
 

@@ -599,7 +599,7 @@ class HipEngine(capacity.Capacities):
             dsf_rc: float = 15.0, dsf_alpha: float = 0.2, want_forces: bool = False,
             dftd3: dict[str, float] | None = None, ewald_accuracy: float = 1e-6,
             embedding: dict[str, Any] | None = None, pme_tangent: bool = False, d3_tangent: bool = False,
-            _d3_block_only: bool = False, strain=None) -> dict[str, Any]:
+            _d3_block_only: bool = False, strain=None, strain_terms: tuple[str, ...] = ()) -> dict[str, Any]:
         """Analytic Hessian-vector products (csrc/hvp.hip, aimnet_engine_hvp): vectors [K, N, 3] -> hv [K, N, 3] on the device
         (+ the forces of the same sweep with `want_forces`).  Inputs as `eval` (`pbc`: three flags or per-system [n_cell, 3]);
         with `dftd3` the dispersion block is added as a central difference of the D3 gradient inside the same call.  The K
@@ -622,9 +622,12 @@ class HipEngine(capacity.Capacities):
         direction k is the path x -> x (1 + t strain_k) + t vectors_k, cell -> cell (1 + t strain_k), in the row-vector convention
         of the stress; any 3 x 3 matrix, shared by the systems of the batch.  The result gains `dvirial` [K, n_mol, 3, 3], the
         tangent of the un-normalised virial S_ab = sum_pairs r_a rbar_b (volume x stress) along the path, and `virial` [n_mol, 3, 3]
-        (both float64); hv is dG/dt along the same path.  Needs a cell; coulomb "none" or "dsf"; no dftd3, no embedding (the
-        engine refuses those before anything is launched).  36 bytes of workspace more per direction and atom; armed for the
-        sweeps of this call only."""
+        (both float64); hv is dG/dt along the same path.  Needs a cell; coulomb "none" or "dsf"; no embedding; `dftd3` only as
+        named next (the engine refuses the others before anything is launched).  36 bytes of workspace more per direction and
+        atom; armed for the sweeps of this call only.
+        `strain_terms=("dftd3",)` (with `strain`, `dftd3` and `d3_tangent=True`) lets the armed sweep carry the dispersion block
+        (aimnet_engine_set_strain_terms): its pair tangents take r strain_k and it adds its share to `virial` and `dvirial`; no
+        workspace of its own.  With the finite-difference block (`d3_tangent=False`) the engine refuses."""
         import torch
 
         inp, t = self._inputs("hvp", coord, numbers, mol_idx, charge, cell, pbc)
@@ -669,6 +672,13 @@ class HipEngine(capacity.Capacities):
             arm(k0, kc)  # (the embedding's tangent struct names this sweep's slice of ext_hv)
             return self.lib.aimnet_engine_hvp(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
                                               hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None, *tail)
+        terms_mask = 0
+        for name in strain_terms:
+            if name not in _lib.STRAIN_TERMS:
+                raise ValueError(f"HipEngine.hvp: unknown strain term {name!r} (known: {sorted(_lib.STRAIN_TERMS)})")
+            terms_mask |= _lib.STRAIN_TERMS[name]
+        if terms_mask and strain is None:
+            raise ValueError("HipEngine.hvp: strain_terms names what a strain sweep carries: it needs strain")
         if strain is not None:
             eps = torch.as_tensor(strain).to(device=dev, dtype=torch.float32)
             if tuple(eps.shape) == (3, 3):
@@ -691,6 +701,8 @@ class HipEngine(capacity.Capacities):
                 raise ValueError("HipEngine.hvp: the dispersion block alone needs dftd3 and d3_tangent=True")
 
             def call(opt, k0, kc, *tail):  # noqa: F811
+                if strain is not None:  # (this sweep's slice of the strains and of dvirial)
+                    arm(k0, kc)
                 return self.lib.aimnet_debug_dftd3_tangent(self._h, C.byref(inp), C.byref(opt), vectors[k0 : k0 + kc].data_ptr(), kc,
                                                            hv[k0 : k0 + kc].data_ptr(), f_out.data_ptr() if f_out is not None else None,
                                                            *tail)
@@ -707,6 +719,8 @@ class HipEngine(capacity.Capacities):
             if strain is not None:  # (likewise; armed without arrays, so that the size queries of the split see the armed state)
                 _lib.check(self.lib.aimnet_engine_set_strain_tangent(self._h, C.byref(_lib.StrainTangent())),
                            "aimnet_engine_set_strain_tangent")
+            if terms_mask:  # (likewise; arming with a struct leaves the mask, disarming below clears it)
+                _lib.check(self.lib.aimnet_engine_set_strain_terms(self._h, terms_mask), "aimnet_engine_set_strain_terms")
             self._tangent_sweeps("hvp", self.lib.aimnet_engine_hvp_workspace_bytes, rq, K, kmax, call)
         finally:
             if mesh:
@@ -715,6 +729,8 @@ class HipEngine(capacity.Capacities):
                 self.lib.aimnet_engine_set_dftd3_tangent(self._h, 0)
             if embedding is not None:
                 self.lib.aimnet_engine_set_embedding(self._h, None)  # (disarms the tangent too)
+            if terms_mask:
+                self.lib.aimnet_engine_set_strain_terms(self._h, 0)
             if strain is not None:
                 self.lib.aimnet_engine_set_strain_tangent(self._h, None)
         res = {"hv": hv, "forces": f_out} if f_out is not None else {"hv": hv}

@@ -390,8 +390,9 @@ int aimnet_engine_set_pme_tangent(aimnet_engine* e, int32_t on);
  * per (atom, group of four directions), no atomics: H_d3 v is bitwise repeatable and independent of how the directions are grouped or
  * split over calls.  Armed, n_vec <= 65535 and the 2^31 limit of the replicas is gone; the workspace holds 32 bytes per (direction,
  * atom) for the block instead of 4 (8 max_nb_d3 + 60) (aimnet_engine_hvp_workspace_bytes counts what the engine's state asks for).
- * Caller-supplied matrices stay refused; strain tangents and domain decomposition are not carried.  aimnet_engine_eval and
- * aimnet_engine_charge_response do not read the switch. */
+ * Caller-supplied matrices stay refused; domain decomposition is not carried.  Under a strain tangent the armed block is carried once
+ * aimnet_engine_set_strain_terms names it (below: Delta gains r eps_k, and the block adds its share of the virial and of its tangent);
+ * the finite-difference block is not.  aimnet_engine_eval and aimnet_engine_charge_response do not read the switch. */
 int aimnet_engine_set_dftd3_tangent(aimnet_engine* e, int32_t on);
 
 /* Strain directions in the analytic Hessian sweep: the derivatives in which the cell moves.  Arming is explicit, as for the mesh; unarmed
@@ -414,15 +415,33 @@ int aimnet_engine_set_dftd3_tangent(aimnet_engine* e, int32_t on);
  *   dvirial  [n_vec][n_mol][9] device fp64 (likewise this call's slice)
  *   virial   [n_mol][9] device fp64 or NULL
  * Rejected while armed, before anything is launched: aimnet_engine_charge_response; aimnet_engine_hvp without a cell, with
- * AIMNET_COULOMB_EWALD or AIMNET_COULOMB_PME, with options.dftd3, with an embedding, or with strain or dvirial NULL.  Carried:
+ * AIMNET_COULOMB_EWALD or AIMNET_COULOMB_PME, with options.dftd3 (unless the term is named, below), with an embedding, or with strain or
+ * dvirial NULL.  Carried:
  * AIMNET_COULOMB_NONE and AIMNET_COULOMB_DSF, one and two charge channels, partial and per-system pbc, n_cell 1 or n_mol.
- * aimnet_engine_eval does not read the struct.  s == NULL disarms.  The struct is copied. */
+ * aimnet_engine_eval does not read the struct.  s == NULL disarms (and clears the terms below).  The struct is copied.
+ *
+ * Terms beside the sweep's own.  aimnet_engine_set_strain_terms(e, mask) names the external terms an armed strain sweep may carry; the
+ * default is 0 (every refusal above as it is), s == NULL above sets it back to 0, arming with a struct leaves it, and bits that are
+ * not defined give AIMNET_E_INVALID.
+ *   AIMNET_STRAIN_TERM_DFTD3   options.dftd3 is accepted under strain when the analytic dispersion block is armed as well
+ *                              (aimnet_engine_set_dftd3_tangent(e, 1); with the finite-difference block the request is refused with a
+ *                              message of its own).  The three tangent passes of csrc/d3.hip run as instantiations of their own: for
+ *                              the ordered pair (i, j) seen from centre i, Delta = v_j - v_i + r_ij eps_k in the formulas of
+ *                              aimnet_engine_set_dftd3_tangent, nothing else changes form.  The pair pass and the cn-force pass hold
+ *                              each pair's increment inc = a u to dE/dx_i and its tangent t_inc, and add -1/2 sum (Delta (x) inc +
+ *                              r (x) t_inc) onto the virial tangent rows of the sweep; the primal share -1/2 sum r (x) inc is the
+ *                              per-atom virial of the evaluation's own D3 launches.  wave_sum, no atomics, no workspace beyond the 36
+ *                              bytes of the strain sweep and the 32 of the armed block per direction and atom; hv and dvirial stay
+ *                              bitwise repeatable and independent of how the directions are grouped or split over calls.
+ * Ewald summation and the mesh get bits of their own when they are carried. */
 typedef struct aimnet_strain_tangent {
   const float* strain;
   double* dvirial;
   double* virial;
 } aimnet_strain_tangent;
 int aimnet_engine_set_strain_tangent(aimnet_engine* e, const aimnet_strain_tangent* s);
+#define AIMNET_STRAIN_TERM_DFTD3 1u
+int aimnet_engine_set_strain_terms(aimnet_engine* e, uint32_t mask);
 
 /* Bytes of scratch `aimnet_engine_eval` needs for the given problem size. */
 size_t aimnet_engine_workspace_bytes(const aimnet_engine* e, int32_t n_atoms, int32_t n_mol, int32_t n_cell,
@@ -618,7 +637,9 @@ int aimnet_debug_pme_tangent(const float* xw, const float* q, const float* tq, c
  * (inputs: coordinates, numbers, mol_idx, cell; options: dftd3 = 1 with its parameters and max_nb_d3; vectors [n_vec][n][3]); the
  * engine must be armed (aimnet_engine_set_dftd3_tangent) and hold the tables, the workspace is aimnet_engine_hvp_workspace_bytes'.  It
  * builds the sweep's lists, runs the primal D3 passes at x and the three tangent passes, and writes hv = H_d3 v [n_vec][n][3] and, if
- * given, forces = the D3 forces [n][3] - no model, no Coulomb term.  status as aimnet_engine_hvp (status[4], status[5]: the D3 rows). */
+ * given, forces = the D3 forces [n][3] - no model, no Coulomb term.  status as aimnet_engine_hvp (status[4], status[5]: the D3 rows).
+ * With a strain tangent armed and AIMNET_STRAIN_TERM_DFTD3 named, the directions carry their strains and the struct's dvirial and
+ * virial receive the block's share alone. */
 int aimnet_debug_dftd3_tangent(aimnet_engine* e, const aimnet_inputs* in, const aimnet_eval_options* opt, const float* vectors,
                                int32_t n_vec, float* hv, float* forces, int32_t* status, void* workspace, size_t workspace_bytes,
                                void* hip_stream);
